@@ -12,6 +12,13 @@ value = proofs / hour over all ranks.  What is timed is what is checked: proofs 
 for byte with the oracle's create_proof of the host-synthesised witness of the same image, and pairing-verified.
 
     python bench.py --gpus N --steps K --warmup W [--mode replicas|shard-msm|msm-only] [--model tiny|small|medium|large]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: its `roofline` comes from the timed steps' own kernel
+events.  The tail legs below (the oracle check, the one-prover pass, the from-resident pass, the lone-proof probes, the other
+three models, the CPU baseline) run with --full only.  --dump-outputs DIR writes what the last timed step handed its caller
+(proof bytes, public outputs; msm-only: the sums) as DIR/<name>.npy in float32 / float64, so that two builds can be compared
+output for output: the inputs are seeded, the same arguments give the same ones.
 
 stdout carries ONE compact JSON line (< 4 KB: the contract keys, `roofline`, `cpu_baseline`, the lone-proof latencies, one
 figure per other model); everything else -- per-kernel tables, families, samples, prose -- goes to bench_detail.json next to
@@ -656,6 +663,42 @@ def image_pool(c: Circuit, count: int = 64) -> np.ndarray:
     return np.stack([real] + [rng.integers(0, 256, size=real.shape, dtype=real.dtype) for _ in range(count - 1)]).reshape(count, -1)
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_LIMIT = 63 << 20  # bytes of all the files of one dump together (headers included: under 64 MiB)
+
+
+def words_f64(a: np.ndarray) -> np.ndarray:
+    """uint64 limbs -> their 32-bit halves as float64 (exact), trailing axis doubled"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return a.view(np.uint32).astype(np.float64).reshape(a.shape[:-1] + (2 * a.shape[-1],))
+
+
+def write_outputs(path: str, arrays: dict, limit: int = DUMP_LIMIT) -> dict:
+    """arrays: name -> float32 / float64 array, all with the same first axis (one row per proof or MSM).  Should they exceed
+    `limit` bytes together, a fixed seeded sample of rows is written (`rows.npy` holds the indices).  Returns name -> shape."""
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    if n * row_bytes > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, (limit - 8 * n) // max(1, row_bytes)), replace=False))
+        arrays = {**{k: a[keep] for k, a in arrays.items()}, "rows": keep.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
+def dump_proof_outputs(path: str, streams) -> dict:
+    """What zg_prover_prove_images hands its caller for the last timed step of every stream, in stream order: the proof bytes
+    (`proofs`, one row per proof, float32) and, image -> proof, the public outputs (`instance_outputs`: the instance column's
+    field elements as 32-bit words, float64)."""
+    arrays = {"proofs": np.stack([np.frombuffer(p, dtype=np.uint8) for s in streams for p in s.last]).astype(np.float32)}
+    if streams[0].last_inst is not None:
+        arrays["instance_outputs"] = words_f64(np.concatenate([s.last_inst for s in streams]))
+    return write_outputs(path, arrays)
+
+
 # ------------------------------------------------------------------------------------------------ a lone proof
 
 def under_counter_collection() -> bool:
@@ -1296,6 +1339,8 @@ def proofs_main(args, rk) -> int:
     em = Emitter() if rk.rank == 0 else None
     out = measure_headline(job)
     if rk.rank == 0:
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_proof_outputs(args.dump_outputs, job.streams)
         em.early(out)
         tail_legs(job, em)
         em.final()
@@ -1469,6 +1514,8 @@ def msm_only_main(args, rk) -> int:
     if rk.rank == 0:
         em = Emitter()
         unit = n * 96 + 96
+        if args.dump_outputs:  # (the normalised sums of the last timed step, in launch order: g_lagrange vectors first)
+            dumped = write_outputs(args.dump_outputs, {"msm_sums": words_f64(sums)})
         out = {"metric": f"KZG commitment MSMs/s (best_multiexp, n = 2^{k}), shapes of {model_name}",
                "value": args.steps * vectors / dt, "unit": "MSMs/s", "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -1480,6 +1527,8 @@ def msm_only_main(args, rk) -> int:
                "mode": "msm-only", "msms_per_step": vectors, "digit_width": width, "points_per_rank": hi - lo, "stub_world": stub or None, "us_per_msm": dt / (args.steps * vectors) * 1e6,
                "collective": collective_object(rk), "ranks_share_a_device": bool(rk.world > 1 and "ZG_BENCH_DEVICE" in os.environ),
                "runtime_env": RUNTIME_ENV, "detail_file": os.path.relpath(DETAIL, ROOT)}
+        if args.dump_outputs:
+            out["dumped_outputs"] = dumped
         if power.get("cards"):
             out["power"] = power
         if stats:
@@ -1587,6 +1636,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-latency-probe", action="store_true", help="skip the lone-proof latency measurements (counter passes)")
     ap.add_argument("--no-lone-default", action="store_true", help="skip the child process behind lone.default")
     ap.add_argument("--tail-only-headline", action="store_true", help="no tail legs at all: the timed region and the line")
+    ap.add_argument("--full", action="store_true",
+                    help="run the tail legs after the timed region (the oracle check, the one-prover pass, the from-resident pass, "
+                         "the lone-proof probes, the other three models, the CPU baseline; each still subject to its --no-* option); "
+                         "without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--stub-world", type=int, default=0,
                     help="msm-only on ONE GPU: this process is rank 0 of a world of G -- points [0, n / G) of both base sets, the other "
                          "ranks' partial sums replaced by copies of its own (no collective, sums not checked): one rank's COMPUTE LEG, "
@@ -1594,7 +1649,7 @@ def parse_args(argv=None):
     ap.add_argument("--lone-child", choices=sorted(MODELS), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
-    if args.tail_only_headline:
+    if args.tail_only_headline or not args.full:
         args.no_cpu_baseline = args.no_other_configs = args.no_verify = args.no_serialised = True
         args.no_from_resident = args.no_latency_probe = args.no_lone_default = True
     return args

@@ -11,6 +11,7 @@ import os
 import re
 import subprocess
 import sys
+from types import SimpleNamespace
 
 import pytest
 
@@ -337,3 +338,49 @@ def test_the_power_sampler_reads_hwmon_files_and_is_silent_without_them(tmp_path
     assert bench.PowerSampler().start().stop() == {}
     line = json.loads(bench.format_line({**_oversized_record(), "power": {**got, "joules_per_proof": 0.8571234}}))
     assert line["power"]["power_w_avg"] == 1300.0 and line["power"]["joules_per_proof"] == 0.857123
+
+
+TAIL_FLAGS = ("no_cpu_baseline", "no_other_configs", "no_verify", "no_serialised", "no_from_resident", "no_latency_probe", "no_lone_default")
+
+
+def test_a_plain_run_runs_no_tail_leg_and_full_runs_them_all():
+    """A plain `--gpus 1 --steps N --warmup W` is set-up, warm-up, the timed steps and the line; --full brings back every tail
+    leg, each still subject to its own --no-* option (and --tail-only-headline still drops them all)."""
+    b = _bench()
+    plain = b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 5 and plain.warmup == 2
+    assert all(getattr(plain, f) for f in TAIL_FLAGS)
+    full = b.parse_args(["--full"])
+    assert not any(getattr(full, f) for f in TAIL_FLAGS)
+    one_off = b.parse_args(["--full", "--no-other-configs"])
+    assert [f for f in TAIL_FLAGS if getattr(one_off, f)] == ["no_other_configs"]
+    assert all(getattr(b.parse_args(["--full", "--tail-only-headline"]), f) for f in TAIL_FLAGS)
+    assert b.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_dumped_outputs_are_float_arrays_that_give_back_the_bytes(tmp_path):
+    """--dump-outputs: proof bytes as float32 and public outputs as the float64 of their 32-bit words, both exact, in stream
+    order; past the size limit a fixed seeded sample of rows (the same one every time) and its indices."""
+    import numpy as np
+
+    b = _bench()
+    rng = np.random.default_rng(5)
+    streams = [SimpleNamespace(last=[rng.integers(0, 256, 96, dtype=np.uint8).tobytes() for _ in range(3)],
+                               last_inst=rng.integers(0, 1 << 64, (3, 10, 4), dtype=np.uint64)) for _ in range(2)]
+    shapes = b.dump_proof_outputs(str(tmp_path / "all"), streams)
+    assert shapes == {"proofs": [6, 96], "instance_outputs": [6, 10, 8]}
+    proofs, outs = np.load(tmp_path / "all" / "proofs.npy"), np.load(tmp_path / "all" / "instance_outputs.npy")
+    assert proofs.dtype == np.float32 and outs.dtype == np.float64
+    assert [p.astype(np.uint8).tobytes() for p in proofs] == [p for s in streams for p in s.last]
+    assert np.array_equal(np.ascontiguousarray(outs.astype(np.uint32)).view(np.uint64), np.concatenate([s.last_inst for s in streams]))
+    # from resident columns there are no public outputs: the proofs alone
+    assert b.dump_proof_outputs(str(tmp_path / "resident"), [SimpleNamespace(last=streams[0].last, last_inst=None)]) == {"proofs": [3, 96]}
+    big = {"a": np.arange(1000 * 64, dtype=np.float64).reshape(1000, 64)}
+    for run in ("x", "y"):
+        got = b.write_outputs(str(tmp_path / run), big, limit=100_000)
+        assert got["a"][0] < 1000 and got["rows"] == [got["a"][0]]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 100_000 + 2 * 128
+    ax, ay = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "y" / "a.npy")
+    rows = np.load(tmp_path / "x" / "rows.npy").astype(np.int64)
+    assert np.array_equal(ax, ay) and np.array_equal(ax, big["a"][rows]) and np.all(np.diff(rows) > 0)
+    assert b.DUMP_LIMIT < 64 << 20

@@ -14,11 +14,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config")
+RUNTIME_KEYS = ("GPU_MAX_HW_QUEUES", "HIP_FORCE_DEV_KERNARG", "HSA_ENABLE_INTERRUPT")
 
 
 def _run(argv, env_extra=None, timeout=900, keep_world=False):
     env = dict(os.environ, ZG_BENCH_STALL_S="240")
     env.pop("WORLD_SIZE", None)
+    for k in RUNTIME_KEYS:  # (the caller's own HIP runtime settings would win over the bench's: `runtime_env` checks the bench's)
+        env.pop(k, None)
     env.update(env_extra or {})
     if not keep_world:
         env.pop("WORLD_SIZE", None)
@@ -39,7 +42,7 @@ def _run(argv, env_extra=None, timeout=900, keep_world=False):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["replicas", "shard-msm"])
 def test_gpus_2_starts_two_ranks_and_says_so(mode):
-    d, detail, _ = _run(["--gpus", "2", "--mode", mode, "--steps", "1", "--warmup", "1", "--provers", "2", "--batch", "4"],
+    d, detail, _ = _run(["--gpus", "2", "--mode", mode, "--steps", "1", "--warmup", "1", "--provers", "2", "--batch", "4", "--full"],
                         {"ZG_BENCH_DEVICE": "0", "ZG_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["collective"] == {"backend": "gloo", "ranks_seen": 2}
     assert detail["rccl_ranks"] is None and detail["ranks_share_a_device"] is True
@@ -57,7 +60,7 @@ def test_gpus_2_starts_two_ranks_and_says_so(mode):
 def test_msm_only_over_two_ranks_gathers_the_oracles_sums():
     """the commitment MSMs by themselves, sharded by point range over two ranks (gloo, one card), ONE
     all-gather per step; sampled sums == the oracle's best_multiexp over the whole vectors."""
-    d, detail, _ = _run(["--gpus", "2", "--mode", "msm-only", "--steps", "2", "--warmup", "1", "--batch", "2"],
+    d, detail, _ = _run(["--gpus", "2", "--mode", "msm-only", "--steps", "2", "--warmup", "1", "--batch", "2", "--full"],
                         {"ZG_BENCH_DEVICE": "0", "ZG_BENCH_BACKEND": "gloo"})
     assert d["unit"] == "MSMs/s" and d["n_gpus"] == 2 and d["collective"]["ranks_seen"] == 2 and d["scaling"] == "strong"
     assert d["verified"] is True and d["mode"] == "msm-only" and detail["msms_per_step"] == 60 and detail["points_per_rank"] == 8192
@@ -72,7 +75,7 @@ def test_the_rccl_code_paths_run_with_a_one_rank_group(mode):
     a real one-rank group (ZG_BENCH_FORCE_DIST=1): init_process_group("nccl"), the barrier, the rank count by all-reduce, the
     MAX over ranks, and msm-only's all_gather_into_tensor queued on the library's own stream between the MSM and the additions."""
     d, detail, _ = _run(["--mode", mode, "--steps", "2", "--warmup", "1", "--provers", "2", "--batch", "4", "--no-other-configs",
-                         "--no-cpu-baseline", "--no-latency-probe"],
+                         "--no-cpu-baseline", "--no-latency-probe", "--full"],
                         {"ZG_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29561", "RANK": "0", "LOCAL_RANK": "0",
                          "WORLD_SIZE": "1"}, keep_world=True)
     assert d["collective"] == {"backend": "rccl", "ranks_seen": 1} and d["verified"] is True and d["n_gpus"] == 1
@@ -84,7 +87,7 @@ def test_one_gpu_line_carries_roofline_cpu_baseline_and_both_lone_pairs():
     """The driver's N = 1 shape at a small size (the other three models are left to the real bench): the headline is
     image -> proof, the from-resident figure sits beside it, the lone proof is reported as opted-in AND as the library comes,
     its gated proofs' bytes were re-made in the plain order, nothing failed."""
-    d, detail, err = _run(["--steps", "2", "--warmup", "1", "--provers", "2", "--batch", "4", "--no-other-configs"])
+    d, detail, err = _run(["--steps", "2", "--warmup", "1", "--provers", "2", "--batch", "4", "--no-other-configs", "--full"])
     assert d["n_gpus"] == 1 and d["verified"] is True and "errors" not in d, detail.get("errors")
     assert d["config"]["workload"].startswith("image -> proof") and d["from_resident_columns_ms_per_proof"] > 0
     c = d["cpu_baseline"]
@@ -99,6 +102,42 @@ def test_one_gpu_line_carries_roofline_cpu_baseline_and_both_lone_pairs():
     #  the committed 12 x 32 line is held to "alone is never slower" in tests/test_bench_contract.py)
     assert d["roofline"]["serialised"]["frac"] >= 0.8 * d["roofline"]["frac"]
     assert "headline" in err  # (written when the timed region ended, before the tail legs)
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path, orc):
+    """Without --full the run is the timed steps and the line (no tail leg); --dump-outputs writes the last timed step's proofs
+    and public outputs, and those are the real ones: the oracle's pairing verifier accepts the first and the last proof of the
+    dump for the outputs dumped beside them."""
+    import importlib.util
+
+    import numpy as np
+
+    d, detail, _ = _run(["--steps", "2", "--warmup", "1", "--provers", "2", "--batch", "4", "--dump-outputs", str(tmp_path)])
+    for leg in ("verified", "cpu_baseline", "lone", "other_configs", "from_resident_columns_ms_per_proof", "errors"):
+        assert leg not in d, leg
+    assert "leg_seconds" not in detail and "serialised" not in d["roofline"]
+    assert d["steps"] == 2 and d["config"]["proofs_per_step"] == 8 and d["config"]["workload"].startswith("image -> proof")
+    assert sorted(os.listdir(tmp_path)) == ["instance_outputs.npy", "proofs.npy"]
+    proofs, outs = np.load(tmp_path / "proofs.npy"), np.load(tmp_path / "instance_outputs.npy")
+    assert proofs.dtype == np.float32 and proofs.shape == (8, detail["proof_len"])
+    assert outs.dtype == np.float64 and outs.shape[0] == 8 and outs.shape[2] == 8
+    assert detail["dumped_outputs"] == {"proofs": list(proofs.shape), "instance_outputs": list(outs.shape)}
+    spec = importlib.util.spec_from_file_location("zg_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    import wnn_circuit
+    import wnn_model
+
+    k, name = b.MODELS["tiny"]
+    cs, asg, _, _ = wnn_circuit.build(wnn_model.load_checked_in(name), wnn_model.load_test_image(), k)
+    c = b.SimpleNamespace(k=k, img=cs.to_c(), fixed=asg.fixed_values(), sigma=asg.sigma_values(),
+                          s=np.array(b.limbs(0x5EED5EED5EED5EED * b.MONT % b.R), dtype=np.uint64),
+                          vk_repr=np.array(b.limbs(0xC0FFEE * b.MONT % b.R), dtype=np.uint64))
+    _, pk = b._oracle_pk(c, b.host_cores())
+    for row in (0, 7):
+        inst = np.ascontiguousarray(outs[row].astype(np.uint32)).view(np.uint64)[None, :, :]
+        assert orc.verify_proof_pairing(pk, inst, proofs[row].astype(np.uint8).tobytes()) == 1, row
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@
 L=0g-halo2_amd/libzg_halo2.so
 for r in $(seq 1 ${3:-3}); do for v in "$1" "$2"; do
   cp "$v" $L
-  python bench.py --steps 40 --warmup 4 --no-cpu-baseline 2>/dev/null > /tmp/ab.json
+  python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline 2>/dev/null > /tmp/ab.json
   python - "$v" <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json')); k=d["single_proof_kernels_ms"]

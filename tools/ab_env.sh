@@ -7,7 +7,7 @@ for rep in $(seq 1 ${REPS:-3}); do for cfg in "$@"; do
   label=${cfg%% *}
   envs=${cfg#* }
   [ "$envs" = "$cfg" ] && envs=""
-  env $envs python bench.py --steps ${STEPS:-10} --warmup 2 --no-other-configs --no-cpu-baseline --no-verify --no-latency-probe --no-image-to-proof ${EXTRA} 2>/dev/null \
+  env $envs python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-other-configs --no-cpu-baseline --no-verify --no-latency-probe --no-image-to-proof ${EXTRA} 2>/dev/null \
     | python -c "import json,sys; d=json.load(sys.stdin); s=(d.get('roofline') or {}).get('serialised') or {}; print('$label ms/proof %.4f device_ms/proof %.3f serialised %.4f' % (d['ms_per_proof'], d['device_ms_per_proof'], s.get('ms_per_proof', 0)))" >> $out
   tail -1 $out
 done; done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B inside the full bench: merged selector columns (halo2's keygen, default) vs one column per selector.
 for r in $(seq 1 ${1:-2}); do for v in 0 1; do
-  ZG_BENCH_NO_SELECTOR_COMPRESSION=$v python bench.py --steps 40 --warmup 4 --no-cpu-baseline 2>/dev/null > /tmp/ab.json
+  ZG_BENCH_NO_SELECTOR_COMPRESSION=$v python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline 2>/dev/null > /tmp/ab.json
   python - "$v" <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json')); k=d["single_proof_kernels_ms"]

@@ -2,7 +2,7 @@
 # bench line of every BASELINE configuration that fits one GPU: ./tools/bench_models.sh [models...]
 for m in ${@:-tiny small medium large}; do
   s=16; [ $m = large ] && s=8
-  python bench.py --model $m --streams $s --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null > /tmp/bm.json
+  python bench.py --full --model $m --streams $s --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null > /tmp/bm.json
   python - $m <<'PY'
 import json,sys
 d=json.load(open('/tmp/bm.json'))

@@ -32,7 +32,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/serial -- python3 $R/bench.py $ONE > $OUT/serial_bench.json 2> $OUT/serial.log
 echo "serial trace done"
 if [ "$MODEL" = tiny ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline --no-other-configs --no-latency-probe --no-from-resident > $OUT/bench_under_trace.json 2> $OUT/trace.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-other-configs --no-latency-probe --no-from-resident > $OUT/bench_under_trace.json 2> $OUT/trace.log
   echo "shared trace done"
 fi
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq1 -- python3 $R/bench.py $ONE > /dev/null 2> $OUT/pmc_sq1.log
@@ -66,7 +66,7 @@ echo "lone trace done"
 cd $R
 python3 tools/timeline.py $(ls -t $OUT/lone/*/*_kernel_trace.csv | head -1) > $OUT/lone_timeline.txt 2>> $OUT/lone.log || true
 if [ "$MODEL" = tiny ]; then
-  python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+  python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   cp bench_detail.json $OUT/bench_detail.json
 fi
 # the raw counter / trace dumps are large (tens of MB) and gpurun merges at most 64 MiB back: keep what install_profile.py reads

@@ -10,7 +10,7 @@ P=29710
 for m in $MODELS; do
   P=$((P+1))
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $P bench.py \
-    --gpus 2 --mode shard-msm --provers 4 --model $m --steps 5 --warmup 2 --no-cpu-baseline \
+    --gpus 2 --mode shard-msm --provers 4 --model $m --steps 5 --warmup 2 --no-cpu-baseline --full \
     > gpurun_out/shard_${TAG}_$m.json 2> gpurun_out/shard_${TAG}_$m.err
   python - <<PY
 import json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # hardware-queue / stream-count sensitivity of the throughput bench (tuning aid)
 for q in 16 24 32; do for s in 8 12 16; do
-  GPU_MAX_HW_QUEUES=$q python bench.py --steps 8 --warmup 1 --streams $s --no-cpu-baseline 2>/dev/null > /tmp/c.json
+  GPU_MAX_HW_QUEUES=$q python bench.py --full --steps 8 --warmup 1 --streams $s --no-cpu-baseline 2>/dev/null > /tmp/c.json
   python - "$q" <<'PY'
 import json,sys
 d=json.load(open('/tmp/c.json'))
