@@ -1,0 +1,67 @@
+// Keccak-f[1600] and EvmTranscript's challenge rule, shared by the two sides of the transcript format: the host writer
+// (transcript.h, used by prover.hip) and the device reader that replays a proof (verify.hip).
+#pragma once
+
+#include "field.h"
+
+namespace zg {
+
+__host__ __device__ __forceinline__ uint64_t keccak_rol(uint64_t x, uint32_t s) {
+    return s ? (x << s) | (x >> (64 - s)) : x;
+}
+
+__host__ __device__ inline void keccak_f1600(uint64_t a[25]) {
+    constexpr uint64_t RC[24] = {
+        0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL,
+        0x000000000000808bULL, 0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL,
+        0x000000000000008aULL, 0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000aULL,
+        0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL, 0x8000000000008003ULL,
+        0x8000000000008002ULL, 0x8000000000000080ULL, 0x000000000000800aULL, 0x800000008000000aULL,
+        0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
+    // rho offsets indexed [x + 5y]
+    constexpr uint32_t RHO[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};
+    for (int round = 0; round < 24; round++) {
+        uint64_t c[5], b[25];
+#pragma unroll
+        for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
+#pragma unroll
+        for (int x = 0; x < 5; x++) {
+            const uint64_t d = c[(x + 4) % 5] ^ keccak_rol(c[(x + 1) % 5], 1);
+#pragma unroll
+            for (int y = 0; y < 5; y++) a[x + 5 * y] ^= d;
+        }
+        // rho + pi: b[y, 2x+3y] = rot(a[x, y])
+#pragma unroll
+        for (int x = 0; x < 5; x++)
+#pragma unroll
+            for (int y = 0; y < 5; y++) b[y + 5 * ((2 * x + 3 * y) % 5)] = keccak_rol(a[x + 5 * y], RHO[x + 5 * y]);
+#pragma unroll
+        for (int y = 0; y < 5; y++)
+#pragma unroll
+            for (int x = 0; x < 5; x++) a[x + 5 * y] = b[x + 5 * y] ^ (~b[(x + 1) % 5 + 5 * y] & b[(x + 2) % 5 + 5 * y]);
+        a[0] ^= RC[round];
+    }
+}
+
+constexpr uint32_t KECCAK_RATE = 136;  // bytes per absorbed block of Keccak-256
+
+// EvmTranscript squeezes keccak256(buffer ++ [1]) when the buffer is exactly the previous 32-byte state (nothing was
+// absorbed since), keccak256(buffer) otherwise
+__host__ __device__ __forceinline__ bool squeeze_appends_one(size_t buffered) { return buffered == 32; }
+
+// the challenge: the 32-byte hash as a big-endian integer, reduced mod r (at most five subtractions: 2^256 < 6r)
+__host__ __device__ inline Fe challenge_from_hash(const uint8_t h[32]) {
+    Fe v;
+    for (int i = 0; i < 8; i++)
+        v.l[i] = (uint32_t)h[31 - 4 * i] | ((uint32_t)h[30 - 4 * i] << 8) | ((uint32_t)h[29 - 4 * i] << 16) |
+                 ((uint32_t)h[28 - 4 * i] << 24);
+    uint32_t pm[8], t[8];
+    for (int i = 0; i < 8; i++) pm[i] = FrParams::p(i);
+    for (int r = 0; r < 6; r++) {
+        if (sub8(t, v.l, pm)) break;
+        for (int i = 0; i < 8; i++) v.l[i] = t[i];
+    }
+    return Fr::from_raw(v);
+}
+
+}  // namespace zg

@@ -110,8 +110,11 @@ enum {
     TAG_PERMUTED_TABLE = 3,
     TAG_PERM_Z = 4,
     TAG_LOOKUP_Z = 5,
-    TAG_RANDOM_POLY = 6
+    TAG_RANDOM_POLY = 6,
+    TAG_VERIFY_BATCH = 7  // the verifier's batch weights r_b (verify.hip), not a blinding scalar
 };
+// rand_fr on the host (Montgomery form)
+Fe rand_fr_host(const uint32_t* key, uint32_t tag, uint64_t index);
 
 // ---- launch helpers (all asynchronous on ctx->stream) ----
 // Lock-step batches: `nb` proofs, proof b's scalars in pc[b], its arrays `*_bs` elements after proof b-1's.

@@ -77,6 +77,7 @@ __host__ __device__ inline Fe rand_fr(const uint32_t* key, uint32_t tag, uint64_
         }
     }
 }
+Fe rand_fr_host(const uint32_t* key, uint32_t tag, uint64_t index) { return rand_fr(key, tag, index); }
 
 // proof b = blockIdx.y: columns [0, ncols0) draw from tag0 (index c * nrows + j), columns [ncols0, ncols) from tag1
 // (index restarts)

@@ -24,35 +24,8 @@
 namespace zg {
 
 // ------------------------------------------------------------------ Keccak-256 (original padding)
-static inline uint64_t rol64(uint64_t x, unsigned s) { return s ? (x << s) | (x >> (64 - s)) : x; }
-
-static void keccak_f1600(uint64_t a[25]) {
-    static const uint64_t rc[24] = {
-        0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL,
-        0x000000000000808bULL, 0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL,
-        0x000000000000008aULL, 0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000aULL,
-        0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL, 0x8000000000008003ULL,
-        0x8000000000008002ULL, 0x8000000000000080ULL, 0x000000000000800aULL, 0x800000008000000aULL,
-        0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
-    // rho offsets indexed [x + 5y]
-    static const unsigned rho[25] = {0,  1,  62, 28, 27, 36, 44, 6,  55, 20, 3,  10, 43,
-                                     25, 39, 41, 45, 15, 21, 8,  18, 2,  61, 56, 14};
-    for (int round = 0; round < 24; round++) {
-        uint64_t c[5], d[5], b[25];
-        for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
-        for (int x = 0; x < 5; x++) d[x] = c[(x + 4) % 5] ^ rol64(c[(x + 1) % 5], 1);
-        for (int i = 0; i < 25; i++) a[i] ^= d[i % 5];
-        // rho + pi: b[y, 2x+3y] = rot(a[x, y])
-        for (int x = 0; x < 5; x++)
-            for (int y = 0; y < 5; y++) b[y + 5 * ((2 * x + 3 * y) % 5)] = rol64(a[x + 5 * y], rho[x + 5 * y]);
-        for (int y = 0; y < 5; y++)
-            for (int x = 0; x < 5; x++) a[x + 5 * y] = b[x + 5 * y] ^ (~b[(x + 1) % 5 + 5 * y] & b[(x + 2) % 5 + 5 * y]);
-        a[0] ^= rc[round];
-    }
-}
-
 void keccak256(const uint8_t* data, size_t len, uint8_t out[32]) {
-    constexpr size_t rate = 136;
+    constexpr size_t rate = KECCAK_RATE;
     uint64_t st[25] = {0};
     auto absorb = [&](const uint8_t* blk) {
         for (size_t i = 0; i < rate / 8; i++) {
@@ -2250,6 +2223,38 @@ int zg_eval_polys_dev(zg_ctx* ctx, const void* d_polys, size_t stride_elems, siz
         ZG_HIP(hipStreamSynchronize(ctx->stream));
     }
     return ZG_OK;
+}
+
+// keygen_vk's commit_lagrange of every fixed column and permutation polynomial, with the MSM the prover commits with
+int zg_prover_vk_commitments(const zg_prover* p, zg_g1_affine* fixed_out, zg_g1_affine* sigma_out) {
+    ZG_REQUIRE(p && (fixed_out || p->pk->F == 0) && (sigma_out || p->pk->P == 0), ZG_ERR_INVALID_ARG,
+               "zg_prover_vk_commitments: null argument");
+    ZG_REQUIRE(p->world == 1 && p->gl->n >= p->pk->n, ZG_ERR_UNSUPPORTED,
+               "zg_prover_vk_commitments: a point-range shard holds only part of g_lagrange");
+    zg_ctx* ctx = p->ctx;
+    ZG_ENTER(ctx);
+    const PkDev& pk = *p->pk;
+    const uint32_t cnt[2] = {pk.F, pk.P};
+    const Fe* vals[2] = {pk.fixed_val, pk.sigma_val};
+    zg_g1_affine* outs[2] = {fixed_out, sigma_out};
+    const uint32_t most = std::max(pk.F, pk.P);
+    if (most == 0) return ZG_OK;
+    void* d_xyzz = nullptr;
+    ZG_HIP(hipMalloc(&d_xyzz, (size_t)most * sizeof(XYZZ)));
+    std::vector<zg_g1> jac(most);
+    int st = ZG_OK;
+    for (int w = 0; w < 2 && st == ZG_OK; w++) {
+        if (!cnt[w]) continue;
+        st = zg_msm_batch_dev(ctx, p->gl, vals[w], pk.n, cnt[w], pk.n, d_xyzz);
+        if (st == ZG_OK) st = zg_msm_finish(ctx, d_xyzz, cnt[w], jac.data());
+        for (uint32_t c = 0; c < cnt[w] && st == ZG_OK; c++) {  // normalised: z = 1, or (0, 1, 0) for the identity
+            const bool inf = fe_is_zero(*reinterpret_cast<const Fe*>(&jac[c].z));
+            outs[w][c].x = inf ? zg_fq{} : jac[c].x;
+            outs[w][c].y = inf ? zg_fq{} : jac[c].y;
+        }
+    }
+    (void)hipFree(d_xyzz);
+    return st;
 }
 
 int zg_kate_division_dev(zg_ctx* ctx, const void* d_a, size_t n, const zg_fr* z, void* d_q) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "curve.h"
+#include "keccak.h"
 
 namespace zg {
 
@@ -56,23 +57,11 @@ class EvmTranscript {
         stream.insert(stream.end(), b, b + 64);
     }
     Fe squeeze() {
-        if (buf.size() == 32) buf.push_back(1);
+        if (squeeze_appends_one(buf.size())) buf.push_back(1);
         uint8_t h[32];
         keccak256(buf.data(), buf.size(), h);
         buf.assign(h, h + 32);
-        // 256-bit big-endian integer mod r: at most five subtractions (2^256 < 6r)
-        Fe v;
-        for (int i = 0; i < 8; i++)
-            v.l[i] = (uint32_t)h[31 - 4 * i] | ((uint32_t)h[30 - 4 * i] << 8) | ((uint32_t)h[29 - 4 * i] << 16) |
-                     ((uint32_t)h[28 - 4 * i] << 24);
-        uint32_t pm[8], t[8];
-        for (int i = 0; i < 8; i++) pm[i] = FrParams::p(i);
-        for (;;) {
-            uint32_t borrow = sub8(t, v.l, pm);
-            if (borrow) break;
-            for (int i = 0; i < 8; i++) v.l[i] = t[i];
-        }
-        return Fr::from_raw(v);
+        return challenge_from_hash(h);
     }
 };
 

@@ -1,0 +1,805 @@
+// Batched GWC verification on the device -- replaces halo2_proofs::plonk::verify_proof::<KZGCommitmentScheme<Bn256>,
+// VerifierGWC, _, EvmTranscript, AccumulatorStrategy> + DualMSM::check (halo2_proofs v2023_04_20 src/plonk/verifier.rs,
+// src/poly/kzg/multiopen/gwc/verifier.rs, src/poly/kzg/strategy.rs) for many proofs of one circuit.
+//
+// Per proof b the GWC equation is  e(L_b, [s]_2) = e(R_b, [1]_2)  with  L_b = sum_j u^j W_j  and
+// R_b = sum_j u^j (z_j W_j + sum_k v^(m_j-1-k) C_jk - e_j G),  j over the opening point sets in first-appearance order,
+// k over a set's queries in query order.  Four launches and one host step:
+//   verify_replay   one wave per proof: the EvmTranscript read back (Keccak-f[1600]), every point and
+//                   scalar validated as it is read, the challenges theta, beta, gamma, y, x, v, u squeezed;
+//   verify_scalars  one wave per proof: x^n, l_0 / l_last / l_blind and the instance evaluations (Lagrange form,
+//                   O(instance_len) per query) with one batched inversion, the expected h(x) from the gates, the
+//                   permutation and the lookups folded with y, then every term's scalar of L_b and R_b;
+//   verify_terms    one workgroup per proof, one lane per term (double-and-add), a tree sum to the pair (L_b, R_b),
+//                   then the weighted pair r_b (L_b, R_b), kept for the failure path;
+//   verify_fold     one workgroup: L = sum_b r_b L_b, R = sum_b r_b R_b;
+//   host            e(L, [s]_2) e(-R, [1]_2) = 1 (pairing.hip), outside the context lock; if it fails, the batch is
+//                   bisected over the weighted pairs down to the proofs that fail alone.
+#include <cstring>
+
+#include "keccak.h"
+#include "poly.h"
+
+namespace zg {
+
+bool pairing_product_is_one(const Affine* p, const zg_g2_affine* q, size_t n);
+
+namespace {
+
+constexpr uint32_t SHARED = 0x80000000u;  // query table: commitment shared by all proofs (fixed, sigma)
+constexpr uint32_t HREF = 0x7fffffffu;    // query table: the h commitment sum_i xn^i H_i
+constexpr uint32_t IEVAL = 0x80000000u;   // evaluation source: an instance evaluation slot
+
+struct alignas(16) VMono {
+    Fe coeff;
+    uint32_t n_factors;
+    uint32_t factors[ZG_MAX_FACTORS];
+    uint32_t pad[3];
+};
+
+struct VQuery {
+    uint32_t term;  // term index of the commitment, SHARED | index, or HREF
+    uint32_t eval;  // index into the proof's evaluations
+    uint32_t set;   // opening point set
+    uint32_t vpow;  // power of v within the set
+};
+
+enum { CH_THETA, CH_BETA, CH_GAMMA, CH_Y, CH_X, CH_V, CH_U, CH_N };
+enum { ST_OK = 1, ST_TRAILING = 0, ST_MALFORMED = -1 };
+
+struct VArgs {
+    // circuit
+    const VMono* monos;
+    const zg_poly* gates;
+    const zg_lookup* lookups;
+    const uint32_t* qsrc;   // per circuit query: evaluation index, or IEVAL | instance slot
+    const uint32_t* psrc;   // per permutation column: the same, at rotation 0
+    const uint32_t* iev_col;
+    const Fe* iev_wr;       // omega^rotation of instance slot e
+    const VQuery* oq;       // opening queries in order
+    const Fe* set_wr;       // omega^rotation of point set j
+    const Fe* lag_w;        // omega^r, r = -(bf + 1) .. 0
+    const Affine* shared;   // fixed, sigma commitments, g0
+    uint32_t n_gates, n_lookups, n_queries, n_iev, n_oq;
+    uint32_t A, F, I, P, NL, sets, chunk, qpd, bf, nsets, nAQ, nFQ;
+    uint32_t NE, NP, NT, ev_h;  // evaluations (with the expected h(x) last), per-proof points, terms
+    uint32_t log_n;
+    Fe omega, ifft_div, delta, vk_repr;
+    // batch
+    const uint8_t* bytes;
+    const uint64_t* off;
+    const uint64_t* len;
+    const Fe* inst;  // [count][I][ilen]
+    uint32_t ilen, count;
+    Affine* pts;     // [count][NP]
+    Fe* ev;          // [count][NE]
+    Fe* ch;          // [count][CH_N]
+    int* status;     // [count]
+    Fe* qe;          // [count][n_queries + n_iev]
+    Fe* tmp;         // [count][2 * ninv]
+    uint32_t ninv;
+    Fe* sc;          // [count][NT], canonical integers
+    const Fe* rb;    // [count], canonical integers
+    XYZZ* wpair;     // [count][2]: r_b L_b, r_b R_b
+    XYZZ* out;       // [2]
+};
+
+// ------------------------------------------------------------------ Keccak-256 sponge
+// EvmTranscript's hash state: the bytes absorbed since the last squeeze, streamed into the sponge
+struct Sponge {
+    uint64_t st[25];
+    uint32_t pos, len;
+};
+__host__ __device__ void sp_reset(Sponge& s) {
+    for (int i = 0; i < 25; i++) s.st[i] = 0;
+    s.pos = 0;
+    s.len = 0;
+}
+__host__ __device__ void sp_byte(Sponge& s, uint32_t b) {
+    s.st[s.pos >> 3] ^= (uint64_t)(b & 0xff) << (8 * (s.pos & 7));
+    s.len++;
+    if (++s.pos == KECCAK_RATE) {
+        keccak_f1600(s.st);
+        s.pos = 0;
+    }
+}
+// 32 big-endian bytes of a canonical integer (8 LE u32 limbs)
+__host__ __device__ void sp_int(Sponge& s, const Fe& raw) {
+    for (int k = 0; k < 32; k++) sp_byte(s, raw.l[(31 - k) >> 2] >> (8 * ((31 - k) & 3)));
+}
+// the squeeze of transcript.h's EvmTranscript, on the streamed sponge; the state becomes the hash
+__host__ __device__ Fe sp_squeeze(Sponge& s) {
+    if (squeeze_appends_one(s.len)) sp_byte(s, 1);
+    s.st[s.pos >> 3] ^= 0x01ull << (8 * (s.pos & 7));
+    s.st[KECCAK_RATE / 8 - 1] ^= 0x80ull << 56;
+    keccak_f1600(s.st);
+    uint8_t h[32];
+    for (int k = 0; k < 32; k++) h[k] = (uint8_t)(s.st[k >> 3] >> (8 * (k & 7)));
+    sp_reset(s);
+    for (int k = 0; k < 32; k++) sp_byte(s, h[k]);
+    return challenge_from_hash(h);
+}
+
+template <class P>
+__host__ __device__ bool below_modulus(const Fe& v) {
+    for (int i = 7; i >= 0; i--) {
+        if (v.l[i] < P::p(i)) return true;
+        if (v.l[i] > P::p(i)) return false;
+    }
+    return false;
+}
+__host__ __device__ Fe be_int(const uint8_t* b) {
+    Fe v;
+    for (int i = 0; i < 8; i++)
+        v.l[i] = (uint32_t)b[31 - 4 * i] | ((uint32_t)b[30 - 4 * i] << 8) | ((uint32_t)b[29 - 4 * i] << 16) |
+                 ((uint32_t)b[28 - 4 * i] << 24);
+    return v;
+}
+
+struct Reader {
+    const uint8_t* p;
+    uint64_t pos, len;
+};
+__host__ __device__ bool read_point(Reader& r, Sponge& s, Affine& out) {
+    if (r.pos + 64 > r.len) return false;
+    const uint8_t* b = r.p + r.pos;
+    r.pos += 64;
+    const Fe x = be_int(b), y = be_int(b + 32);
+    if (!below_modulus<FqParams>(x) || !below_modulus<FqParams>(y)) return false;
+    out.x = Fq::from_raw(x);
+    out.y = Fq::from_raw(y);
+    if (affine_is_identity(out) || !affine_on_curve(out)) return false;  // (the transcript refuses the identity)
+    for (int k = 0; k < 64; k++) sp_byte(s, b[k]);
+    return true;
+}
+__host__ __device__ bool read_scalar(Reader& r, Sponge& s, Fe& out) {
+    if (r.pos + 32 > r.len) return false;
+    const uint8_t* b = r.p + r.pos;
+    r.pos += 32;
+    const Fe v = be_int(b);
+    if (!below_modulus<FrParams>(v)) return false;
+    out = Fr::from_raw(v);
+    for (int k = 0; k < 32; k++) sp_byte(s, b[k]);
+    return true;
+}
+
+// Read order: advice commitments | theta | per lookup (permuted input, permuted table) | beta, gamma | permutation z
+// per set | lookup z | random | y | h pieces | x | advice, fixed evals, random eval, sigma evals, permutation evals
+// (z, z(wx), and z(w^last x) except for the last set), lookup evals (z, z(wx), a', a'(w^-1 x), s') | v | one W per
+// point set | u.  Points land in pts in that order (W last), evaluations in ev.
+__host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
+    Sponge s;
+    sp_reset(s);
+    Reader r{a.bytes + a.off[b], 0, a.len[b]};
+    Affine* pts = a.pts + (size_t)b * a.NP;
+    Fe* ev = a.ev + (size_t)b * a.NE;
+    Fe* ch = a.ch + (size_t)b * CH_N;
+    sp_int(s, Fr::to_raw(a.vk_repr));
+    const Fe* inst = a.inst + (size_t)b * a.I * a.ilen;
+    for (uint32_t i = 0; i < a.I * a.ilen; i++) sp_int(s, Fr::to_raw(inst[i]));
+    bool ok = true;
+    uint32_t pi = 0, ei = 0;
+    for (uint32_t c = 0; c < a.A && ok; c++) ok = read_point(r, s, pts[pi++]);
+    if (ok) ch[CH_THETA] = sp_squeeze(s);
+    for (uint32_t l = 0; l < 2 * a.NL && ok; l++) ok = read_point(r, s, pts[pi++]);
+    if (ok) {
+        ch[CH_BETA] = sp_squeeze(s);
+        ch[CH_GAMMA] = sp_squeeze(s);
+    }
+    for (uint32_t c = 0; c < a.sets + a.NL + 1 && ok; c++) ok = read_point(r, s, pts[pi++]);
+    if (ok) ch[CH_Y] = sp_squeeze(s);
+    for (uint32_t c = 0; c < a.qpd && ok; c++) ok = read_point(r, s, pts[pi++]);
+    if (ok) ch[CH_X] = sp_squeeze(s);
+    for (uint32_t c = 0; c < a.ev_h && ok; c++) ok = read_scalar(r, s, ev[ei++]);
+    if (ok) ch[CH_V] = sp_squeeze(s);
+    for (uint32_t c = 0; c < a.nsets && ok; c++) ok = read_point(r, s, pts[pi++]);
+    if (ok) ch[CH_U] = sp_squeeze(s);
+    a.status[b] = !ok ? ST_MALFORMED : r.pos != r.len ? ST_TRAILING : ST_OK;
+}
+// One wave per proof, every lane running the same code on the same data (identical stores), so the per-proof work runs
+// in uniform control flow.  63 of the 64 lanes are redundant; the layout is kept because the one-lane-per-proof form of
+// these two kernels gave wrong field products on the device (the same bodies are right on the host), for a reason not
+// found yet.  The two kernels are a small share of a batch's time.
+__global__ __launch_bounds__(64) void verify_replay(VArgs a) {
+    const uint32_t b = blockIdx.x;
+    if (b < a.count) replay_one(a, b);
+}
+
+// in-place inversion of x[0..m) (zeros stay zero) with one field inversion; pre = m scratch elements
+__host__ __device__ void batch_inv(Fe* x, Fe* pre, uint32_t m) {
+    Fe acc = Fr::one();
+    for (uint32_t i = 0; i < m; i++) {
+        pre[i] = acc;
+        if (!fe_is_zero(x[i])) acc = Fr::mul(acc, x[i]);
+    }
+    Fe inv = Fr::inv(acc);
+    for (uint32_t i = m; i-- > 0;) {
+        if (fe_is_zero(x[i])) continue;
+        const Fe xi = x[i];
+        x[i] = Fr::mul(inv, pre[i]);
+        inv = Fr::mul(inv, xi);
+    }
+}
+
+__host__ __device__ Fe eval_poly(const VArgs& a, const zg_poly& p, const Fe* qe) {
+    Fe acc = fe_zero();
+    for (uint32_t m = p.first; m < p.first + p.count; m++) {
+        const VMono mo = a.monos[m];
+        Fe t = mo.coeff;
+        for (uint32_t f = 0; f < ZG_MAX_FACTORS; f++) {
+            if (f >= mo.n_factors) break;
+            const Fe q = qe[mo.factors[f]];
+            const Fe r = Fr::mul(t, q);
+            t = r;
+        }
+        acc = Fr::add(acc, t);
+    }
+    return acc;
+}
+
+__host__ __device__ __forceinline__ Fe src_eval(uint32_t src, const Fe* ev, const Fe* iev) {
+    return (src & IEVAL) ? iev[src & ~IEVAL] : ev[src];
+}
+
+__host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
+    Fe* ev = a.ev + (size_t)b * a.NE;
+    const Fe* ch = a.ch + (size_t)b * CH_N;
+    Fe* qe = a.qe + (size_t)b * (a.n_queries + a.n_iev);
+    Fe* iev = qe + a.n_queries;
+    Fe* den = a.tmp + (size_t)b * 2 * a.ninv;
+    Fe* pre = den + a.ninv;
+    Fe* sc = a.sc + (size_t)b * a.NT;
+    const Fe* inst = a.inst + (size_t)b * a.I * a.ilen;
+    const Fe x = ch[CH_X], y = ch[CH_Y], beta = ch[CH_BETA], gamma = ch[CH_GAMMA], theta = ch[CH_THETA];
+    const Fe v = ch[CH_V], u = ch[CH_U], one = Fr::one();
+    Fe xn = x;
+    for (uint32_t i = 0; i < a.log_n; i++) xn = Fr::sqr(xn);
+
+    // denominators: x^n - 1 | x - omega^r for the l's | x omega^rot - omega^i per instance slot and row
+    const uint32_t nl = a.bf + 2;
+    den[0] = Fr::sub(xn, one);
+    for (uint32_t i = 0; i < nl; i++) den[1 + i] = Fr::sub(x, a.lag_w[i]);
+    for (uint32_t e = 0; e < a.n_iev; e++) {
+        const Fe pt = Fr::mul(x, a.iev_wr[e]);
+        Fe wi = one;
+        for (uint32_t i = 0; i < a.ilen; i++) {
+            den[1 + nl + e * a.ilen + i] = Fr::sub(pt, wi);
+            wi = Fr::mul(wi, a.omega);
+        }
+    }
+    batch_inv(den, pre, 1 + nl + a.n_iev * a.ilen);
+    // l_i(x) = (x^n - 1)/n * omega^i / (x - omega^i)
+    const Fe num = Fr::mul(Fr::sub(xn, one), a.ifft_div);
+    Fe llast = fe_zero(), l0 = fe_zero(), lblind = fe_zero();
+    for (uint32_t i = 0; i < nl; i++) {
+        const Fe li = Fr::mul(Fr::mul(num, a.lag_w[i]), den[1 + i]);
+        if (i == 0) llast = li;
+        else if (i + 1 == nl) l0 = li;
+        else lblind = Fr::add(lblind, li);
+    }
+    const Fe lactive = Fr::sub(one, Fr::add(llast, lblind));
+    // instance column c at x omega^rot: (x^n - 1)/n * sum_i inst_i omega^i / (x omega^rot - omega^i)
+    for (uint32_t e = 0; e < a.n_iev; e++) {
+        const Fe* col = inst + (size_t)a.iev_col[e] * a.ilen;
+        Fe acc = fe_zero(), wi = one;
+        for (uint32_t i = 0; i < a.ilen; i++) {
+            acc = Fr::add(acc, Fr::mul(Fr::mul(col[i], wi), den[1 + nl + e * a.ilen + i]));
+            wi = Fr::mul(wi, a.omega);
+        }
+        iev[e] = Fr::mul(acc, num);
+    }
+    for (uint32_t q = 0; q < a.n_queries; q++) qe[q] = src_eval(a.qsrc[q], ev, iev);
+
+    // expected h(x): gates, permutation, lookups folded with y (the prover's order), over x^n - 1
+    Fe acc = fe_zero();
+#define FOLD(val) acc = Fr::add(Fr::mul(acc, y), (val))
+    for (uint32_t g = 0; g < a.n_gates; g++) FOLD(eval_poly(a, a.gates[g], qe));
+    const uint32_t EV_PZ = a.nAQ + a.nFQ + 1 + a.P;
+    if (a.sets > 0) {
+        const Fe* pz = ev + EV_PZ;  // set s: z at 3s, z(wx) at 3s + 1, z(w^last x) at 3s + 2
+        FOLD(Fr::mul(Fr::sub(one, pz[0]), l0));
+        const Fe zl = pz[3 * (a.sets - 1)];
+        FOLD(Fr::mul(Fr::sub(Fr::sqr(zl), zl), llast));
+        for (uint32_t s = 1; s < a.sets; s++) FOLD(Fr::mul(Fr::sub(pz[3 * s], pz[3 * (s - 1) + 2]), l0));
+        Fe cd0 = Fr::mul(beta, x);
+        for (uint32_t s = 0; s < a.sets; s++) {
+            Fe left = pz[3 * s + 1], right = pz[3 * s], cd = cd0;
+            const uint32_t c0 = s * a.chunk, c1 = c0 + a.chunk > a.P ? a.P : c0 + a.chunk;
+            for (uint32_t c = c0; c < c1; c++) {
+                const Fe ce = src_eval(a.psrc[c], ev, iev);
+                const Fe sig = ev[a.nAQ + a.nFQ + 1 + c];
+                left = Fr::mul(left, Fr::add(Fr::add(Fr::mul(beta, sig), ce), gamma));
+                right = Fr::mul(right, Fr::add(Fr::add(ce, cd), gamma));
+                cd = Fr::mul(cd, a.delta);
+            }
+            cd0 = cd;
+            FOLD(Fr::mul(Fr::sub(left, right), lactive));
+        }
+    }
+    const Fe* lk = ev + EV_PZ + (a.sets ? 3 * a.sets - 1 : 0);
+    for (uint32_t l = 0; l < a.NL; l++) {
+        const zg_lookup L = a.lookups[l];
+        Fe ai = fe_zero(), ti = fe_zero();
+        for (uint32_t e = 0; e < ZG_MAX_LOOKUP_WIDTH; e++) {
+            if (e >= L.width) break;
+            ai = Fr::add(Fr::mul(ai, theta), eval_poly(a, L.inputs[e], qe));
+            ti = Fr::add(Fr::mul(ti, theta), eval_poly(a, L.tables[e], qe));
+        }
+        const Fe* e5 = lk + 5 * l;  // z, z(wx), a', a'(w^-1 x), s'
+        FOLD(Fr::mul(Fr::sub(one, e5[0]), l0));
+        FOLD(Fr::mul(Fr::sub(Fr::sqr(e5[0]), e5[0]), llast));
+        const Fe lft = Fr::mul(Fr::mul(Fr::add(e5[2], beta), Fr::add(e5[4], gamma)), e5[1]);
+        const Fe rgt = Fr::mul(Fr::mul(Fr::add(ai, beta), Fr::add(ti, gamma)), e5[0]);
+        FOLD(Fr::mul(Fr::sub(lft, rgt), lactive));
+        const Fe ams = Fr::sub(e5[2], e5[4]);
+        FOLD(Fr::mul(ams, l0));
+        FOLD(Fr::mul(Fr::mul(Fr::sub(e5[2], e5[3]), ams), lactive));
+    }
+#undef FOLD
+    ev[a.ev_h] = Fr::mul(acc, den[0]);
+
+    // term scalars: u^j v^k on each commitment (x_n^i more on the h pieces), -sum u^j e_j on g0, u^j and u^j z_j on W_j
+    for (uint32_t t = 0; t < a.NT; t++) sc[t] = fe_zero();
+    const uint32_t T_SHARED = a.NP + a.nsets, T_G0 = a.NT - 1, PT_H = a.A + 3 * a.NL + a.sets + 1, PT_W = PT_H + a.qpd;
+    Fe g0 = fe_zero();
+    for (uint32_t q = 0; q < a.n_oq; q++) {
+        const VQuery oq = a.oq[q];
+        const Fe coef = Fr::mul(Fr::pow_u64(u, oq.set), Fr::pow_u64(v, oq.vpow));
+        g0 = Fr::sub(g0, Fr::mul(coef, ev[oq.eval]));
+        if (oq.term == HREF) {
+            Fe c = coef;
+            for (uint32_t i = 0; i < a.qpd; i++) {
+                sc[PT_H + i] = Fr::add(sc[PT_H + i], c);
+                c = Fr::mul(c, xn);
+            }
+        } else {
+            const uint32_t t = (oq.term & SHARED) ? T_SHARED + (oq.term & ~SHARED) : oq.term;
+            sc[t] = Fr::add(sc[t], coef);
+        }
+    }
+    sc[T_G0] = g0;
+    Fe uj = one;
+    for (uint32_t j = 0; j < a.nsets; j++) {
+        sc[a.NP + j] = uj;
+        sc[PT_W + j] = Fr::add(sc[PT_W + j], Fr::mul(uj, Fr::mul(x, a.set_wr[j])));
+        uj = Fr::mul(uj, u);
+    }
+    for (uint32_t t = 0; t < a.NT; t++) sc[t] = Fr::to_raw(sc[t]);
+}
+__global__ __launch_bounds__(64) void verify_scalars(VArgs a) {
+    const uint32_t b = blockIdx.x;
+    if (b < a.count && a.status[b] == ST_OK) scalars_one(a, b);
+}
+
+constexpr uint32_t TERMS_WG = 128;
+
+__device__ void tree_sum(XYZZ* sl, XYZZ* sr, uint32_t tid) {
+    for (uint32_t h = TERMS_WG / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (tid < h) {
+            sl[tid] = xyzz_add(sl[tid], sl[tid + h]);
+            sr[tid] = xyzz_add(sr[tid], sr[tid + h]);
+        }
+    }
+    __syncthreads();
+}
+
+// workgroup b: proof b's (L_b, R_b); lanes 0 and 1 then weight them by r_b (a proof that did not parse: the identity)
+__global__ __launch_bounds__(TERMS_WG) void verify_terms(VArgs a) {
+    __shared__ XYZZ sl[TERMS_WG], sr[TERMS_WG];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const bool live = a.status[b] == ST_OK;
+    XYZZ accl = xyzz_identity(), accr = xyzz_identity();
+    if (live) {
+        const Affine* pts = a.pts + (size_t)b * a.NP;
+        const Fe* sc = a.sc + (size_t)b * a.NT;
+        const uint32_t PT_W = a.NP - a.nsets;
+        for (uint32_t t = tid; t < a.NT; t += TERMS_WG) {
+            const bool left = t >= a.NP && t < a.NP + a.nsets;
+            const Affine p = t < a.NP ? pts[t] : left ? pts[PT_W + t - a.NP] : a.shared[t - a.NP - a.nsets];
+            const XYZZ m = xyzz_mul_raw(p, sc[t].l);
+            if (left) accl = xyzz_add(accl, m);
+            else accr = xyzz_add(accr, m);
+        }
+    }
+    sl[tid] = accl;
+    sr[tid] = accr;
+    tree_sum(sl, sr, tid);
+    if (tid < 2) {
+        const XYZZ s = tid == 0 ? sl[0] : sr[0];
+        a.wpair[2 * b + tid] = live ? xyzz_mul_raw(xyzz_to_affine(s), a.rb[b].l) : xyzz_identity();
+    }
+}
+
+__global__ __launch_bounds__(TERMS_WG) void verify_fold(VArgs a) {
+    __shared__ XYZZ sl[TERMS_WG], sr[TERMS_WG];
+    const uint32_t tid = threadIdx.x;
+    XYZZ accl = xyzz_identity(), accr = xyzz_identity();
+    for (uint32_t b = tid; b < a.count; b += TERMS_WG) {
+        accl = xyzz_add(accl, a.wpair[2 * b]);
+        accr = xyzz_add(accr, a.wpair[2 * b + 1]);
+    }
+    sl[tid] = accl;
+    sr[tid] = accr;
+    tree_sum(sl, sr, tid);
+    if (tid == 0) {
+        a.out[0] = sl[0];
+        a.out[1] = sr[0];
+    }
+}
+
+Fe fe_of(const zg_fr& x) {
+    Fe r;
+    std::memcpy(&r, &x, sizeof(r));
+    return r;
+}
+
+}  // namespace
+}  // namespace zg
+
+using namespace zg;
+
+struct zg_verifier {
+    zg_ctx* ctx = nullptr;
+    VArgs a{};
+    zg_g2_affine g2{}, s_g2{};
+    std::vector<void*> owned;  // circuit arrays
+    // batch buffers, grown on demand
+    size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0;
+    std::vector<void*> batch;
+};
+
+namespace {
+
+template <class T>
+int upload(zg_verifier* v, const T** dst, const std::vector<T>& src) {
+    void* p = nullptr;
+    ZG_HIP(hipMalloc(&p, (src.empty() ? 1 : src.size()) * sizeof(T)));
+    v->owned.push_back(p);
+    if (!src.empty()) ZG_HIP(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    *dst = static_cast<const T*>(p);
+    return ZG_OK;
+}
+
+template <class T>
+int grow(zg_verifier* v, T** dst, size_t elems) {
+    void* p = nullptr;
+    ZG_HIP(hipMalloc(&p, (elems ? elems : 1) * sizeof(T)));
+    v->batch.push_back(p);
+    *dst = static_cast<T*>(p);
+    return ZG_OK;
+}
+
+void free_batch(zg_verifier* v) {
+    for (void* p : v->batch) (void)hipFree(p);
+    v->batch.clear();
+    v->cap = v->bytes_cap = v->inst_cap = v->tmp_cap = 0;
+}
+
+// batch buffers for `count` proofs of `bytes` bytes in all, `inst` instance values and `tmp` inversion scratch elements
+int ensure(zg_verifier* v, size_t count, size_t bytes, size_t inst, size_t tmp) {
+    VArgs& a = v->a;
+    if (count <= v->cap && bytes <= v->bytes_cap && inst <= v->inst_cap && tmp <= v->tmp_cap) return ZG_OK;
+    free_batch(v);
+    count = std::max(count, (size_t)1);
+    bytes = std::max(bytes, (size_t)1);
+    inst = std::max(inst, (size_t)1);
+    tmp = std::max(tmp, (size_t)1);
+    ZG_TRY(grow(v, (uint8_t**)&a.bytes, bytes));
+    ZG_TRY(grow(v, (uint64_t**)&a.off, count));
+    ZG_TRY(grow(v, (uint64_t**)&a.len, count));
+    ZG_TRY(grow(v, (Fe**)&a.inst, inst));
+    ZG_TRY(grow(v, &a.pts, count * a.NP));
+    ZG_TRY(grow(v, &a.ev, count * a.NE));
+    ZG_TRY(grow(v, &a.ch, count * CH_N));
+    ZG_TRY(grow(v, &a.status, count));
+    ZG_TRY(grow(v, &a.qe, count * (a.n_queries + a.n_iev)));
+    ZG_TRY(grow(v, &a.sc, count * a.NT));
+    ZG_TRY(grow(v, (Fe**)&a.rb, count));
+    ZG_TRY(grow(v, &a.wpair, count * 2));
+    ZG_TRY(grow(v, &a.out, 2));
+    ZG_TRY(grow(v, &a.tmp, tmp));
+    v->cap = count;
+    v->bytes_cap = bytes;
+    v->inst_cap = inst;
+    v->tmp_cap = tmp;
+    return ZG_OK;
+}
+
+Fe omega_pow(const Fe& omega, const Fe& omega_inv, int64_t r) {
+    return Fr::pow_u64(r >= 0 ? omega : omega_inv, (uint64_t)(r >= 0 ? r : -r));
+}
+
+int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fixed_c, const zg_g1_affine* sigma_c,
+                    const zg_g1_affine* g0, const zg_fr* vk_repr) {
+    VArgs& a = v->a;
+    const uint32_t n_log = cs->k;
+    const uint64_t n = 1ull << n_log;
+    a.log_n = n_log;
+    a.A = cs->n_advice; a.F = cs->n_fixed; a.I = cs->n_instance; a.P = cs->n_perm_columns; a.NL = cs->n_lookups;
+    a.bf = cs->blinding_factors;
+    a.chunk = cs->cs_degree - 2;
+    a.sets = a.P ? (a.P + a.chunk - 1) / a.chunk : 0;
+    a.qpd = cs->cs_degree - 1;
+    a.nAQ = cs->n_advice_queries; a.nFQ = cs->n_fixed_queries;
+    a.n_gates = cs->n_gates; a.n_lookups = cs->n_lookups; a.n_queries = cs->n_queries;
+    a.omega = host_domain_omega(n_log);
+    const Fe omega_inv = Fr::inv(a.omega);
+    a.ifft_div = Fr::inv(Fr::from_u64(n));
+    a.delta = fr_delta();
+    a.vk_repr = fe_of(*vk_repr);
+    // evaluations in read order: advice, fixed, random, sigma, permutation (3 per set, 2 for the last), lookups (5 each)
+    const uint32_t EV_FIX = a.nAQ, EV_RAND = a.nAQ + a.nFQ, EV_SIG = EV_RAND + 1, EV_PZ = EV_SIG + a.P;
+    const uint32_t EV_LK = EV_PZ + (a.sets ? 3 * a.sets - 1 : 0);
+    a.ev_h = EV_LK + 5 * a.NL;
+    a.NE = a.ev_h + 1;
+
+    // where each circuit query's evaluation comes from
+    std::vector<uint32_t> iev_col;
+    std::vector<Fe> iev_wr;
+    std::vector<std::pair<uint32_t, int32_t>> iev_key;
+    auto inst_slot = [&](uint32_t col, int32_t rot) {
+        for (size_t e = 0; e < iev_key.size(); e++)
+            if (iev_key[e].first == col && iev_key[e].second == rot) return (uint32_t)e | IEVAL;
+        iev_key.push_back({col, rot});
+        iev_col.push_back(col);
+        iev_wr.push_back(omega_pow(a.omega, omega_inv, rot));
+        return (uint32_t)(iev_key.size() - 1) | IEVAL;
+    };
+    auto source = [&](uint32_t kind, uint32_t col, int32_t rot, uint32_t* out) {
+        if (kind == ZG_INSTANCE) {
+            *out = inst_slot(col, rot);
+            return true;
+        }
+        const zg_query* list = kind == ZG_ADVICE ? cs->advice_queries : cs->fixed_queries;
+        const uint32_t cnt = kind == ZG_ADVICE ? a.nAQ : a.nFQ, base = kind == ZG_ADVICE ? 0 : EV_FIX;
+        bool found = false;
+        for (uint32_t i = 0; i < cnt; i++)
+            if (list[i].column == col && list[i].rotation == rot) {
+                *out = base + i;
+                found = true;
+            }
+        return found;
+    };
+    std::vector<uint32_t> qsrc(a.n_queries), psrc(a.P);
+    for (uint32_t q = 0; q < a.n_queries; q++)
+        ZG_REQUIRE(source(cs->queries[q].kind, cs->queries[q].column, cs->queries[q].rotation, &qsrc[q]),
+                   ZG_ERR_INVALID_ARG, "zg_verifier_create: query %u is not among the circuit's column queries", q);
+    for (uint32_t c = 0; c < a.P; c++)
+        ZG_REQUIRE(source(cs->perm_columns[c].kind, cs->perm_columns[c].column, 0, &psrc[c]), ZG_ERR_INVALID_ARG,
+                   "zg_verifier_create: permutation column %u has no query at the current row", c);
+    a.n_iev = (uint32_t)iev_col.size();
+
+    // per-proof points in read order: advice | (permuted input, permuted table) per lookup | permutation z | lookup z |
+    // random | h pieces | W per point set
+    const uint32_t PT_LK = a.A, PT_PZ = PT_LK + 2 * a.NL, PT_LZ = PT_PZ + a.sets, PT_RAND = PT_LZ + a.NL;
+    // opening queries in the prover's order; point sets by first appearance of their rotation
+    std::vector<VQuery> oq;
+    std::vector<int64_t> set_rot;
+    std::vector<uint32_t> set_size;
+    const int64_t nn = (int64_t)n, last = -(int64_t)(a.bf + 1);
+    auto add = [&](int64_t rot, uint32_t term, uint32_t eval) {
+        const int64_t key = ((rot % nn) + nn) % nn;
+        uint32_t j = 0;
+        while (j < set_rot.size() && set_rot[j] != key) j++;
+        if (j == set_rot.size()) {
+            set_rot.push_back(key);
+            set_size.push_back(0);
+        }
+        oq.push_back({term, eval, j, set_size[j]++});
+    };
+    for (uint32_t i = 0; i < a.nAQ; i++) add(cs->advice_queries[i].rotation, cs->advice_queries[i].column, i);
+    for (uint32_t s = 0; s < a.sets; s++) {
+        add(0, PT_PZ + s, EV_PZ + 3 * s);
+        add(1, PT_PZ + s, EV_PZ + 3 * s + 1);
+    }
+    for (uint32_t s = a.sets; s-- > 0;)
+        if (s + 1 != a.sets) add(last, PT_PZ + s, EV_PZ + 3 * s + 2);
+    for (uint32_t l = 0; l < a.NL; l++) {
+        add(0, PT_LZ + l, EV_LK + 5 * l);
+        add(0, PT_LK + 2 * l, EV_LK + 5 * l + 2);
+        add(0, PT_LK + 2 * l + 1, EV_LK + 5 * l + 4);
+        add(-1, PT_LK + 2 * l, EV_LK + 5 * l + 3);
+        add(1, PT_LZ + l, EV_LK + 5 * l + 1);
+    }
+    for (uint32_t i = 0; i < a.nFQ; i++)
+        add(cs->fixed_queries[i].rotation, SHARED | cs->fixed_queries[i].column, EV_FIX + i);
+    for (uint32_t c = 0; c < a.P; c++) add(0, SHARED | (a.F + c), EV_SIG + c);
+    add(0, HREF, a.ev_h);
+    add(0, PT_RAND, EV_RAND);
+    // v-powers run down within a set: the first query of a set of m gets v^(m-1)
+    for (VQuery& q : oq) q.vpow = set_size[q.set] - 1 - q.vpow;
+    a.nsets = (uint32_t)set_rot.size();
+    a.n_oq = (uint32_t)oq.size();
+    a.NP = PT_RAND + 1 + a.qpd + a.nsets;
+    a.NT = a.NP + a.nsets + a.F + a.P + 1;
+    std::vector<Fe> set_wr, lag_w;
+    for (int64_t r : set_rot) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
+    for (int64_t r = last; r <= 0; r++) lag_w.push_back(omega_pow(a.omega, omega_inv, r));
+
+    std::vector<VMono> monos(cs->n_monomials);
+    for (uint32_t m = 0; m < cs->n_monomials; m++) {
+        VMono& d = monos[m];
+        std::memset(&d, 0, sizeof(d));
+        d.coeff = fe_of(cs->monomials[m].coeff);
+        d.n_factors = cs->monomials[m].n_factors;
+        ZG_REQUIRE(d.n_factors <= ZG_MAX_FACTORS, ZG_ERR_INVALID_ARG, "zg_verifier_create: monomial %u too long", m);
+        for (uint32_t f = 0; f < d.n_factors; f++) {
+            d.factors[f] = cs->monomials[m].factors[f];
+            ZG_REQUIRE(d.factors[f] < a.n_queries, ZG_ERR_INVALID_ARG, "zg_verifier_create: bad factor in monomial %u", m);
+        }
+    }
+    std::vector<zg_poly> gates(cs->gates, cs->gates + cs->n_gates);
+    std::vector<zg_lookup> lookups(cs->lookups, cs->lookups + cs->n_lookups);
+    auto poly_ok = [&](const zg_poly& p) { return (uint64_t)p.first + p.count <= cs->n_monomials; };
+    for (const zg_poly& g : gates) ZG_REQUIRE(poly_ok(g), ZG_ERR_INVALID_ARG, "zg_verifier_create: gate out of range");
+    for (const zg_lookup& l : lookups) {
+        ZG_REQUIRE(l.width <= ZG_MAX_LOOKUP_WIDTH, ZG_ERR_INVALID_ARG, "zg_verifier_create: lookup too wide");
+        for (uint32_t e = 0; e < l.width; e++)
+            ZG_REQUIRE(poly_ok(l.inputs[e]) && poly_ok(l.tables[e]), ZG_ERR_INVALID_ARG,
+                       "zg_verifier_create: lookup polynomial out of range");
+    }
+    for (uint32_t i = 0; i < a.nAQ; i++)
+        ZG_REQUIRE(cs->advice_queries[i].column < a.A, ZG_ERR_INVALID_ARG, "zg_verifier_create: bad advice query");
+    for (uint32_t i = 0; i < a.nFQ; i++)
+        ZG_REQUIRE(cs->fixed_queries[i].column < a.F, ZG_ERR_INVALID_ARG, "zg_verifier_create: bad fixed query");
+    for (uint32_t c : iev_col) ZG_REQUIRE(c < a.I, ZG_ERR_INVALID_ARG, "zg_verifier_create: bad instance query");
+    std::vector<Affine> shared(a.F + a.P + 1);
+    if (a.F) std::memcpy(shared.data(), fixed_c, a.F * sizeof(Affine));
+    if (a.P) std::memcpy(shared.data() + a.F, sigma_c, a.P * sizeof(Affine));
+    std::memcpy(&shared[a.F + a.P], g0, sizeof(Affine));
+
+    ZG_TRY(upload(v, &a.monos, monos));
+    ZG_TRY(upload(v, &a.gates, gates));
+    ZG_TRY(upload(v, &a.lookups, lookups));
+    ZG_TRY(upload(v, &a.qsrc, qsrc));
+    ZG_TRY(upload(v, &a.psrc, psrc));
+    ZG_TRY(upload(v, &a.iev_col, iev_col));
+    ZG_TRY(upload(v, &a.iev_wr, iev_wr));
+    ZG_TRY(upload(v, &a.oq, oq));
+    ZG_TRY(upload(v, &a.set_wr, set_wr));
+    ZG_TRY(upload(v, &a.lag_w, lag_w));
+    ZG_TRY(upload(v, &a.shared, shared));
+    return ZG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zg_verifier_create(zg_ctx* ctx, const zg_circuit* cs, const zg_g1_affine* fixed_commitments,
+                       const zg_g1_affine* sigma_commitments, const zg_g1_affine* g0, const zg_g2_affine* g2,
+                       const zg_g2_affine* s_g2, const zg_fr* vk_repr, zg_verifier** out) {
+    ZG_REQUIRE(ctx && cs && g0 && g2 && s_g2 && vk_repr && out, ZG_ERR_INVALID_ARG, "zg_verifier_create: null argument");
+    ZG_REQUIRE((fixed_commitments || cs->n_fixed == 0) && (sigma_commitments || cs->n_perm_columns == 0),
+               ZG_ERR_INVALID_ARG, "zg_verifier_create: null commitments");
+    ZG_REQUIRE(cs->k >= 1 && cs->k <= 28 && cs->cs_degree >= 3, ZG_ERR_UNSUPPORTED, "zg_verifier_create: k = %u, degree %u",
+               cs->k, cs->cs_degree);
+    ZG_ENTER(ctx);
+    zg_verifier* v = new zg_verifier();
+    v->ctx = ctx;
+    v->g2 = *g2;
+    v->s_g2 = *s_g2;
+    const int st = verifier_create(v, cs, fixed_commitments, sigma_commitments, g0, vk_repr);
+    if (st != ZG_OK) {
+        zg_verifier_destroy(v);
+        return st;
+    }
+    *out = v;
+    return ZG_OK;
+}
+
+void zg_verifier_destroy(zg_verifier* v) {
+    if (!v) return;
+    {
+        std::lock_guard<std::recursive_mutex> lock(v->ctx->mu);
+        (void)hipSetDevice(v->ctx->device);
+        (void)hipStreamSynchronize(v->ctx->stream);
+        free_batch(v);
+        for (void* p : v->owned) (void)hipFree(p);
+    }
+    delete v;
+}
+
+int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const* proofs, const size_t* proof_lens,
+                             const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
+    ZG_REQUIRE(v && key && (count == 0 || (proofs && proof_lens && verdicts && (instance || v->a.I == 0))),
+               ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: null argument");
+    ZG_REQUIRE(count < (1u << 24) && instance_len < (1u << 24), ZG_ERR_UNSUPPORTED,
+               "zg_verifier_verify_batch: %zu proofs of %zu instance rows", count, instance_len);
+    if (count == 0) return ZG_OK;
+    zg_ctx* ctx = v->ctx;
+    std::vector<int> status(count);
+    std::vector<XYZZ> wpair(2 * count);
+    XYZZ acc[2];
+    {
+        // the device part holds the context (and this verifier's buffers); the host pairings below do not
+        ZG_ENTER(ctx);
+        VArgs& a = v->a;
+        const size_t per_inst = (size_t)a.I * instance_len;
+        std::vector<uint64_t> off(count), len(count);
+        size_t total = 0;
+        for (size_t b = 0; b < count; b++) {
+            ZG_REQUIRE(proofs[b] || proof_lens[b] == 0, ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: proof %zu is null", b);
+            ZG_REQUIRE(per_inst == 0 || instance[b], ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: instance %zu is null", b);
+            off[b] = total;
+            len[b] = proof_lens[b];
+            total += proof_lens[b];
+        }
+        std::vector<uint8_t> bytes(total ? total : 1);
+        std::vector<Fe> inst(count * per_inst);
+        std::vector<Fe> rb(count);
+        uint32_t kw[8];
+        std::memcpy(kw, key, 32);
+        for (size_t b = 0; b < count; b++) {
+            if (proof_lens[b]) std::memcpy(bytes.data() + off[b], proofs[b], proof_lens[b]);
+            if (per_inst) std::memcpy(inst.data() + b * per_inst, instance[b], per_inst * sizeof(Fe));
+            rb[b] = Fr::to_raw(rand_fr_host(kw, TAG_VERIFY_BATCH, b));
+            if (fe_is_zero(rb[b])) rb[b].l[0] = 1;  // (a zero weight would hide the proof; probability 2^-254)
+        }
+        // inversion scratch per proof: x^n - 1, the bf + 2 Lagrange denominators, one per instance slot and row (twice)
+        a.ninv = 1 + (a.bf + 2) + a.n_iev * (uint32_t)instance_len;
+        ZG_TRY(ensure(v, count, total, count * per_inst, count * 2 * (size_t)a.ninv));
+        a.count = (uint32_t)count;
+        a.ilen = (uint32_t)instance_len;
+        hipStream_t st = ctx->stream;
+        ZG_HIP(hipMemcpyAsync((void*)a.bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
+        ZG_HIP(hipMemcpyAsync((void*)a.off, off.data(), count * 8, hipMemcpyHostToDevice, st));
+        ZG_HIP(hipMemcpyAsync((void*)a.len, len.data(), count * 8, hipMemcpyHostToDevice, st));
+        if (per_inst) ZG_HIP(hipMemcpyAsync((void*)a.inst, inst.data(), inst.size() * sizeof(Fe), hipMemcpyHostToDevice, st));
+        ZG_HIP(hipMemcpyAsync((void*)a.rb, rb.data(), count * sizeof(Fe), hipMemcpyHostToDevice, st));
+        ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay, dim3((uint32_t)count), dim3(64), 0, a);
+        ZG_LAUNCH(ctx, "verify_scalars", (double)count * a.NE * 32, verify_scalars, dim3((uint32_t)count), dim3(64), 0, a);
+        ZG_LAUNCH(ctx, "verify_terms", (double)count * a.NT * 96, verify_terms, dim3((uint32_t)count), dim3(TERMS_WG), 0, a);
+        ZG_LAUNCH(ctx, "verify_fold", (double)count * 256, verify_fold, dim3(1), dim3(TERMS_WG), 0, a);
+        ZG_HIP(hipGetLastError());
+        ZG_HIP(hipMemcpyAsync(status.data(), a.status, count * sizeof(int), hipMemcpyDeviceToHost, st));
+        ZG_HIP(hipMemcpyAsync(wpair.data(), a.wpair, 2 * count * sizeof(XYZZ), hipMemcpyDeviceToHost, st));
+        ZG_HIP(hipMemcpyAsync(acc, a.out, sizeof(acc), hipMemcpyDeviceToHost, st));
+        ZG_HIP(hipStreamSynchronize(st));
+    }
+
+    // e(L, [s]_2) e(-R, [1]_2) = 1 over a set of proofs, from their weighted pairs
+    const zg_g2_affine q[2] = {v->s_g2, v->g2};
+    auto holds = [&](const XYZZ& l, const XYZZ& r) {
+        const Affine ps[2] = {xyzz_to_affine(l), affine_neg(xyzz_to_affine(r))};
+        return pairing_product_is_one(ps, q, 2);
+    };
+    std::vector<size_t> live;
+    for (size_t b = 0; b < count; b++) {
+        verdicts[b] = status[b];
+        if (status[b] == ST_OK) live.push_back(b);
+    }
+    if (live.empty() || holds(acc[0], acc[1])) return ZG_OK;
+    // The batch fails: bisect.  A range that is known to fail is split; a half whose weighted sum holds is accepted
+    // (with the CSPRNG weights a failing proof cannot be cancelled by the others but with probability ~2^-254, the
+    // batch check's own soundness); a failing range of one proof is rejected -- r_b != 0, so that is the lone check.
+    // k bad proofs among n cost about k log2(n) pairings instead of n.
+    auto range_holds = [&](size_t lo, size_t hi) {
+        XYZZ l = xyzz_identity(), r = xyzz_identity();
+        for (size_t i = lo; i < hi; i++) {
+            l = xyzz_add(l, wpair[2 * live[i]]);
+            r = xyzz_add(r, wpair[2 * live[i] + 1]);
+        }
+        return holds(l, r);
+    };
+    std::vector<std::pair<size_t, size_t>> failing = {{0, live.size()}};
+    while (!failing.empty()) {
+        const auto [lo, hi] = failing.back();
+        failing.pop_back();
+        if (hi - lo == 1) {
+            verdicts[live[lo]] = 0;
+            continue;
+        }
+        const size_t mid = lo + (hi - lo) / 2;
+        if (range_holds(lo, mid)) {
+            failing.push_back({mid, hi});  // (the whole fails and this half holds: the other half fails)
+        } else {
+            failing.push_back({lo, mid});
+            if (!range_holds(mid, hi)) failing.push_back({mid, hi});
+        }
+    }
+    return ZG_OK;
+}
+
+}  // extern "C"

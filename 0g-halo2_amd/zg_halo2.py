@@ -74,6 +74,7 @@ ABI_SYMBOLS = [
     "zg_witness_plan_create", "zg_witness_plan_destroy", "zg_witness_plan_image_bytes", "zg_witness_plan_instance_len",
     "zg_witness_run_dev", "zg_prover_prove_images", "zg_prover_set_shard_rccl", "zg_xyzz_sum_ranks_dev", "zg_bases_enable_bit_table",
     "zg_tuning_set", "zg_tuning_get", "zg_tuning_names", "zg_bases_enable_digit_table", "zg_prover_enable_digit_tables",
+    "zg_prover_vk_commitments", "zg_verifier_create", "zg_verifier_destroy", "zg_verifier_verify_batch", "zg_pairing_check",
 ]
 
 def tuning_names() -> list:
@@ -166,6 +167,17 @@ def g1_sum(parts: np.ndarray) -> np.ndarray:
     out = np.zeros(12, np.uint64)
     _check(load().zg_g1_sum(_ptr(parts), c_size_t(parts.shape[0]), _ptr(out)))
     return out
+
+
+def pairing_check(p: np.ndarray, q: np.ndarray) -> int:
+    """1 iff prod_i e(p[i], q[i]) = 1.  p: uint64[n, 8] G1 affine, q: uint64[n, 16] G2 affine (Montgomery limbs, as
+    orc.Params.g2 / .s_g2 hold them); no device needed."""
+    p = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8)
+    q = np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 16)
+    assert p.shape[0] == q.shape[0]
+    res = c_int(-1)
+    _check(load().zg_pairing_check(_ptr(p), _ptr(q), c_size_t(p.shape[0]), ctypes.byref(res)))
+    return res.value
 
 
 def xyzz_sum_ranks(parts: np.ndarray) -> np.ndarray:
@@ -663,6 +675,14 @@ class Prover:
         _check(self.ctx.lib.zg_prover_gate_stats(self.h, out, c_size_t(4)))
         return dict(zip(("gated_proofs", "gates_armed", "remade_plain", "yields"), (int(x) for x in out)))
 
+    def vk_commitments(self):
+        """keygen_vk's commitments: (fixed uint64[n_fixed, 8], sigma uint64[n_perm_columns, 8]), affine."""
+        c = self.image.c
+        fixed = np.zeros((c.n_fixed, 8), np.uint64)
+        sigma = np.zeros((c.n_perm_columns, 8), np.uint64)
+        _check(self.ctx.lib.zg_prover_vk_commitments(self.h, _ptr(fixed), _ptr(sigma)))
+        return fixed, sigma
+
     def fetch(self, what: int, index: int, count: int, slot: int = 0) -> np.ndarray:
         out = np.zeros((count, 4), np.uint64)
         _check(self.ctx.lib.zg_prover_fetch_slot(self.h, c_size_t(slot), c_uint32(what), c_uint32(index), _ptr(out),
@@ -678,6 +698,54 @@ class Prover:
         try:
             self.close()
         except Exception:
+            pass
+
+
+class Verifier:
+    """zg_verifier: batched GWC verification of proofs of one circuit (circuit.py CircuitImage) on one GPU."""
+
+    def __init__(self, ctx: Ctx, image, fixed_c: np.ndarray, sigma_c: np.ndarray, g0: np.ndarray, g2: np.ndarray,
+                 s_g2: np.ndarray, vk_repr: np.ndarray):
+        """fixed_c / sigma_c: uint64[.., 8] affine commitments (Prover.vk_commitments); g0: uint64[8] = g[0];
+        g2, s_g2: uint64[16] G2 affine points of the parameters."""
+        self.ctx = ctx
+        self.image = image
+        lib = ctx.lib
+        lib.zg_verifier_destroy.argtypes = [c_void_p]
+        lib.zg_verifier_destroy.restype = None
+        arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (fixed_c, sigma_c, g0, g2, s_g2)]
+        h = c_void_p()
+        _check(lib.zg_verifier_create(ctx.h, image.ptr(), *[_ptr(a) for a in arrs], _ptr(_fr(vk_repr)),
+                                      ctypes.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def verify(self, proofs, instances, key) -> list:
+        """Verdict per proof: 1 accepted, 0 rejected, < 0 malformed.  instances[b]: uint64[n_instance, len, 4];
+        key: 32 bytes from a CSPRNG (an int in tests, as rng_key)."""
+        count = len(proofs)
+        bufs = [bytes(p) for p in proofs]
+        pptrs = (ctypes.c_char_p * count)(*bufs)
+        lens = (c_size_t * count)(*[len(p) for p in bufs])
+        insts, inst_len = [], 0
+        for b in range(count):
+            i, inst_len = Prover._inst(instances[b])
+            insts.append(i)
+        iptrs = (c_void_p * count)(*[c_void_p(i.ctypes.data) for i in insts])
+        verdicts = (c_int * count)()
+        _check(self.ctx.lib.zg_verifier_verify_batch(self.h, c_size_t(count), pptrs, lens, iptrs, c_size_t(inst_len),
+                                                     rng_key(key), verdicts))
+        return list(verdicts)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.zg_verifier_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
             pass
 
 

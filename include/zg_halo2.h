@@ -502,6 +502,41 @@ int zg_witness_run_dev(zg_witness_plan* plan, const uint8_t* images, size_t coun
 int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, const uint8_t* rng_keys,
                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses);
 
+/* ------------------------------------------------------------------ verifier
+ * Replaces halo2_proofs::plonk::verify_proof::<KZGCommitmentScheme<Bn256>, VerifierGWC, _, EvmTranscript,
+ * AccumulatorStrategy> followed by `DualMSM::check` (halo2_proofs v2023_04_20 src/plonk/verifier.rs,
+ * src/poly/kzg/multiopen/gwc/verifier.rs, src/poly/kzg/strategy.rs), as Wnn::verify_proof calls it
+ * (/root/reference/src/wnn.rs:265-280), for a batch of proofs of one circuit.  The proofs' transcripts are replayed
+ * and their opening terms multiplied out on the device; a random linear combination reduces the batch to one
+ * two-pairing check on the host (DESIGN.md section "Verification"). */
+typedef struct { zg_fq c0, c1; } zg_fq2;        /* c0 + c1 u, u^2 = -1 (bn256::Fq2)                          */
+typedef struct { zg_fq2 x, y; } zg_g2_affine;   /* bn256::G2Affine on y^2 = x^3 + 3/(9+u); (0,0) = identity */
+typedef struct zg_verifier zg_verifier;
+
+/* keygen_vk's commitments (halo2_proofs src/plonk/keygen.rs: params.commit_lagrange of each fixed column and each
+ * permutation polynomial), with the prover's g_lagrange bases: fixed_out[n_fixed], sigma_out[n_perm_columns], affine,
+ * an all-zero column giving (0,0).  A point-range shard (world > 1) holds only part of the bases: ZG_ERR_UNSUPPORTED. */
+int zg_prover_vk_commitments(const zg_prover *p, zg_g1_affine *fixed_out, zg_g1_affine *sigma_out);
+/* The verifying key on the device: the circuit (its polynomials, queries and opening point sets), the fixed and
+ * sigma commitments, and ParamsVerifierKZG's g0 = g[0], g2 and s_g2.  The secret scalar is never needed.  vk_repr:
+ * vk.transcript_repr, hashed into every transcript first.  All host pointers, copied. */
+int zg_verifier_create(zg_ctx *ctx, const zg_circuit *circuit, const zg_g1_affine *fixed_commitments,
+                       const zg_g1_affine *sigma_commitments, const zg_g1_affine *g0, const zg_g2_affine *g2,
+                       const zg_g2_affine *s_g2, const zg_fr *vk_repr, zg_verifier **out);
+void zg_verifier_destroy(zg_verifier *v);
+/* Verifies `count` proofs (EvmTranscript bytes proofs[b], proof_lens[b] long) against their public inputs
+ * instance[b] ([n_instance][instance_len], as zg_prover_prove_batch takes them).  verdicts[b]: 1 = accepted; 0 = the
+ * opening equation fails or bytes follow the proof; negative = malformed (short, a coordinate or scalar not below
+ * its modulus, a point off the curve or at infinity).  Each verdict is the one a lone verification would give.
+ * Proof b's share of the batch equation is weighted by r_b = rand_fr(key, TAG_VERIFY_BATCH, b) (the ChaCha20
+ * scalar of the prover's blinding).  `key` MUST come from the caller's CSPRNG: a prover who knows it can choose
+ * bad proofs whose errors cancel in the weighted sum.  Returns the zg_status of the call itself. */
+int zg_verifier_verify_batch(zg_verifier *v, size_t count, const uint8_t *const *proofs, const size_t *proof_lens,
+                             const zg_fr *const *instance, size_t instance_len, const uint8_t key[32], int *verdicts);
+/* Host helper (no device): *result = 1 iff prod_i e(p[i], q[i]) = 1 in GT (BN254 optimal ate pairing); identity
+ * points contribute 1.  The points are taken to be in G1 and G2.  bn256::multi_miller_loop + final_exponentiation. */
+int zg_pairing_check(const zg_g1_affine *p, const zg_g2_affine *q, size_t n, int *result);
+
 #ifdef __cplusplus
 }
 #endif
