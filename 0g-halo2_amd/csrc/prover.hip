@@ -18,6 +18,7 @@
 #include <memory>
 
 #include "poly.h"
+#include "check.h"
 #include "field9.h"
 #include "transcript.h"
 
@@ -91,6 +92,8 @@ struct PkDev {
     };
     Dom dom[3];           // [0]: the single coset; [1], [2]: the two parts of the split domain (when it applies)
     uint32_t nparts = 1;  // 1, or 3 when the split domain is prepared too
+    uint32_t NG = 0;
+    CheckInfo ck;         // the witness check's share of the key (check.hip): made at the first zg_prover_check_*
     ~PkDev() {
         (void)hipSetDevice(device);
         for (void* q : owned) (void)hipFree(q);
@@ -653,6 +656,11 @@ ProverShape prover_shape(const zg_prover* p) {
     const PkDev& k = *p->pk;
     return ProverShape{p->ctx, k.device, k.k, k.A, k.I, k.usable, p->in_flight};
 }
+CheckView prover_check_view(zg_prover* p) {
+    PkDev& k = *p->pk;
+    return CheckView{p->ctx, k.device, k.k, k.n, k.usable, k.F, k.A, k.I, k.P, k.NL, k.NG, p->cap, k.dc,
+                     k.fixed_val, k.sigma_val, p->adv_val, p->in_flight, &k.ck};
+}
 int prover_drain(zg_prover* p) {
     ZG_ENTER(p->ctx);
     ZG_HIP(hipStreamSynchronize(p->ctx->stream));
@@ -804,6 +812,17 @@ static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fi
         ZG_REQUIRE(qq.column < lim, ZG_ERR_INVALID_ARG, "zg_prover_create: permutation column %u out of range", c);
     }
     ZG_REQUIRE(cs->n_lookups <= 60, ZG_ERR_UNSUPPORTED, "zg_prover_create: %u lookups", cs->n_lookups);
+    // (the witness check's host view: which lookup tables are the key's alone, which depend on the witness)
+    pk->NG = cs->n_gates;
+    pk->ck.perm_cols.assign(cs->perm_columns, cs->perm_columns + cs->n_perm_columns);
+    for (uint32_t l = 0; l < cs->n_lookups; l++) {
+        bool var = false;
+        for (uint32_t e = 0; e < lks[l].width; e++)
+            for (uint32_t m = lks[l].tables[e].first; m < lks[l].tables[e].first + lks[l].tables[e].count; m++)
+                for (uint32_t f = 0; f < monos[m].n_factors; f++) var |= cs->queries[monos[m].factors[f]].kind != ZG_FIXED;
+        pk->ck.lookup_width.push_back(lks[l].width);
+        pk->ck.table_var.push_back(var ? 1 : 0);
+    }
     zg_query* d_q; DMono* d_m; zg_poly* d_g; DLookup* d_l; zg_query* d_pc;
     ZG_TRY(dalloc(&d_q, cs->n_queries));
     ZG_TRY(dalloc(&d_m, cs->n_monomials));

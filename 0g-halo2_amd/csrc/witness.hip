@@ -883,35 +883,52 @@ int zg_witness_run_dev(zg_witness_plan* p, const uint8_t* images, size_t count, 
     return ZG_OK;
 }
 
-int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, const uint8_t* rng_keys,
-                           uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses) {
-    ZG_REQUIRE(p && plan && images && rng_keys && proofs && proof_lens && (outputs || !plan->n_instance), ZG_ERR_INVALID_ARG,
-               "zg_prover_prove_images: null argument");
+// What zg_prover_prove_images and zg_prover_check_images share: the plan's program into the prover's slots 0..count-1.
+// slots / inst: [64]; inst[b] = the program's instance values of image b, inside `outputs`.
+static int images_into_slots(const char* who, zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, zg_fr* outputs,
+                             void** slots, const zg_fr** inst) {
     ZG_REQUIRE(count >= 1 && count <= zg_prover_batch(p) && count <= 64, ZG_ERR_INVALID_ARG,
-               "zg_prover_prove_images: %zu images for a prover of %zu slots (64 at most per call)", count, zg_prover_batch(p));
-    void* slots[64];
-    const zg_fr* inst[64];
+               "%s: %zu images for a prover of %zu slots (64 at most per call)", who, count, zg_prover_batch(p));
     for (size_t b = 0; b < count; b++) {
         slots[b] = zg_prover_advice_slot(p, b);
-        ZG_REQUIRE(slots[b] != nullptr, ZG_ERR_INVALID_ARG, "zg_prover_prove_images: the prover has no slot %zu", b);
+        ZG_REQUIRE(slots[b] != nullptr, ZG_ERR_INVALID_ARG, "%s: the prover has no slot %zu", who, b);
         inst[b] = outputs + b * plan->n_instance;
     }
     // The program writes [n_advice][2^k] columns into the prover's slots: a plan recorded for another model (other k or
     // column count) would overrun them, so its shape must be the prover's circuit's, on the prover's device.
     const ProverShape sh = prover_shape(p);
-    ZG_REQUIRE(plan->ctx->device == sh.device, ZG_ERR_INVALID_ARG, "zg_prover_prove_images: the plan lives on device %d, the prover on %d",
+    ZG_REQUIRE(plan->ctx->device == sh.device, ZG_ERR_INVALID_ARG, "%s: the plan lives on device %d, the prover on %d", who,
                plan->ctx->device, sh.device);
     ZG_REQUIRE(plan->k == sh.k && plan->n_advice == sh.n_advice, ZG_ERR_INVALID_ARG,
-               "zg_prover_prove_images: the plan writes %u advice columns of 2^%u rows, the prover's circuit has %u of 2^%u", plan->n_advice,
+               "%s: the plan writes %u advice columns of 2^%u rows, the prover's circuit has %u of 2^%u", who, plan->n_advice,
                plan->k, sh.n_advice, sh.k);
     ZG_REQUIRE((plan->n_instance == 0 || sh.n_instance == 1) && plan->n_instance <= sh.usable_rows, ZG_ERR_INVALID_ARG,
-               "zg_prover_prove_images: the plan yields %u instance values for a circuit with %u instance column(s) of %u usable rows",
+               "%s: the plan yields %u instance values for a circuit with %u instance column(s) of %u usable rows", who,
                plan->n_instance, sh.n_instance, sh.usable_rows);
     // The witness runs on the plan's stream, the proofs on the prover's: when those differ (or a batch left through an
     // error return and its kernels may still read the slots) the prover's streams are drained before the slots are rewritten.
     if (sh.in_flight || plan->ctx != sh.ctx) ZG_TRY(prover_drain(p));
-    ZG_TRY(zg_witness_run_dev(plan, images, count, slots, outputs));
+    return zg_witness_run_dev(plan, images, count, slots, outputs);
+}
+
+int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, const uint8_t* rng_keys,
+                           uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses) {
+    ZG_REQUIRE(p && plan && images && rng_keys && proofs && proof_lens && (outputs || !plan->n_instance), ZG_ERR_INVALID_ARG,
+               "zg_prover_prove_images: null argument");
+    void* slots[64];
+    const zg_fr* inst[64];
+    ZG_TRY(images_into_slots("zg_prover_prove_images", p, plan, images, count, outputs, slots, inst));
     return zg_prover_prove_batch_dev(p, count, nullptr, inst, plan->n_instance, rng_keys, proofs, proof_cap, proof_lens, statuses);
+}
+
+int zg_prover_check_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, zg_fr* outputs,
+                           zg_failure* failures, size_t cap, uint32_t* totals) {
+    ZG_REQUIRE(p && plan && images && totals && (outputs || !plan->n_instance) && (failures || cap == 0), ZG_ERR_INVALID_ARG,
+               "zg_prover_check_images: null argument");
+    void* slots[64];
+    const zg_fr* inst[64];
+    ZG_TRY(images_into_slots("zg_prover_check_images", p, plan, images, count, outputs, slots, inst));
+    return zg_prover_check_batch_dev(p, count, nullptr, inst, plan->n_instance, failures, cap, totals);
 }
 
 }  // extern "C"

@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "zg_witness_run_dev", "zg_prover_prove_images", "zg_prover_set_shard_rccl", "zg_xyzz_sum_ranks_dev", "zg_bases_enable_bit_table",
     "zg_tuning_set", "zg_tuning_get", "zg_tuning_names", "zg_bases_enable_digit_table", "zg_prover_enable_digit_tables",
     "zg_prover_vk_commitments", "zg_verifier_create", "zg_verifier_destroy", "zg_verifier_verify_batch", "zg_pairing_check",
+    "zg_prover_check_batch", "zg_prover_check_batch_dev", "zg_prover_check_images", "zg_permutation_mapping",
 ]
 
 def tuning_names() -> list:
@@ -113,6 +114,29 @@ def rng_key(seed) -> bytes:
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("launches", ctypes.c_uint64), ("total_ms", ctypes.c_double),
                 ("algo_bytes", ctypes.c_double), ("unit_bytes", ctypes.c_double)]
+
+
+FAIL_GATE, FAIL_LOOKUP, FAIL_COPY = 0, 1, 2
+
+
+class Failure(ctypes.Structure):
+    """zg_failure: one record of the witness check.  as_tuple(): (kind, index, row, other_index, other_row)."""
+    _fields_ = [("kind", c_uint32), ("index", c_uint32), ("row", c_uint32), ("other_index", c_uint32),
+                ("other_row", c_uint32)]
+
+    def as_tuple(self) -> tuple:
+        return (int(self.kind), int(self.index), int(self.row), int(self.other_index), int(self.other_row))
+
+
+def permutation_mapping(sigma_values: np.ndarray, k: int):
+    """zg_permutation_mapping (no device): sigma values uint64[n_perm, 2^k, 4] -> (next_col, next_row), uint32[n_perm, 2^k]
+    each: sigma[c][r] = delta^next_col[c][r] * omega^next_row[c][r].  Raises ZgError when a value is no such product."""
+    sigma_values = np.ascontiguousarray(sigma_values, dtype=np.uint64).reshape(-1, 1 << k, 4)
+    m = sigma_values.shape[0]
+    next_col = np.zeros((m, 1 << k), np.uint32)
+    next_row = np.zeros((m, 1 << k), np.uint32)
+    _check(load().zg_permutation_mapping(c_uint32(k), c_uint32(m), _ptr(sigma_values), _ptr(next_col), _ptr(next_row)))
+    return next_col, next_row
 
 
 def _check(status: int) -> None:
@@ -635,6 +659,58 @@ class Prover:
         if st != 0 and raise_on_error:
             _check(st)
         return [bytes(bufs[b][: lens[b]]) for b in range(count)], outputs, list(sts)
+
+    # ---- witness check (Wnn::mock_proof)
+    @staticmethod
+    def _reports(count, cap, recs, totals):
+        out = []
+        for b in range(count):
+            t = [int(totals[3 * b + j]) for j in range(3)]
+            out.append((t, [recs[b * cap + i].as_tuple() for i in range(min(sum(t), cap))]))
+        return out
+
+    def check_batch(self, advice, instances, cap: int = 64, device: bool = False):
+        """zg_prover_check_batch(_dev): one (totals, records) per witness -- totals = [gate, lookup, copy] failure counts,
+        records = the first min(sum(totals), cap) failures as (kind, index, row, other_index, other_row), ascending.
+        advice: list of host arrays (device=False) or device addresses (device=True); None entries (or advice=None) =
+        the slot as it stands.  The slots are only read."""
+        count = len(instances)
+        lib = self.ctx.lib
+        keep = []
+        if advice is None:
+            adv_ptrs = None
+        elif device:
+            adv_ptrs = (c_void_p * count)(*[c_void_p(a) if a else None for a in advice])
+        else:
+            keep = [np.ascontiguousarray(a, dtype=np.uint64) if a is not None else None for a in advice]
+            adv_ptrs = (c_void_p * count)(*[c_void_p(a.ctypes.data) if a is not None else None for a in keep])
+        insts, inst_len = [], 0
+        for b in range(count):
+            i, inst_len = self._inst(instances[b])
+            insts.append(i)
+        inst_ptrs = (c_void_p * count)(*[c_void_p(i.ctypes.data) for i in insts])
+        recs = (Failure * max(1, count * cap))()
+        totals = (c_uint32 * (3 * count))()
+        fn = lib.zg_prover_check_batch_dev if device else lib.zg_prover_check_batch
+        _check(fn(self.h, c_size_t(count), adv_ptrs, inst_ptrs, c_size_t(inst_len), recs if cap else None, c_size_t(cap),
+                  totals))
+        return self._reports(count, cap, recs, totals)
+
+    def check(self, advice: np.ndarray, instance: np.ndarray, cap: int = 64):
+        """One witness: (totals, records); see check_batch."""
+        return self.check_batch([advice], [instance], cap)[0]
+
+    def check_images(self, plan: "WitnessPlan", images: np.ndarray, cap: int = 64):
+        """Wnn::mock_proof for a batch: image bytes -> (reports as check_batch, outputs uint64[count, n_instance, 4])."""
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        count = images.shape[0]
+        images = images.reshape(count, -1)
+        outputs = np.zeros((count, plan.n_instance, 4), np.uint64)
+        recs = (Failure * max(1, count * cap))()
+        totals = (c_uint32 * (3 * count))()
+        _check(self.ctx.lib.zg_prover_check_images(self.h, plan.h, _ptr(images), c_size_t(count), _ptr(outputs),
+                                                   recs if cap else None, c_size_t(cap), totals))
+        return self._reports(count, cap, recs, totals), outputs
 
     def evaluate_h(self, advice_polys, instance_polys, perm_z_polys, lookup_z_polys, permuted_polys, theta, beta, gamma, y,
                    extended_n: int) -> np.ndarray:

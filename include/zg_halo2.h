@@ -502,6 +502,54 @@ int zg_witness_run_dev(zg_witness_plan* plan, const uint8_t* images, size_t coun
 int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, const uint8_t* rng_keys,
                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses);
 
+/* ------------------------------------------------------------------ witness check
+ * Replaces halo2_proofs::dev::MockProver::run followed by MockProver::verify / assert_satisfied (halo2_proofs
+ * v2023_04_20 src/dev.rs), as Wnn::mock_proof calls them (/root/reference/src/wnn.rs:203-210), for a batch of
+ * witnesses of the prover's circuit: is the witness satisfied, and if not, where does it fail.  With n = 2^k and
+ * usable = n - (blinding_factors + 1):
+ *   gates    gate polynomial g (index in zg_circuit.gates) fails on row r < usable iff its value there is not 0; a
+ *            query with rotation t reads row (r + t) mod n of the column as it stands;
+ *   lookups  lookup l fails on row r < usable iff the tuple of its input polynomials at r equals, component by
+ *            component, the tuple of its table polynomials at NO row r' < usable (exact tuples, no compression);
+ *   copies   with next(c, r) = (c', r') the cell for which sigma_c(omega^r) = delta^c' * omega^r' (c, c' index
+ *            zg_circuit.perm_columns; halo2's permutation::keygen::Assembly::mapping), cell (c, r), r < n, fails iff
+ *            its value differs from that of next(c, r).
+ * MockProver's CellNotAssigned / ConstraintPoisoned diagnostics have no counterpart: the ABI carries values, not regions.
+ * Per witness the check reports the exact number of failures of each kind and the first min(total, cap) failures in
+ * ascending (kind, index, row) order. */
+enum { ZG_FAIL_GATE = 0, ZG_FAIL_LOOKUP = 1, ZG_FAIL_COPY = 2 };
+typedef struct {
+    uint32_t kind;        /* ZG_FAIL_*                                                         */
+    uint32_t index;       /* gate / lookup / permutation-column index                          */
+    uint32_t row;
+    uint32_t other_index; /* ZG_FAIL_COPY: permutation column of next(c, r); else 0            */
+    uint32_t other_row;   /* ZG_FAIL_COPY: its row; else 0                                     */
+} zg_failure;
+
+/* count <= max_batch witnesses.  advice[b]: host [n_advice][2^k] (copied into slot b), or NULL = slot b as it stands;
+ * instance[b]: [n_instance][instance_len], zero beyond.  failures: [count][cap] (may be NULL when cap == 0; entries past
+ * a witness's total are left alone); totals: [count][3] by kind.  The check only READS the slot: it draws no blinding
+ * rows and leaves every buffer a following proof reads as it found it (check, then zg_prover_prove_batch_dev on the
+ * slot as it stands, gives the bytes proving alone gives).  A point-range shard can be checked: no bases are involved.
+ * Returns the status of the CALL -- an unsatisfied witness is not an error of the call; ZG_ERR_INVALID_ARG also when a
+ * sigma value of the proving key is no delta^c * omega^r (the mapping is recovered at the first check). */
+int zg_prover_check_batch(zg_prover *p, size_t count, const zg_fr *const *advice, const zg_fr *const *instance,
+                          size_t instance_len, zg_failure *failures, size_t cap, uint32_t *totals);
+/* Same with the advice columns in HBM (as zg_prover_prove_batch_dev: copied into the slot unless they are the slot;
+ * NULL entries, or d_advice NULL = the slots as they stand).  Blocking, like the host form. */
+int zg_prover_check_batch_dev(zg_prover *p, size_t count, void *const *d_advice, const zg_fr *const *instance,
+                              size_t instance_len, zg_failure *failures, size_t cap, uint32_t *totals);
+/* Wnn::mock_proof for a batch of images (/root/reference/src/wnn.rs:203-210: image -> witness -> MockProver): the
+ * witness program into the prover's slots 0..count-1, then the check with the program's instance values; outputs and
+ * the plan's conditions as zg_prover_prove_images. */
+int zg_prover_check_images(zg_prover *p, zg_witness_plan *plan, const uint8_t *images, size_t count, zg_fr *outputs,
+                           zg_failure *failures, size_t cap, uint32_t *totals);
+/* Host helper (no device): next_col / next_row [n_perm][2^k] such that sigma_values[c][r] = delta^next_col *
+ * omega^next_row -- Assembly::mapping back from what halo2's ProvingKey holds (pk.permutation.permutations).
+ * ZG_ERR_INVALID_ARG when a value is no such product. */
+int zg_permutation_mapping(uint32_t k, uint32_t n_perm, const zg_fr *sigma_values, uint32_t *next_col,
+                           uint32_t *next_row);
+
 /* ------------------------------------------------------------------ verifier
  * Replaces halo2_proofs::plonk::verify_proof::<KZGCommitmentScheme<Bn256>, VerifierGWC, _, EvmTranscript,
  * AccumulatorStrategy> followed by `DualMSM::check` (halo2_proofs v2023_04_20 src/plonk/verifier.rs,

@@ -504,6 +504,47 @@ pub fn create_proofs_zg<ConcreteCircuit: Circuit<Fr>, R: RngCore>(
     Ok(bufs)
 }
 
+/// UNVERIFIED like the rest of this file.  `MockProver::run(..).verify()` for a batch (what `Wnn::mock_proof` asks of one
+/// circuit): per witness the failure counts by kind ([gates, lookups, copies]) and the first `cap` failures in ascending
+/// (kind, index, row) order.  For debug builds, a newly recorded witness program, or a batch the verifier rejected.
+pub fn check_witnesses_zg<ConcreteCircuit: Circuit<Fr>>(
+    params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Affine>, circuits: &[ConcreteCircuit], instances: &[&[&[Fr]]], cap: usize,
+) -> Result<Vec<([u32; 3], Vec<zg_failure>)>, Error> {
+    assert_eq!(circuits.len(), instances.len());
+    let key = fingerprint(params, pk, true);
+    let mut cache = PROVERS.lock().unwrap();
+    if !cache.contains_key(&key) {
+        let h = build_handle(params, pk).expect("circuit outside the backend's scope");
+        check(unsafe { zg_prover_set_overlap(h.prover, 0) })?;
+        cache.insert(key, h);
+    }
+    let h = cache.get(&key).unwrap();
+    let count = circuits.len();
+    if unsafe { zg_prover_batch(h.prover) } < count {
+        check(unsafe { zg_prover_set_batch(h.prover, count) })?;
+    }
+    let inst_len = instances[0].iter().map(|c| c.len()).max().unwrap_or(0);
+    let mut adv = Vec::with_capacity(count);
+    let mut inst = Vec::with_capacity(count);
+    for (c, i) in circuits.iter().zip(instances.iter()) {
+        adv.push(synthesize(pk.get_vk().cs(), params.k(), c, i)?);
+        let mut flat = vec![Fr::zero(); i.len() * inst_len];
+        for (col, v) in i.iter().enumerate() { flat[col * inst_len..col * inst_len + v.len()].copy_from_slice(v); }
+        inst.push(flat);
+    }
+    let adv_ptrs: Vec<*const Fr> = adv.iter().map(|a| a.as_ptr()).collect();
+    let inst_ptrs: Vec<*const Fr> = inst.iter().map(|a| a.as_ptr()).collect();
+    let mut recs = vec![zg_failure::default(); count * cap.max(1)];
+    let mut totals = vec![0u32; 3 * count];
+    check(unsafe { zg_prover_check_batch(h.prover, count, adv_ptrs.as_ptr(), inst_ptrs.as_ptr(), inst_len,
+                                         if cap > 0 { recs.as_mut_ptr() } else { std::ptr::null_mut() }, cap, totals.as_mut_ptr()) })?;
+    Ok((0..count).map(|b| {
+        let t = [totals[3 * b], totals[3 * b + 1], totals[3 * b + 2]];
+        let m = ((t[0] + t[1] + t[2]) as usize).min(cap);
+        (t, recs[b * cap..b * cap + m].to_vec())
+    }).collect())
+}
+
 impl Drop for Handle {
     fn drop(&mut self) {
         unsafe { zg_prover_destroy(self.prover); zg_ctx_destroy(self.ctx); }
