@@ -1,4 +1,4 @@
-// What the witness check (check.hip) and the prover (prover.hip) know of each other.
+// The witness check's share of a proving key (check.hip); the key itself is PkDev (prover.h).
 #pragma once
 
 #include <memory>
@@ -23,19 +23,5 @@ struct CheckInfo {
     std::mutex mu;
     std::shared_ptr<CheckKey> key;
 };
-
-// A prover as the check sees it (prover.hip).  adv_val: [slots][A][n], the advice slots of a lock-step batch.
-struct CheckView {
-    zg_ctx* ctx;
-    int device;
-    uint32_t k, n, usable, F, A, I, P, NL, NG, slots;
-    DevCircuit dc;
-    const Fe* fixed_val;
-    const Fe* sigma_val;
-    Fe* adv_val;
-    bool in_flight;
-    CheckInfo* info;
-};
-CheckView prover_check_view(zg_prover* p);
 
 }  // namespace zg

@@ -13,7 +13,7 @@
 // A failing lane sets its bit in a per-witness bitmap [constraint][n / 64] (one wave ballot = one 64-bit word, plain
 // vector stores) and a workgroup with failures bumps its witness's counter of that kind once.  The host reads the
 // count x 3 totals; only a witness with failures has its bitmap read back and walked into ordered records.
-#include "check.h"
+#include "prover.h"
 #include "poly_eval.h"
 
 #include <algorithm>
@@ -318,8 +318,7 @@ struct CheckKey {
     }
 };
 
-static int build_check_key(const CheckView& v, CheckKey& ck) {
-    zg_ctx* ctx = v.ctx;
+static int build_check_key(zg_ctx* ctx, const PkDev& v, CheckKey& ck) {
     const uint32_t n = v.n;
     ck.device = v.device;
     // ---- the mapping, from the sigma values the key holds in HBM
@@ -339,8 +338,8 @@ static int build_check_key(const CheckView& v, CheckKey& ck) {
     uint32_t n_key = 0;
     size_t key_elems = 0;
     for (uint32_t l = 0; l < v.NL; l++) {
-        const size_t sz = (size_t)v.info->lookup_width[l] * n;
-        if (v.info->table_var[l]) {
+        const size_t sz = (size_t)v.ck.lookup_width[l] * n;
+        if (v.ck.table_var[l]) {
             ck.tabs.var_mask |= 1ull << l;
             ck.tabs.off[l] = (uint32_t)ck.var_elems;
             ck.var_slots.lookup[ck.n_var] = l;
@@ -371,15 +370,15 @@ static int build_check_key(const CheckView& v, CheckKey& ck) {
 }
 
 // the key data of this prover, made on first use
-static int check_key(const CheckView& v, std::shared_ptr<CheckKey>& out) {
-    std::lock_guard<std::mutex> lock(v.info->mu);
-    if (!v.info->key) {
+static int check_key(zg_ctx* ctx, PkDev& v, std::shared_ptr<CheckKey>& out) {
+    std::lock_guard<std::mutex> lock(v.ck.mu);
+    if (!v.ck.key) {
         std::shared_ptr<CheckKey> ck = std::make_shared<CheckKey>();
-        ck->status = build_check_key(v, *ck);
+        ck->status = build_check_key(ctx, v, *ck);
         if (ck->status != ZG_OK) ck->error = zg_last_error();
-        v.info->key = ck;
+        v.ck.key = ck;
     }
-    out = v.info->key;
+    out = v.ck.key;
     if (out->status != ZG_OK) set_error("%s", out->error.c_str());
     return out->status;
 }
@@ -389,28 +388,20 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
                             const zg_fr* const* instance, size_t instance_len, zg_failure* failures, size_t cap, uint32_t* totals) {
     ZG_REQUIRE(p && totals, ZG_ERR_INVALID_ARG, "zg_prover_check: null argument");
     ZG_REQUIRE(failures || cap == 0, ZG_ERR_INVALID_ARG, "zg_prover_check: room for %zu failures per witness but no array", cap);
-    zg_ctx* ctx = prover_shape(p).ctx;
+    zg_ctx* ctx = p->ctx;
     ZG_ENTER(ctx);
-    const CheckView v = prover_check_view(p);
-    ZG_REQUIRE(count >= 1 && count <= v.slots, ZG_ERR_INVALID_ARG, "zg_prover_check: %zu witnesses for %u slots (zg_prover_set_batch)",
-               count, v.slots);
-    ZG_REQUIRE(v.I == 0 || instance || instance_len == 0, ZG_ERR_INVALID_ARG, "zg_prover_check: instance is null");
-    ZG_REQUIRE(instance_len <= v.usable, ZG_ERR_INVALID_ARG, "zg_prover_check: instance too large (Error::InstanceTooLarge)");
+    PkDev& v = *p->pk;  // (the key: the circuit's shape, its tables, the fixed and sigma values)
+    ZG_TRY(batch_args_ok("zg_prover_check", "witnesses", p, count, instance, instance_len));
     if (v.I && instance_len)
         for (size_t b = 0; b < count; b++) ZG_REQUIRE(instance[b], ZG_ERR_INVALID_ARG, "zg_prover_check: instance %zu is null", b);
-    if (v.in_flight) ZG_TRY(prover_drain(p));  // (a batch left through an error return may still read the slots)
+    if (p->in_flight) ZG_TRY(prover_drain(p));  // (a batch left through an error return may still read the slots)
     std::shared_ptr<CheckKey> ck;
-    ZG_TRY(check_key(v, ck));
+    ZG_TRY(check_key(ctx, v, ck));
 
     hipStream_t st = ctx->stream;
     const uint32_t nb = (uint32_t)count, n = v.n;
     const size_t adv_bs = (size_t)v.A * n, inst_bs = (size_t)v.I * n;
-    for (uint32_t b = 0; b < nb && v.A; b++) {
-        Fe* slot = v.adv_val + b * adv_bs;
-        if (advice_host && advice_host[b]) ZG_HIP(hipMemcpyAsync(slot, advice_host[b], adv_bs * 32, hipMemcpyHostToDevice, st));
-        else if (advice_dev && advice_dev[b] && advice_dev[b] != (void*)slot)
-            ZG_HIP(hipMemcpyAsync(slot, advice_dev[b], adv_bs * 32, hipMemcpyDeviceToDevice, st));
-    }
+    ZG_TRY(advice_into_slots(p, nb, advice_host, advice_dev));
     const uint32_t nc = v.NG + v.NL + v.P, w = (n + 63) / 64;
     WsScope ws(ctx);
     Fe* inst = ws.get<Fe>((size_t)nb * inst_bs);  // the prover's own instance columns belong to its proofs
@@ -437,7 +428,7 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
         }
     }
     Cols cols{};
-    cols.fixed = v.fixed_val; cols.advice = v.adv_val; cols.instance = inst;
+    cols.fixed = v.fixed_val; cols.advice = p->adv_val; cols.instance = inst;
     cols.log_size = v.k; cols.rot_scale = 1;
     cols.adv_bs = adv_bs; cols.inst_bs = inst_bs;
     const dim3 blk(256);

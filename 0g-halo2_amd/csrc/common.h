@@ -119,7 +119,7 @@ struct zg_ctx {
     double unit_next = -1.0;
     bool msm_dense_hint = false;  // set by a caller around an MSM whose vectors are all random (latency form: one lane per task)
     uint32_t* msm_tickets = nullptr;  // last-workgroup-done counters of the MSM reduction (msm.hip), zero between launches
-    // While a prover's gate kernel (prover.hip, ZG_LAT_GATE) spins on this context's stream -- or on the main stream this side
+    // While a prover's gate kernel (prove_batch.hip, ZG_LAT_GATE) spins on this context's stream -- or on the main stream this side
     // context's stream follows -- the host must not WAIT for that stream before it has opened the gate.  Every path of the
     // library that can block behind a stream from inside a proof (a workspace block that has to be allocated, a pinned arena
     // that has to grow, a twiddle table made on first use, the MSM's ticket counters) calls gate_yield() first: it opens the
@@ -250,15 +250,5 @@ enum Knob : int {
 };
 int knob(Knob k);
 bool runtime_serialises_launches();  // AMD_SERIALIZE_KERNEL / HIP_LAUNCH_BLOCKING are set: no launch may wait for the host
-
-// prover.hip: what a witness program has to match before it may write into a prover's advice slots (witness.hip)
-struct ProverShape {
-    zg_ctx* ctx;
-    int device;
-    uint32_t k, n_advice, n_instance, usable_rows;
-    bool in_flight;  // a batch left through an error return: work may still be queued on the prover's streams
-};
-ProverShape prover_shape(const zg_prover* p);
-int prover_drain(zg_prover* p);  // waits for everything queued on the prover's streams
 
 }  // namespace zg

@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "keccak.h"
 
 namespace zg {
 
@@ -152,6 +153,8 @@ using namespace zg;
 extern "C" {
 
 const char* zg_last_error(void) { return g_last_error.c_str(); }
+
+void zg_keccak256(const uint8_t* data, size_t len, uint8_t out[32]) { zg::keccak256(data, len, out); }
 
 const char* zg_version(void) { return "zg_halo2 0.3 (gfx950)"; }
 

@@ -1,6 +1,8 @@
-// Keccak-f[1600] and EvmTranscript's challenge rule, shared by the two sides of the transcript format: the host writer
-// (transcript.h, used by prover.hip) and the device reader that replays a proof (verify.hip).
+// Keccak-f[1600], Keccak-256 and EvmTranscript's challenge rule, shared by the two sides of the transcript format: the
+// host writer (transcript.h, used by prove_batch.hip) and the device reader that replays a proof (verify.hip).
 #pragma once
+
+#include <cstring>
 
 #include "field.h"
 
@@ -44,6 +46,33 @@ __host__ __device__ inline void keccak_f1600(uint64_t a[25]) {
 }
 
 constexpr uint32_t KECCAK_RATE = 136;  // bytes per absorbed block of Keccak-256
+
+// Keccak-256 (original padding) on the host
+inline void keccak256(const uint8_t* data, size_t len, uint8_t out[32]) {
+    constexpr size_t rate = KECCAK_RATE;
+    uint64_t st[25] = {0};
+    auto absorb = [&](const uint8_t* blk) {
+        for (size_t i = 0; i < rate / 8; i++) {
+            uint64_t w = 0;
+            for (int j = 0; j < 8; j++) w |= (uint64_t)blk[8 * i + j] << (8 * j);
+            st[i] ^= w;
+        }
+        keccak_f1600(st);
+    };
+    while (len >= rate) {
+        absorb(data);
+        data += rate;
+        len -= rate;
+    }
+    uint8_t last[rate];
+    memset(last, 0, rate);
+    memcpy(last, data, len);
+    last[len] ^= 0x01;
+    last[rate - 1] ^= 0x80;
+    absorb(last);
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 8; j++) out[8 * i + j] = (uint8_t)(st[i] >> (8 * j));
+}
 
 // EvmTranscript squeezes keccak256(buffer ++ [1]) when the buffer is exactly the previous 32-byte state (nothing was
 // absorbed since), keccak256(buffer) otherwise

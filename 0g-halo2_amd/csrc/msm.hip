@@ -21,18 +21,10 @@
 // Integer-ALU bound (a mixed add is 10 field products of ~130 v_mad_u64_u32 each); no MFMA.
 #include <cstdlib>
 
-#include "common.h"
+#include "msm.h"
 #include "field9.h"
 
 namespace zg {
-
-int msm_batch2_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t batch, size_t n, XYZZ* d_out);
-int msm_batch3_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask);
-int msm_batch4_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t per, size_t outer, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask,
-                   uint32_t naf_width);
 
 // Max points per accumulate task.  Throughput form: 48 -- the fewer tasks, the fewer partial sums the reduction has
 // to merge, and since lanes take tasks in length-sorted order (msm_scan_kernel) longer tasks cost no lane
@@ -1271,7 +1263,7 @@ int bases_enable_naf(zg_ctx* ctx, zg_bases* b, uint32_t w, bool strict) {
     ZG_REQUIRE(w >= 3 && w <= 16, ZG_ERR_INVALID_ARG, "bases_enable_naf: digit width %u not in [3,16]", w);
     std::lock_guard<std::mutex> lock(b->mu);
     if (zg_bases* have = b->dense.load(std::memory_order_acquire)) {
-        // (the table serves any digit width -- msm_batch4_dev takes one per launch; naf_w is only its default: the
+        // (the table serves any digit width -- msm_dev takes one per launch; naf_w is only its default: the
         //  first call decides it, and the public entry refuses to pretend otherwise)
         ZG_REQUIRE(!strict || have->naf_w == w, ZG_ERR_INVALID_ARG,
                    "zg_bases_enable_bit_table: the base set already has its bit-position table, made for width %u", have->naf_w);
@@ -1678,9 +1670,13 @@ int bases_enable_full(zg_ctx* ctx, zg_bases* b, uint32_t window_bits, bool with_
     return ZG_OK;
 }
 
-// The latency form of msm_batch4_dev over digit tables (conditions checked by the caller).
-static int msm_full_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars, size_t stride,
-                        size_t per, size_t outer, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask) {
+// The latency form of msm_dev over digit tables (conditions checked by the caller).
+static int msm_full_dev(zg_ctx* ctx, const MsmJob& j) {
+    const zg_bases *bases = j.bases, *bases_b = j.bases_b;
+    const size_t split = j.split, stride = j.stride, per = j.per, outer = j.outer, batch = j.batch, n = j.n;
+    const Fe* d_scalars = j.scalars;
+    XYZZ* d_out = j.out;
+    const uint64_t run_mask = j.run_mask;
     const uint32_t c = bases->full_c, W = bases->full_windows, D = 1u << (c - 1);
     const uint32_t B = (uint32_t)batch, N = (uint32_t)n;
     const uint64_t entries = (uint64_t)N * W;
@@ -1731,158 +1727,327 @@ static int msm_full_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* base
     return ZG_OK;
 }
 
-int msm_batch_dev(zg_ctx* ctx, const zg_bases* bases, const Fe* d_scalars, size_t stride, size_t batch,
-                  size_t n, XYZZ* d_out) {
-    // (a base set with a bit-position table, zg_bases_enable_bit_table, is multiplied in the free-position form by a
-    //  context in its throughput form; a latency-form context keeps the window table -- DESIGN.md 4)
-    if (const zg_bases* d = bases_dense(bases); d && d->naf_w && !ctx->msm_pair) bases = d;
-    return msm_batch2_dev(ctx, bases, nullptr, batch, d_scalars, stride, batch, n, d_out);
+// ---- the bucket forms of an MSM launch sequence, in four parts: argument checks, launch plan, workspace, launches
+// the tables a job's vectors are multiplied against: window (or bit-position) tables and running-sum tables of both sets
+struct MsmTables {
+    const Affine *a, *b, *run_a, *run_b;
+};
+static MsmTables msm_tables(const MsmJob& j) {
+    return MsmTables{j.bases->table, j.bases_b ? j.bases_b->table : j.bases->table, j.bases->run_table,
+                     j.bases_b ? j.bases_b->run_table : j.bases->run_table};
 }
 
-// Vectors [0, split) are multiplied against `bases`, vectors [split, batch) against `bases_b` (same
-// length and window size, e.g. ParamsKZG::g_lagrange and ::g) in ONE launch sequence.
-int msm_batch2_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t batch, size_t n, XYZZ* d_out) {
-    return msm_batch3_dev(ctx, bases, bases_b, split, d_scalars, stride, batch, n, d_out, 0);
-}
-
-// ... and the vectors named by run_mask (bit b, b < 64) are multiplied in the run form (msm_digits_kernel); their
-// base set must have its running-sum table (bases_enable_runs).
-int msm_batch3_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask) {
-    return msm_batch4_dev(ctx, bases, bases_b, split, d_scalars, stride, 0, 0, batch, n, d_out, run_mask, 0);
-}
-
-// ... and the batch may be `batch / per` groups of `per` vectors each (the same commitments of several proofs):
-// vector v = group * per + j lives at d_scalars + group * outer + j * stride; split and run_mask go by j.
-// per = 0: one group (v = j).
-int msm_batch4_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t per, size_t outer, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask,
-                   uint32_t naf_width) {
-    if (per == 0) {
-        per = batch ? batch : 1;
-        outer = 0;
+// (a) What a job must satisfy.  Leaves its grouping and run mask in canonical form (per = 0 -> one group; mask bits below
+// `per` only) and the digit width of the free-position form in *naf_out (0: windows).
+static int msm_check(MsmJob& j, uint32_t* naf_out) {
+    const zg_bases *bases = j.bases, *bases_b = j.bases_b;
+    if (j.per == 0) {
+        j.per = j.batch ? j.batch : 1;
+        j.outer = 0;
     }
-    ZG_REQUIRE(batch % per == 0, ZG_ERR_INVALID_ARG, "zg_msm: batch %zu is no multiple of the group size %zu", batch, per);
-    if (per < 64) run_mask &= (1ull << per) - 1ull;
-    const uint64_t mask_a = split >= 64 ? ~0ull : (1ull << split) - 1ull;
-    const Affine* run_a = bases->run_table;
-    const Affine* run_b = bases_b ? bases_b->run_table : bases->run_table;
-    ZG_REQUIRE((run_mask & mask_a) == 0 || run_a != nullptr, ZG_ERR_INVALID_ARG, "zg_msm: run form asked for bases without a running-sum table");
-    ZG_REQUIRE((run_mask & ~mask_a) == 0 || run_b != nullptr, ZG_ERR_INVALID_ARG, "zg_msm: run form asked for bases without a running-sum table");
+    ZG_REQUIRE(j.batch % j.per == 0, ZG_ERR_INVALID_ARG, "zg_msm: batch %zu is no multiple of the group size %zu", j.batch, j.per);
+    if (j.per < 64) j.run_mask &= (1ull << j.per) - 1ull;
+    const uint64_t mask_a = j.split >= 64 ? ~0ull : (1ull << j.split) - 1ull;
+    const MsmTables t = msm_tables(j);
+    ZG_REQUIRE((j.run_mask & mask_a) == 0 || t.run_a != nullptr, ZG_ERR_INVALID_ARG, "zg_msm: run form asked for bases without a running-sum table");
+    ZG_REQUIRE((j.run_mask & ~mask_a) == 0 || t.run_b != nullptr, ZG_ERR_INVALID_ARG, "zg_msm: run form asked for bases without a running-sum table");
     if (bases_b)
         ZG_REQUIRE(bases_b->n == bases->n && bases_b->c == bases->c, ZG_ERR_INVALID_ARG,
                    "zg_msm: the two base sets differ in length or window size");
-    ZG_REQUIRE(n <= bases->n, ZG_ERR_INVALID_ARG, "zg_msm: %zu scalars for %zu bases", n, bases->n);
-    ZG_REQUIRE(batch <= 65535, ZG_ERR_UNSUPPORTED, "zg_msm: batch %zu > 65535", batch);
-    if (batch == 0) return ZG_OK;
-    // free-position odd digits (bases_enable_naf): "c" below is then the bucket-index width + 1 (nb = 2^(w-2) buckets),
-    // "W" the digit slots per scalar; the throughput form's kernels take both as they take windows
+    ZG_REQUIRE(j.n <= bases->n, ZG_ERR_INVALID_ARG, "zg_msm: %zu scalars for %zu bases", j.n, bases->n);
+    ZG_REQUIRE(j.batch <= 65535, ZG_ERR_UNSUPPORTED, "zg_msm: batch %zu > 65535", j.batch);
     // (a bit-position table serves any digit width: naf_width picks it per launch, 0 = the width the table was made for)
-    const uint32_t naf = bases->naf_w ? (naf_width ? naf_width : bases->naf_w) : 0;
+    const uint32_t naf = bases->naf_w ? (j.naf_width ? j.naf_width : bases->naf_w) : 0;
+    *naf_out = naf;
+    if (j.batch == 0) return ZG_OK;  // (nothing to multiply, nothing more to ask)
     ZG_REQUIRE(!naf || (naf >= 3 && naf <= 16), ZG_ERR_INVALID_ARG, "zg_msm: digit width %u", naf);
     ZG_REQUIRE(!bases_b || (bases_b->naf_w != 0) == (naf != 0), ZG_ERR_INVALID_ARG, "zg_msm: the two base sets differ in their digit form");
-    // (digits sit at least `naf` positions apart, the first at >= 0, the last at <= 254: at most 254 / naf + 1 of them)
-    const uint32_t c = naf ? naf - 1 : bases->c, W = naf ? 254 / naf + 1 : bases->windows, nb = 1u << (c - 1);
-    const uint32_t B = (uint32_t)batch, N = (uint32_t)n;
-    if (n == 0) {
-        std::vector<XYZZ> ids(batch, xyzz_identity());
-        ZG_HIP(hipMemcpyAsync(d_out, ids.data(), batch * sizeof(XYZZ), hipMemcpyDefault, ctx->stream));  // (d_out may be mapped host memory)
-        ZG_HIP(hipStreamSynchronize(ctx->stream));
-        return ZG_OK;
-    }
-    if (ctx->msm_pair && !naf && bases->full_table.load(std::memory_order_acquire) &&
-        (!bases_b || (bases_b->full_table.load(std::memory_order_acquire) && bases_b->full_c == bases->full_c))) {
-        // latency form over digit tables -- when every table this launch names exists
-        const uint64_t mask_a2 = split >= 64 ? ~0ull : (1ull << split) - 1ull;
-        const bool runs_ok = ((run_mask & mask_a2) == 0 || bases->full_run_table.load(std::memory_order_acquire)) &&
-                             ((run_mask & ~mask_a2) == 0 || (bases_b ? bases_b : bases)->full_run_table.load(std::memory_order_acquire));
-        if (runs_ok) return msm_full_dev(ctx, bases, bases_b, split, d_scalars, stride, per, outer, batch, n, d_out, run_mask);
-    }
+    return ZG_OK;
+}
+
+// latency form over digit tables -- when every table this job names exists
+static bool msm_full_applies(const zg_ctx* ctx, const MsmJob& j, uint32_t naf) {
+    const zg_bases *bases = j.bases, *bases_b = j.bases_b;
+    if (!(ctx->msm_pair && !naf && bases->full_table.load(std::memory_order_acquire) &&
+          (!bases_b || (bases_b->full_table.load(std::memory_order_acquire) && bases_b->full_c == bases->full_c))))
+        return false;
+    const uint64_t mask_a = j.split >= 64 ? ~0ull : (1ull << j.split) - 1ull;
+    return ((j.run_mask & mask_a) == 0 || bases->full_run_table.load(std::memory_order_acquire)) &&
+           ((j.run_mask & ~mask_a) == 0 || (bases_b ? bases_b : bases)->full_run_table.load(std::memory_order_acquire));
+}
+
+// (b) The launch plan: what (form, bases, batch, n, knobs) come to as launch shapes.  Host arithmetic only.
+struct MsmPlan {
+    uint32_t B, N;       // vectors, scalars per vector
+    uint32_t naf;        // digit width of the free-position form, 0 = windows
+    // free-position odd digits (bases_enable_naf): c is then the bucket-index width + 1 (nb = 2^(w-2) buckets), W the digit
+    // slots per scalar; the throughput form's kernels take both as they take windows
+    uint32_t c, W, nb;
+    uint64_t entries;    // digit entries per vector
+    uint32_t K;          // points per accumulate task
+    uint32_t R;          // rounds of batched-affine pre-reduction before the XYZZ chains
+    size_t cap;          // entries per vector with every bucket's range padded to a multiple of 2^R, at most
+    uint64_t left;       // summands per vector after the rounds, at most
+    uint32_t max_tasks;
+    bool pair_tasks;     // lane pairs per accumulate task
+    uint32_t rb, nblk;   // buckets per reduction block, blocks per vector (latency form)
+    int lanes;           // lanes per addition in the latency form's reduction
+    uint32_t heavy_thr, max_heavy;  // a hot bucket holds more than heavy_thr * K summands; at most max_heavy per vector
+    uint32_t strip, nstrips, strip_per;  // throughput form's reduction: buckets per lane, strips, strips per summing lane
+    uint32_t tbits;      // spare top bits the window form spreads the top window over
+    uint32_t topsplit;
+};
+static int msm_plan(const zg_ctx* ctx, const MsmJob& j, uint32_t naf, MsmPlan* out) {
+    MsmPlan p{};
+    const size_t n = j.n;
+    p.B = (uint32_t)j.batch; p.N = (uint32_t)n; p.naf = naf;
+    // (with the top digit split, ZG_MSM_TOPSPLIT, neighbouring digits may sit closer than `naf` positions; the first is at
+    //  >= 0, the last at <= 254, and 254 / naf + 1 slots hold them either way)
+    p.c = naf ? naf - 1 : j.bases->c; p.W = naf ? 254 / naf + 1 : j.bases->windows; p.nb = 1u << (p.c - 1);
     const int k_env = knob(K_MSM_K);
     // (a lone k = 14 proof with 12 / 16 / 24 / 32 / 48 points per task: 3.38 / 3.01 / 3.15 / 3.21 / 3.42 ms)
     const int kl_env = knob(K_MSM_K_LAT);
     // (... and at n = 2^17, where a lone launch fills the chip several times over, longer tasks win again -- fewer
     //  partial sums to merge: 16 / 32 / 48 -> 10.56 / 10.34 / 10.23 ms for a lone k = 17 proof; 8: every bucket turns hot, 36 ms)
     const uint32_t k_lat_default = n >= (1u << 17) ? 48u : n >= (1u << 16) ? 32u : MSM_K_LATENCY;
-    const uint32_t MSM_K = ctx->msm_pair ? (kl_env >= 4 && kl_env <= 120 ? (uint32_t)kl_env : k_lat_default)
-                                         : (k_env >= 4 && k_env <= 120 ? (uint32_t)k_env : MSM_K_THROUGHPUT);
-    const uint64_t entries = (uint64_t)N * W;
-    ZG_REQUIRE(entries < (1ull << 31), ZG_ERR_UNSUPPORTED, "zg_msm: n*windows too large");
+    p.K = ctx->msm_pair ? (kl_env >= 4 && kl_env <= 120 ? (uint32_t)kl_env : k_lat_default)
+                        : (k_env >= 4 && k_env <= 120 ? (uint32_t)k_env : MSM_K_THROUGHPUT);
+    p.entries = (uint64_t)p.N * p.W;
+    ZG_REQUIRE(p.entries < (1ull << 31), ZG_ERR_UNSUPPORTED, "zg_msm: n*windows too large");
     // R rounds of batched-affine pre-reduction before the XYZZ chains (throughput form only; ZG_MSM_AFFINE): every bucket's
     // entry range is padded to a multiple of 2^R, `cap` entries per vector at most, cap >> R points left for the tasks
     const int aff_env = knob(K_MSM_AFFINE);
-    const uint32_t R = ctx->msm_pair ? 0u : aff_env >= 0 && aff_env <= 4 ? (uint32_t)aff_env : MSM_AFFINE_ROUNDS;
-    const uint64_t padm = (1ull << R) - 1ull;
-    const size_t cap = (size_t)((entries + (uint64_t)nb * padm + padm) & ~padm);
-    ZG_REQUIRE(cap < (1ull << 31), ZG_ERR_UNSUPPORTED, "zg_msm: n*windows too large");
-    const uint64_t left = cap >> R;  // summands per vector after the rounds, at most
-    uint64_t mt = left / MSM_K + (left < nb ? left : nb) + 1;
-    const uint32_t max_tasks = (uint32_t)mt;
+    p.R = ctx->msm_pair ? 0u : aff_env >= 0 && aff_env <= 4 ? (uint32_t)aff_env : MSM_AFFINE_ROUNDS;
+    const uint64_t padm = (1ull << p.R) - 1ull;
+    p.cap = (size_t)((p.entries + (uint64_t)p.nb * padm + padm) & ~padm);
+    ZG_REQUIRE(p.cap < (1ull << 31), ZG_ERR_UNSUPPORTED, "zg_msm: n*windows too large");
+    p.left = p.cap >> p.R;
+    p.max_tasks = (uint32_t)(p.left / p.K + (p.left < p.nb ? p.left : p.nb) + 1);
+    // (lane pairs per task -- half the dependent products per point -- while the launch is latency-bound; from n = 2^16
+    //  on it fills the chip several times over and the pair form's exchanges are pure cost)
+    p.pair_tasks = ctx->msm_pair && p.N < (1u << 16);
     // buckets per reduction block: 256 in the throughput configuration; the latency configuration spreads
     // the same buckets over more, smaller workgroups (one wave per SIMD, shorter scans) while the block
     // totals still fit one block's LDS array (nblk <= rb)
-    uint32_t rb = MSM_RB;
-    int lanes = 1;
+    p.rb = MSM_RB;
+    p.lanes = 1;
     if (ctx->msm_pair) {
         // tuning overrides (tools/sweep_rb.sh, tools/sweep_lanes.sh); by default 64-bucket blocks with four
         // lanes per addition when the block totals fit (c <= 13), else 128-bucket blocks with two
         const int rb_env = knob(K_MSM_RB), lanes_env = knob(K_MSM_LANES);
         // (64-bucket blocks only while each gets a CU to itself: tools/chain_probe.hip, 3.9 us per dependent addition
         //  against 6.3 us once two workgroups share a CU and 4.3 us for two lanes on 128-bucket blocks)
-        const uint32_t nblk64 = (nb + 63) / 64;
-        const bool quad_fits = nblk64 <= 64 && (uint64_t)nblk64 * B <= (uint64_t)ctx->num_cus;
+        const uint32_t nblk64 = (p.nb + 63) / 64;
+        const bool quad_fits = nblk64 <= 64 && (uint64_t)nblk64 * p.B <= (uint64_t)ctx->num_cus;
         uint32_t want = rb_env == 64 || rb_env == 128 || rb_env == 256 ? (uint32_t)rb_env : quad_fits ? 64u : 128u;
-        if ((nb + want - 1) / want <= want) rb = want;
-        lanes = lanes_env == 2 || lanes_env == 4 ? lanes_env : rb == 64 ? 4 : 2;
-        if (rb > 128) lanes = 2;  // (4 lanes x 256 buckets would exceed a workgroup)
+        if ((p.nb + want - 1) / want <= want) p.rb = want;
+        p.lanes = lanes_env == 2 || lanes_env == 4 ? lanes_env : p.rb == 64 ? 4 : 2;
+        if (p.rb > 128) p.lanes = 2;  // (4 lanes x 256 buckets would exceed a workgroup)
     }
-    const uint32_t nblk = (nb + rb - 1) / rb;
-    ZG_REQUIRE(nblk <= 256 && nblk <= rb, ZG_ERR_UNSUPPORTED, "zg_msm: window_bits %u too large", c);
+    p.nblk = (p.nb + p.rb - 1) / p.rb;
+    ZG_REQUIRE(p.nblk <= 256 && p.nblk <= p.rb, ZG_ERR_UNSUPPORTED, "zg_msm: window_bits %u too large", p.c);
+    // a hot bucket holds more than heavy_thr * K summands (of the cap >> R that are left after the affine rounds)
+    const int hv_env = knob(K_MSM_HEAVY);
+    p.heavy_thr = hv_env >= 1 && hv_env <= 64 ? (uint32_t)hv_env : ctx->msm_pair ? MSM_HEAVY : MSM_HEAVY_THROUGHPUT;
+    p.max_heavy = (uint32_t)(p.left / ((uint64_t)p.heavy_thr * p.K)) + 1;
+    if (p.max_heavy > p.nb) p.max_heavy = p.nb;
+    const int s_env = knob(K_MSM_STRIP);
+    p.strip = s_env == 2 || s_env == 4 || s_env == 8 || s_env == 16 ? (uint32_t)s_env : MSM_STRIP;
+    p.nstrips = (p.nb + p.strip - 1) / p.strip;
+    p.strip_per = 1;
+    while (p.strip_per * MSM_STRIP_LANES < p.nstrips) p.strip_per <<= 1;
+    // largest t with r + t*r < 2^(c*W - 1):  t_max = floor(2^(cW-1) / r) - 1, r ~ 2^253.6
+    const int spare = (int)(p.c * p.W) - 1 - 254;  // 2^(cW-1) / 2^254
+    if (spare >= 1) p.tbits = (uint32_t)spare;     // 2^spare * (2^254 / r) - 1 >= 2^spare with 2^254/r ~ 1.32
+    if (p.tbits > 10) p.tbits = 10;  // (c = 12, W = 22 leaves 9 spare bits: the top window then spreads over ~1500 buckets;
+                                     // capped at 6 it spread over ~200, each just past the hot-bucket threshold)
+    p.topsplit = knob(K_MSM_TOPSPLIT) != 0 ? 1u : 0u;
+    *out = p;
+    return ZG_OK;
+}
 
+// (c) The workspace of one launch sequence (every block goes back to the context's pool with the scope).
+struct MsmWs {
+    uint32_t *dig, *cnt, *slot, *off, *toff, *tot, *ttotal, *stoff, *sbucket, *sorted;
+    XYZZ9* partial;
+    // batched-affine rounds: points of the odd rounds, of the even rounds, the per-pair prefixes, the two levels of totals
+    Affine *pts_odd, *pts_even;
+    int32_t *aff_pre, *aff_val, *aff_pfx, *aff_val2, *aff_pfx2;
+    XYZZ9 *blk_w, *tsum, *blk_p, *sfx;
+    uint32_t *hmap, *hlist, *nheavy;
+    XYZZ9* hsum;
+};
+static bool msm_workspace(WsScope& ws, const MsmPlan& p, MsmWs* out) {
+    const uint32_t B = p.B, W = p.W, nb = p.nb, R = p.R;
+    const size_t cap = p.cap;
+    MsmWs w{};
+    w.dig = ws.get<uint32_t>((size_t)B * p.entries);
+    w.cnt = ws.get<uint32_t>((size_t)B * W * (nb + 1));
+    w.slot = ws.get<uint32_t>((size_t)B * p.entries);
+    w.off = ws.get<uint32_t>((size_t)B * W * (nb + 1));
+    w.toff = ws.get<uint32_t>((size_t)B * (nb + 2));
+    w.tot = ws.get<uint32_t>((size_t)B * (nb + 2));
+    w.ttotal = ws.get<uint32_t>(B);
+    w.stoff = ws.get<uint32_t>((size_t)B * (nb + 2));
+    w.sbucket = ws.get<uint32_t>((size_t)B * (nb + 1));
+    w.sorted = ws.get<uint32_t>((size_t)B * cap);
+    w.partial = ws.get<XYZZ9>((size_t)B * p.max_tasks);
+    const uint32_t aff_lanes = R ? (uint32_t)((((cap >> 1) + AFF_A - 1) / AFF_A + 255) / 256 * 256) : 0u;  // round 1: the widest
+    const size_t aff_n1 = (size_t)B * aff_lanes, aff_n2 = (aff_n1 + AFF_S - 1) / AFF_S;
+    w.pts_odd = R >= 1 ? ws.get<Affine>((size_t)B * (cap >> 1)) : nullptr;
+    w.pts_even = R >= 2 ? ws.get<Affine>((size_t)B * (cap >> 2)) : nullptr;
+    w.aff_pre = R ? ws.get<int32_t>((size_t)9 * AFF_A * aff_n1) : nullptr;
+    w.aff_val = R ? ws.get<int32_t>((size_t)9 * aff_n1) : nullptr;
+    w.aff_pfx = R ? ws.get<int32_t>((size_t)9 * aff_n1) : nullptr;
+    w.aff_val2 = R ? ws.get<int32_t>((size_t)9 * aff_n2) : nullptr;
+    w.aff_pfx2 = R ? ws.get<int32_t>((size_t)9 * aff_n2) : nullptr;
+    w.blk_w = ws.get<XYZZ9>((size_t)B * p.nblk);
+    w.tsum = ws.get<XYZZ9>(B);  // (odd-digit buckets: the vectors' plain bucket sums, msm_bucket_sum_kernel)
+    w.blk_p = ws.get<XYZZ9>((size_t)B * p.nblk);
+    w.sfx = ws.get<XYZZ9>((size_t)B * p.nblk * p.rb);
+    w.hmap = ws.get<uint32_t>((size_t)B * (nb + 1));
+    w.hlist = ws.get<uint32_t>((size_t)B * p.max_heavy);
+    w.nheavy = ws.get<uint32_t>(B);
+    w.hsum = ws.get<XYZZ9>((size_t)B * p.max_heavy);
+    *out = w;
+    return !ws.failed;
+}
+
+// (d) The launches.  Algorithmic bytes: the UNIT is one MSM: n * (32 B scalar + 64 B base) in, 96 B out --
+// charged ONCE per launch sequence, on msm_accumulate (the kernel that reads the bases).  Every other stage kernel is
+// charged what IT streams: digit words, counters, offsets, partial sums (round 3 charged all eight kernels the whole MSM,
+// which counted the family's algorithmic bytes eight times and gave stage kernels "fractions of HBM peak" above 1).
+// scalars -> digits -> per-bucket entry lists
+static void msm_launch_sort(zg_ctx* ctx, const MsmJob& j, const MsmPlan& p, const MsmWs& w) {
+    const uint32_t B = p.B, N = p.N, c = p.c, W = p.W, nb = p.nb;
+    const double ent = (double)B * (double)p.entries, cells = (double)B * (double)W * (nb + 1.0), bk = (double)B * (nb + 2.0);
+    const double dig_bytes = (double)B * (double)N * 32.0 + ent * 4.0;  // scalars in, digit words out
+    const double hist_bytes = ent * 8.0 + cells * 4.0;                   // digits in, slots out, counts out
+    const double scan_bytes = cells * 8.0 + bk * 24.0;                   // counts in, cell offsets out, six per-bucket arrays
+    const double scat_bytes = ent * 16.0;                                // digit + slot + cell offset in, entry out
+    if (p.naf)
+        ZG_LAUNCH(ctx, "msm_digits", dig_bytes, msm_digits_naf_kernel, dim3((N + 255) / 256, B), dim3(256), 0, j.scalars, j.stride,
+                  (uint32_t)j.per, j.outer, N, p.naf, W, w.dig, j.run_mask, p.topsplit);
+    else
+        ZG_LAUNCH(ctx, "msm_digits", dig_bytes, msm_digits_kernel, dim3((N + 255) / 256, B), dim3(256), 0, j.scalars, j.stride,
+                  (uint32_t)j.per, j.outer, N, c, W, p.tbits, w.dig, j.run_mask);
+    ZG_LAUNCH(ctx, "msm_hist", hist_bytes, msm_hist_kernel, dim3(W, B), dim3(1024), (size_t)(nb + 1) * 4, w.dig, N, c, W, w.cnt,
+              w.slot);
+    ZG_LAUNCH(ctx, "msm_scan", scan_bytes, msm_scan_kernel, dim3(B), dim3(1024), (size_t)(nb + 2) * 4, w.cnt, c, W, w.toff, w.tot,
+              w.ttotal, w.hmap, w.hlist, w.nheavy, p.max_heavy, w.off, p.K, w.stoff, w.sbucket, p.R, w.sorted, p.cap, p.heavy_thr);
+    const uint32_t chunks = (N + 255) / 256;  // (chunks * W <= entries / 256 + W < 2^23)
+    const bool by_xcd = B >= 64;  // (eight vectors per XCD and more: every XCD has its share of the launch)
+    ZG_LAUNCH(ctx, "msm_scatter", scat_bytes, msm_scatter_kernel, by_xcd ? dim3(8u * chunks * W, (B + 7) / 8) : dim3(chunks * W, B),
+              dim3(256), 0, w.dig, N, c, W, w.off, w.slot, w.sorted, p.naf, p.cap, B, chunks, by_xcd ? 1u : 0u);
+}
+
+// the R rounds of batched-affine pairwise additions; returns the points the last round left (nullptr: none ran)
+static const Affine* msm_launch_affine(zg_ctx* ctx, const MsmJob& j, const MsmPlan& p, const MsmWs& w) {
+    const uint32_t B = p.B;
+    const MsmTables t = msm_tables(j);
+    const Affine* aff_pts = nullptr;
+    for (uint32_t r = 1; r <= p.R; r++) {
+        const size_t pairs = p.cap >> r;  // per vector, at most (the kernels read the vector's own count)
+        AffArgs a;
+        a.table_a = t.a; a.table_b = t.b; a.run_a = t.run_a; a.run_b = t.run_b;
+        a.split = (uint32_t)j.split; a.n_table = (uint32_t)j.bases->n; a.per = (uint32_t)j.per; a.nb = p.nb; a.run_mask = j.run_mask;
+        a.tot = w.tot; a.sorted = w.sorted; a.prev = aff_pts; a.out = (r & 1u) ? w.pts_odd : w.pts_even; a.cap = p.cap; a.r = r;
+        a.lanes = (uint32_t)(((pairs + AFF_A - 1) / AFF_A + 255) / 256 * 256);
+        a.pre = w.aff_pre; a.val = w.aff_val;
+        const size_t n1 = (size_t)B * a.lanes, n2 = (n1 + AFF_S - 1) / AFF_S;
+        const double pr = (double)B * (double)pairs;
+        const dim3 g(a.lanes / 256, B);
+        if (r == 1) ZG_LAUNCH(ctx, "msm_aff_prefix", pr * (8.0 + 64.0 + 36.0), aff_prefix_kernel<true>, g, dim3(256), 0, a);
+        else ZG_LAUNCH(ctx, "msm_aff_prefix", pr * (64.0 + 36.0), aff_prefix_kernel<false>, g, dim3(256), 0, a);
+        ZG_LAUNCH(ctx, "msm_aff_invert", (double)n1 * 72.0, aff_inv_up_kernel, dim3((uint32_t)((n2 + 255) / 256)), dim3(256), 0, w.aff_val,
+                  w.aff_pfx, n1, w.aff_val2, n2);
+        ZG_LAUNCH(ctx, "msm_aff_invert", (double)n2 * 108.0, aff_inv_top_kernel, dim3(1), dim3(AFF_TOP), 0, w.aff_val2, w.aff_pfx2, n2);
+        ZG_LAUNCH(ctx, "msm_aff_invert", (double)n1 * 108.0, aff_inv_down_kernel, dim3((uint32_t)((n2 + 255) / 256)), dim3(256), 0, w.aff_val,
+                  w.aff_pfx, n1, w.aff_val2, n2);
+        if (r == 1) ZG_LAUNCH(ctx, "msm_aff_apply", pr * (8.0 + 128.0 + 36.0 + 64.0), aff_apply_kernel<true>, g, dim3(256), 0, a);
+        else ZG_LAUNCH(ctx, "msm_aff_apply", pr * (128.0 + 36.0 + 64.0), aff_apply_kernel<false>, g, dim3(256), 0, a);
+        aff_pts = a.out;
+    }
+    return aff_pts;
+}
+
+// per-bucket entry lists -> partial sums per task: lane pairs (latency form below 2^16 scalars), the chains over what the
+// affine rounds left, or the plain chains -- three instances of one kernel, one launch
+static void msm_launch_accumulate(zg_ctx* ctx, const MsmJob& j, const MsmPlan& p, const MsmWs& w, const Affine* aff_pts) {
+    const MsmTables t = msm_tables(j);
+    const double msm_bytes = (double)p.B * ((double)p.N * 96.0 + 96.0);
+    using AccKernel = decltype(&msm_accumulate_kernel<false, false>);
+    const AccKernel acc = p.pair_tasks ? &msm_accumulate_kernel<true, false>
+                          : p.R        ? &msm_accumulate_kernel<false, true>
+                                       : &msm_accumulate_kernel<false, false>;
+    const uint32_t lanes = p.pair_tasks ? 2 * p.max_tasks : p.max_tasks;
+    ZG_LAUNCH_U(ctx, "msm_accumulate", msm_bytes, msm_bytes, acc, dim3((lanes + 255) / 256, p.B), dim3(256), 0, t.a, t.b,
+                (uint32_t)j.split, (uint32_t)j.bases->n, p.c, p.W, p.N, w.tot, w.toff, w.ttotal, w.sorted, p.max_tasks, w.partial, t.run_a,
+                t.run_b, j.run_mask, (uint32_t)j.per, w.stoff, w.sbucket, p.cap, p.pair_tasks ? 0u : p.R, p.pair_tasks ? nullptr : aff_pts);
+}
+
+// partial sums -> bucket sums -> the vectors' sums in j.out
+static void msm_launch_reduce(zg_ctx* ctx, const MsmJob& j, const MsmPlan& p, const MsmWs& w) {
+    const uint32_t B = p.B, c = p.c, nb = p.nb, nblk = p.nblk, max_tasks = p.max_tasks, max_heavy = p.max_heavy;
+    const double part_bytes = (double)B * (double)(nb < max_tasks ? nb : max_tasks) * sizeof(XYZZ9);  // >= one partial sum per bucket
+    // hot buckets are few (repeated or tiny scalars put one or two per window at most): a flat grid strides over the
+    // launch's (vector, hot bucket) pairs and leaves at once when there are none
+    const dim3 hgrid(MSM_HEAVY_WGS);
+    if (ctx->msm_pair) {  // several lanes per addition: shorter dependent chains in the reduction
+        ZG_LAUNCH(ctx, "msm_heavy", (double)B * 4.0, msm_heavy_kernel<2>, hgrid, dim3(512), 0, w.partial, w.toff, w.hlist, w.nheavy, max_tasks,
+                  max_heavy, c, w.hsum, B);
+        auto reduce = [&](auto ltag, auto rtag) {
+            constexpr int L = decltype(ltag)::value;
+            constexpr uint32_t RB = decltype(rtag)::value;
+            ZG_LAUNCH(ctx, "msm_bucket_scan", part_bytes + (double)B * nblk * (RB + 1.0) * sizeof(XYZZ9), (msm_bucket_scan_kernel<L, RB>), dim3(nblk, B), dim3(L * RB), 0,
+                      w.partial, w.toff, w.hmap, w.hsum, max_tasks, max_heavy, c, w.sfx, w.blk_p, nblk);
+            ZG_LAUNCH(ctx, "msm_bucket_sum", (double)B * nblk * (RB + 2.0) * sizeof(XYZZ9), (msm_bucket_sum_kernel<L, RB>), dim3(nblk, B), dim3(L * RB), 0, w.sfx,
+                      w.blk_p, w.blk_w, nblk, ctx->msm_tickets, j.out, p.naf ? 1u : 0u, w.tsum);
+        };
+        using I2 = std::integral_constant<int, 2>;
+        using I4 = std::integral_constant<int, 4>;
+        // (four lanes pay off while the workgroup stays at one wave per SIMD: 64-bucket blocks)
+        if (p.rb == 64 && p.lanes == 4) reduce(I4{}, std::integral_constant<uint32_t, 64>{});
+        else if (p.rb == 64) reduce(I2{}, std::integral_constant<uint32_t, 64>{});
+        else if (p.rb == 128 && p.lanes == 4) reduce(I4{}, std::integral_constant<uint32_t, 128>{});
+        else if (p.rb == 128) reduce(I2{}, std::integral_constant<uint32_t, 128>{});
+        else reduce(I2{}, std::integral_constant<uint32_t, MSM_RB>{});
+    } else {
+        ZG_LAUNCH(ctx, "msm_heavy", (double)B * 4.0, msm_heavy_groups_kernel, hgrid, dim3(256), 0, w.partial, w.toff, w.hlist, w.nheavy,
+                  max_tasks, max_heavy, c, w.hsum, B);
+        // (sfx has room for nb points per vector: the strip sums and strip-local weighted sums share it)
+        const uint32_t nstrips = p.nstrips;
+        XYZZ9 *strip_u = w.sfx, *strip_loc = w.sfx + (size_t)B * nstrips;
+        ZG_LAUNCH(ctx, "msm_strip", part_bytes + (double)B * 2.0 * nstrips * sizeof(XYZZ9), msm_strip_kernel, dim3((nstrips + 255) / 256, B), dim3(256), 0, w.partial,
+                  w.toff, w.hmap, w.hsum, max_tasks, max_heavy, c, nstrips, strip_u, strip_loc, p.strip);
+        ZG_LAUNCH(ctx, "msm_strip_sum", (double)B * (2.0 * nstrips * sizeof(XYZZ9) + sizeof(XYZZ)), msm_strip_sum_kernel, dim3(B), dim3(MSM_STRIP_LANES), 0, strip_u, strip_loc,
+                  nstrips, p.strip_per, j.out, p.strip, p.naf ? 1u : 0u);
+    }
+}
+
+int msm_dev(zg_ctx* ctx, const MsmJob& job) {
+    MsmJob j = job;
+    uint32_t naf = 0;
+    ZG_TRY(msm_check(j, &naf));
+    if (j.batch == 0) return ZG_OK;
+    if (j.n == 0) {
+        std::vector<XYZZ> ids(j.batch, xyzz_identity());
+        ZG_HIP(hipMemcpyAsync(j.out, ids.data(), j.batch * sizeof(XYZZ), hipMemcpyDefault, ctx->stream));  // (out may be mapped host memory)
+        ZG_HIP(hipStreamSynchronize(ctx->stream));
+        return ZG_OK;
+    }
+    if (msm_full_applies(ctx, j, naf)) return msm_full_dev(ctx, j);
+    MsmPlan plan;
+    ZG_TRY(msm_plan(ctx, j, naf, &plan));
     if (!ctx->msm_tickets) {  // one ticket counter per vector of a batch; the kernels leave them at zero
         gate_yield(ctx);
         ZG_HIP(hipMalloc(&ctx->msm_tickets, MSM_MAX_BATCH * sizeof(uint32_t)));
         ZG_HIP(hipMemset(ctx->msm_tickets, 0, MSM_MAX_BATCH * sizeof(uint32_t)));
     }
-    ZG_REQUIRE(B <= MSM_MAX_BATCH, ZG_ERR_UNSUPPORTED, "zg_msm: batch of %u vectors", (unsigned)B);
+    ZG_REQUIRE(plan.B <= MSM_MAX_BATCH, ZG_ERR_UNSUPPORTED, "zg_msm: batch of %u vectors", (unsigned)plan.B);
     WsScope ws(ctx);
-    uint32_t* dig = ws.get<uint32_t>((size_t)B * entries);
-    uint32_t* cnt = ws.get<uint32_t>((size_t)B * W * (nb + 1));
-    uint32_t* slot = ws.get<uint32_t>((size_t)B * entries);
-    uint32_t* off = ws.get<uint32_t>((size_t)B * W * (nb + 1));
-    uint32_t* toff = ws.get<uint32_t>((size_t)B * (nb + 2));
-    uint32_t* tot = ws.get<uint32_t>((size_t)B * (nb + 2));
-    uint32_t* ttotal = ws.get<uint32_t>(B);
-    uint32_t* stoff = ws.get<uint32_t>((size_t)B * (nb + 2));
-    uint32_t* sbucket = ws.get<uint32_t>((size_t)B * (nb + 1));
-    uint32_t* sorted = ws.get<uint32_t>((size_t)B * cap);
-    XYZZ9* partial = ws.get<XYZZ9>((size_t)B * max_tasks);
-    // batched-affine rounds: points of the odd rounds, of the even rounds, the per-pair prefixes, the two levels of totals
-    const uint32_t aff_lanes = R ? (uint32_t)((((cap >> 1) + AFF_A - 1) / AFF_A + 255) / 256 * 256) : 0u;  // round 1: the widest
-    const size_t aff_n1 = (size_t)B * aff_lanes, aff_n2 = (aff_n1 + AFF_S - 1) / AFF_S;
-    Affine* pts_odd = R >= 1 ? ws.get<Affine>((size_t)B * (cap >> 1)) : nullptr;
-    Affine* pts_even = R >= 2 ? ws.get<Affine>((size_t)B * (cap >> 2)) : nullptr;
-    int32_t* aff_pre = R ? ws.get<int32_t>((size_t)9 * AFF_A * aff_n1) : nullptr;
-    int32_t* aff_val = R ? ws.get<int32_t>((size_t)9 * aff_n1) : nullptr;
-    int32_t* aff_pfx = R ? ws.get<int32_t>((size_t)9 * aff_n1) : nullptr;
-    int32_t* aff_val2 = R ? ws.get<int32_t>((size_t)9 * aff_n2) : nullptr;
-    int32_t* aff_pfx2 = R ? ws.get<int32_t>((size_t)9 * aff_n2) : nullptr;
-    XYZZ9* blk_w = ws.get<XYZZ9>((size_t)B * nblk);
-    XYZZ9* tsum = ws.get<XYZZ9>(B);  // (odd-digit buckets: the vectors' plain bucket sums, msm_bucket_sum_kernel)
-    XYZZ9* blk_p = ws.get<XYZZ9>((size_t)B * nblk);
-    XYZZ9* sfx = ws.get<XYZZ9>((size_t)B * nblk * rb);
-    // a hot bucket holds more than heavy_thr * MSM_K summands (of the cap >> R that are left after the affine rounds)
-    const int hv_env = knob(K_MSM_HEAVY);
-    const uint32_t heavy_thr = hv_env >= 1 && hv_env <= 64 ? (uint32_t)hv_env : ctx->msm_pair ? MSM_HEAVY : MSM_HEAVY_THROUGHPUT;
-    uint32_t max_heavy = (uint32_t)(left / ((uint64_t)heavy_thr * MSM_K)) + 1;
-    if (max_heavy > nb) max_heavy = nb;
-    uint32_t* hmap = ws.get<uint32_t>((size_t)B * (nb + 1));
-    uint32_t* hlist = ws.get<uint32_t>((size_t)B * max_heavy);
-    uint32_t* nheavy = ws.get<uint32_t>(B);
-    XYZZ9* hsum = ws.get<XYZZ9>((size_t)B * max_heavy);
-    if (ws.failed) return ZG_ERR_OOM;
-
+    MsmWs w;
+    if (!msm_workspace(ws, plan, &w)) return ZG_ERR_OOM;
     {   // dynamic LDS above 64 KB is an opt-in per function AND per device
         DeviceState& ds = device_state(ctx->device);
         std::lock_guard<std::mutex> lock(ds.mu);
@@ -1892,122 +2057,26 @@ int msm_batch4_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, 
             ds.msm_attrs = true;
         }
     }
-    // Algorithmic bytes.  The UNIT is one MSM: n * (32 B scalar + 64 B base) in, 96 B out -- charged ONCE per
-    // launch sequence, on msm_accumulate (the kernel that reads the bases).  Every other stage kernel is charged what IT
-    // streams: digit words, counters, offsets, partial sums (round 3 charged all eight kernels the whole MSM, which
-    // counted the family's algorithmic bytes eight times and gave stage kernels "fractions of HBM peak" above 1).
-    const double msm_bytes = (double)B * ((double)N * 96.0 + 96.0);
-    const double ent = (double)B * (double)entries, cells = (double)B * (double)W * (nb + 1.0), bk = (double)B * (nb + 2.0);
-    const double dig_bytes = (double)B * (double)N * 32.0 + ent * 4.0;  // scalars in, digit words out
-    const double hist_bytes = ent * 8.0 + cells * 4.0;                   // digits in, slots out, counts out
-    const double scan_bytes = cells * 8.0 + bk * 24.0;                   // counts in, cell offsets out, six per-bucket arrays
-    const double scat_bytes = ent * 16.0;                                // digit + slot + cell offset in, entry out
-    const double part_bytes = (double)B * (double)(nb < max_tasks ? nb : max_tasks) * sizeof(XYZZ9);  // >= one partial sum per bucket
-    // largest t with r + t*r < 2^(c*W - 1):  t_max = floor(2^(cW-1) / r) - 1, r ~ 2^253.6
-    uint32_t tbits = 0;
-    {
-        const int spare = (int)(c * W) - 1 - 254;  // 2^(cW-1) / 2^254
-        if (spare >= 1) tbits = (uint32_t)spare;   // 2^spare * (2^254 / r) - 1 >= 2^spare with 2^254/r ~ 1.32
-        if (tbits > 10) tbits = 10;  // (c = 12, W = 22 leaves 9 spare bits: the top window then spreads over ~1500 buckets;
-                                     // capped at 6 it spread over ~200, each just past the hot-bucket threshold)
-    }
-    if (naf)
-        ZG_LAUNCH(ctx, "msm_digits", dig_bytes, msm_digits_naf_kernel, dim3((N + 255) / 256, B), dim3(256), 0, d_scalars, stride,
-                  (uint32_t)per, outer, N, naf, W, dig, run_mask, knob(K_MSM_TOPSPLIT) != 0 ? 1u : 0u);
-    else
-        ZG_LAUNCH(ctx, "msm_digits", dig_bytes, msm_digits_kernel, dim3((N + 255) / 256, B), dim3(256), 0, d_scalars, stride,
-                  (uint32_t)per, outer, N, c, W, tbits, dig, run_mask);
-    ZG_LAUNCH(ctx, "msm_hist", hist_bytes, msm_hist_kernel, dim3(W, B), dim3(1024), (size_t)(nb + 1) * 4, dig, N, c, W, cnt,
-              slot);
-    ZG_LAUNCH(ctx, "msm_scan", scan_bytes, msm_scan_kernel, dim3(B), dim3(1024), (size_t)(nb + 2) * 4, cnt, c, W, toff, tot,
-              ttotal, hmap, hlist, nheavy, max_heavy, off, MSM_K, stoff, sbucket, R, sorted, cap, heavy_thr);
-    {
-        const uint32_t chunks = (N + 255) / 256;  // (chunks * W <= entries / 256 + W < 2^23)
-        const bool by_xcd = B >= 64;  // (eight vectors per XCD and more: every XCD has its share of the launch)
-        ZG_LAUNCH(ctx, "msm_scatter", scat_bytes, msm_scatter_kernel, by_xcd ? dim3(8u * chunks * W, (B + 7) / 8) : dim3(chunks * W, B),
-                  dim3(256), 0, dig, N, c, W, off, slot, sorted, naf, cap, B, chunks, by_xcd ? 1u : 0u);
-    }
-    const Affine* aff_pts = nullptr;
-    for (uint32_t r = 1; r <= R; r++) {
-        const size_t pairs = cap >> r;  // per vector, at most (the kernels read the vector's own count)
-        AffArgs a;
-        a.table_a = bases->table; a.table_b = bases_b ? bases_b->table : bases->table; a.run_a = run_a; a.run_b = run_b;
-        a.split = (uint32_t)split; a.n_table = (uint32_t)bases->n; a.per = (uint32_t)per; a.nb = nb; a.run_mask = run_mask;
-        a.tot = tot; a.sorted = sorted; a.prev = aff_pts; a.out = (r & 1u) ? pts_odd : pts_even; a.cap = cap; a.r = r;
-        a.lanes = (uint32_t)(((pairs + AFF_A - 1) / AFF_A + 255) / 256 * 256);
-        a.pre = aff_pre; a.val = aff_val;
-        const size_t n1 = (size_t)B * a.lanes, n2 = (n1 + AFF_S - 1) / AFF_S;
-        const double pr = (double)B * (double)pairs;
-        const dim3 g(a.lanes / 256, B);
-        if (r == 1) ZG_LAUNCH(ctx, "msm_aff_prefix", pr * (8.0 + 64.0 + 36.0), aff_prefix_kernel<true>, g, dim3(256), 0, a);
-        else ZG_LAUNCH(ctx, "msm_aff_prefix", pr * (64.0 + 36.0), aff_prefix_kernel<false>, g, dim3(256), 0, a);
-        ZG_LAUNCH(ctx, "msm_aff_invert", (double)n1 * 72.0, aff_inv_up_kernel, dim3((uint32_t)((n2 + 255) / 256)), dim3(256), 0, aff_val,
-                  aff_pfx, n1, aff_val2, n2);
-        ZG_LAUNCH(ctx, "msm_aff_invert", (double)n2 * 108.0, aff_inv_top_kernel, dim3(1), dim3(AFF_TOP), 0, aff_val2, aff_pfx2, n2);
-        ZG_LAUNCH(ctx, "msm_aff_invert", (double)n1 * 108.0, aff_inv_down_kernel, dim3((uint32_t)((n2 + 255) / 256)), dim3(256), 0, aff_val,
-                  aff_pfx, n1, aff_val2, n2);
-        if (r == 1) ZG_LAUNCH(ctx, "msm_aff_apply", pr * (8.0 + 128.0 + 36.0 + 64.0), aff_apply_kernel<true>, g, dim3(256), 0, a);
-        else ZG_LAUNCH(ctx, "msm_aff_apply", pr * (128.0 + 36.0 + 64.0), aff_apply_kernel<false>, g, dim3(256), 0, a);
-        aff_pts = a.out;
-    }
-    // (lane pairs per task -- half the dependent products per point -- while the launch is latency-bound; from n = 2^16
-    //  on it fills the chip several times over and the pair form's exchanges are pure cost)
-    if (ctx->msm_pair && N < (1u << 16)) {
-        ZG_LAUNCH_U(ctx, "msm_accumulate", msm_bytes, msm_bytes, msm_accumulate_kernel<true>, dim3((2 * max_tasks + 255) / 256, B), dim3(256),
-                  0, bases->table, bases_b ? bases_b->table : bases->table, (uint32_t)split, (uint32_t)bases->n, c, W, N, tot,
-                  toff, ttotal, sorted, max_tasks, partial, run_a, run_b, run_mask, (uint32_t)per, stoff, sbucket, cap, 0u,
-                  (const Affine*)nullptr);
-    } else if (R) {
-        ZG_LAUNCH_U(ctx, "msm_accumulate", msm_bytes, msm_bytes, (msm_accumulate_kernel<false, true>), dim3((max_tasks + 255) / 256, B),
-                    dim3(256), 0, bases->table, bases_b ? bases_b->table : bases->table, (uint32_t)split, (uint32_t)bases->n, c, W, N,
-                    tot, toff, ttotal, sorted, max_tasks, partial, run_a, run_b, run_mask, (uint32_t)per, stoff, sbucket, cap, R,
-                    aff_pts);
-    } else {
-        ZG_LAUNCH_U(ctx, "msm_accumulate", msm_bytes, msm_bytes, msm_accumulate_kernel<false>, dim3((max_tasks + 255) / 256, B), dim3(256), 0,
-                  bases->table, bases_b ? bases_b->table : bases->table, (uint32_t)split, (uint32_t)bases->n, c, W, N, tot,
-                  toff, ttotal, sorted, max_tasks, partial, run_a, run_b, run_mask, (uint32_t)per, stoff, sbucket, cap, 0u,
-                  (const Affine*)nullptr);
-    }
-    // hot buckets are few (repeated or tiny scalars put one or two per window at most): a flat grid strides over the
-    // launch's (vector, hot bucket) pairs and leaves at once when there are none
-    const dim3 hgrid(MSM_HEAVY_WGS);
-    if (ctx->msm_pair) {  // several lanes per addition: shorter dependent chains in the reduction
-        ZG_LAUNCH(ctx, "msm_heavy", (double)B * 4.0, msm_heavy_kernel<2>, hgrid, dim3(512), 0, partial, toff, hlist, nheavy, max_tasks,
-                  max_heavy, c, hsum, B);
-        auto reduce = [&](auto ltag, auto rtag) {
-            constexpr int L = decltype(ltag)::value;
-            constexpr uint32_t RB = decltype(rtag)::value;
-            ZG_LAUNCH(ctx, "msm_bucket_scan", part_bytes + (double)B * nblk * (RB + 1.0) * sizeof(XYZZ9), (msm_bucket_scan_kernel<L, RB>), dim3(nblk, B), dim3(L * RB), 0,
-                      partial, toff, hmap, hsum, max_tasks, max_heavy, c, sfx, blk_p, nblk);
-            ZG_LAUNCH(ctx, "msm_bucket_sum", (double)B * nblk * (RB + 2.0) * sizeof(XYZZ9), (msm_bucket_sum_kernel<L, RB>), dim3(nblk, B), dim3(L * RB), 0, sfx,
-                      blk_p, blk_w, nblk, ctx->msm_tickets, d_out, naf ? 1u : 0u, tsum);
-        };
-        using I2 = std::integral_constant<int, 2>;
-        using I4 = std::integral_constant<int, 4>;
-        // (four lanes pay off while the workgroup stays at one wave per SIMD: 64-bucket blocks)
-        if (rb == 64 && lanes == 4) reduce(I4{}, std::integral_constant<uint32_t, 64>{});
-        else if (rb == 64) reduce(I2{}, std::integral_constant<uint32_t, 64>{});
-        else if (rb == 128 && lanes == 4) reduce(I4{}, std::integral_constant<uint32_t, 128>{});
-        else if (rb == 128) reduce(I2{}, std::integral_constant<uint32_t, 128>{});
-        else reduce(I2{}, std::integral_constant<uint32_t, MSM_RB>{});
-    } else {
-        ZG_LAUNCH(ctx, "msm_heavy", (double)B * 4.0, msm_heavy_groups_kernel, hgrid, dim3(256), 0, partial, toff, hlist, nheavy,
-                  max_tasks, max_heavy, c, hsum, B);
-        // (sfx has room for nb points per vector: the strip sums and strip-local weighted sums share it)
-        const int s_env = knob(K_MSM_STRIP);
-        const uint32_t S = s_env == 2 || s_env == 4 || s_env == 8 || s_env == 16 ? (uint32_t)s_env : MSM_STRIP;
-        const uint32_t nstrips = (nb + S - 1) / S;
-        uint32_t per = 1;
-        while (per * MSM_STRIP_LANES < nstrips) per <<= 1;
-        XYZZ9 *strip_u = sfx, *strip_loc = sfx + (size_t)B * nstrips;
-        ZG_LAUNCH(ctx, "msm_strip", part_bytes + (double)B * 2.0 * nstrips * sizeof(XYZZ9), msm_strip_kernel, dim3((nstrips + 255) / 256, B), dim3(256), 0, partial,
-                  toff, hmap, hsum, max_tasks, max_heavy, c, nstrips, strip_u, strip_loc, S);
-        ZG_LAUNCH(ctx, "msm_strip_sum", (double)B * (2.0 * nstrips * sizeof(XYZZ9) + sizeof(XYZZ)), msm_strip_sum_kernel, dim3(B), dim3(MSM_STRIP_LANES), 0, strip_u, strip_loc,
-                  nstrips, per, d_out, S, naf ? 1u : 0u);
-    }
+    msm_launch_sort(ctx, j, plan, w);
+    msm_launch_accumulate(ctx, j, plan, w, msm_launch_affine(ctx, j, plan, w));
+    msm_launch_reduce(ctx, j, plan, w);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
+
+// A plain batch of vectors against one base set (the C ABI's zg_msm*).
+// (a base set with a bit-position table, zg_bases_enable_bit_table, is multiplied in the free-position form by a
+//  context in its throughput form; a latency-form context keeps the window table -- DESIGN.md 4)
+static int msm_plain_dev(zg_ctx* ctx, const zg_bases* bases, const Fe* d_scalars, size_t stride, size_t batch, size_t n, XYZZ* d_out) {
+    if (const zg_bases* d = bases_dense(bases); d && d->naf_w && !ctx->msm_pair) bases = d;
+    MsmJob j;
+    j.bases = bases; j.split = batch;
+    j.scalars = d_scalars; j.stride = stride;
+    j.batch = batch; j.n = n;
+    j.out = d_out;
+    return msm_dev(ctx, j);
+}
+
 
 // host: XYZZ -> normalised Jacobian (z = 1; identity = (0, 1, 0)), one shared inversion
 void xyzz_batch_normalise(const XYZZ* in, size_t count, zg_g1* out) {
@@ -2096,7 +2165,7 @@ int zg_msm_batch_dev(zg_ctx* ctx, const zg_bases* bases, const void* d_scalars, 
     ZG_REQUIRE(ctx && bases && d_scalars && d_out_xyzz, ZG_ERR_INVALID_ARG, "zg_msm_batch_dev: null argument");
     ZG_REQUIRE(bases->device == ctx->device, ZG_ERR_INVALID_ARG, "zg_msm_batch_dev: bases live on another device");
     ZG_ENTER(ctx);
-    return msm_batch_dev(ctx, bases, (const Fe*)d_scalars, stride_elems, batch, n, (XYZZ*)d_out_xyzz);
+    return msm_plain_dev(ctx, bases, (const Fe*)d_scalars, stride_elems, batch, n, (XYZZ*)d_out_xyzz);
 }
 
 int zg_msm_finish(zg_ctx* ctx, const void* d_xyzz, size_t batch, zg_g1* out) {
@@ -2125,7 +2194,7 @@ int zg_msm_batch(zg_ctx* ctx, const zg_bases* bases, const zg_fr* const* scalars
         ZG_REQUIRE(scalars[b] != nullptr || n == 0, ZG_ERR_INVALID_ARG, "zg_msm_batch: scalars[%zu] is null", b);
         if (n) ZG_HIP(hipMemcpyAsync(d + b * n, scalars[b], n * 32, hipMemcpyHostToDevice, ctx->stream));
     }
-    ZG_TRY(msm_batch_dev(ctx, bases, d, n, batch, n, r));
+    ZG_TRY(msm_plain_dev(ctx, bases, d, n, batch, n, r));
     return zg_msm_finish(ctx, r, batch, out);
 }
 

@@ -16,10 +16,11 @@
 //   store so a polynomial crosses HBM exactly twice per transform.
 // The kernel is integer-ALU bound (one 254-bit Montgomery product per butterfly), not MFMA work.
 //
-// A nine-limb back end (field9.h; 36-byte lazily reduced elements in LDS, 18 % fewer instructions per butterfly) was
-// built, bit-exact, and measured on par at best (1.56 vs 1.56 ms/proof; 1.75 vs 1.65 with 4-byte LDS accesses): the
-// transform is bound by its LDS round trips and barriers before its VALU work.  It was removed in round 3 with its
-// ZG_NTT9 switch (git history has it); the twiddle tables keep their second half, omega^i * 2^5, which evaluate_h reads.
+// The pass exists twice: on 8 x 32-bit limbs (ntt_pass_kernel) and on nine 29-bit limbs (ntt9_pass_kernel: field9.h,
+// 36-byte lazily reduced elements in LDS, 18 % fewer instructions per butterfly).  Under many provers the two measure on
+// par at best -- the transform is bound by its LDS round trips and barriers before its VALU work -- while a lone proof's
+// transforms finish sooner on nine limbs: that form is the default of the latency form, ZG_NTT9 = 0 / 1 forces one
+// (ntt_run).  The twiddle tables carry a second half, omega^i * 2^5, which the nine-limb pass and evaluate_h read.
 #include "poly.h"
 #include "field9.h"
 
@@ -840,12 +841,6 @@ int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len,
 }  // namespace zg
 
 using namespace zg;
-
-static inline Fe to_fe(const zg_fr* p) {
-    Fe r;
-    memcpy(&r, p, 32);
-    return r;
-}
 
 extern "C" {
 

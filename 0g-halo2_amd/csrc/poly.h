@@ -1,7 +1,8 @@
-// Device-side circuit image and the launch helpers of poly.hip (shared with prover.hip).
+// Device-side circuit image and the launch helpers of poly.hip (shared with prover.hip and prove_batch.hip).
 #pragma once
 
 #include "common.h"
+#include "msm.h"
 
 namespace zg {
 
@@ -113,6 +114,11 @@ enum {
     TAG_RANDOM_POLY = 6,
     TAG_VERIFY_BATCH = 7  // the verifier's batch weights r_b (verify.hip), not a blinding scalar
 };
+inline Fe to_fe(const zg_fr* s) {
+    Fe r;
+    memcpy(&r, s, 32);
+    return r;
+}
 // rand_fr on the host (Montgomery form)
 Fe rand_fr_host(const uint32_t* key, uint32_t tag, uint64_t index);
 
@@ -218,7 +224,7 @@ int coeff_to_coset_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, uint32_t i
                        size_t batch, uint32_t ext_k, bool hat, int zeta_pow, const Grouping* grp = nullptr);
 int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len, Fe* d_out, bool unhat, int zeta_pow,
                        size_t batch = 1, size_t in_stride = 0, size_t out_stride = 0);
-// split extended domain (prover.hip): the pieces of the interpolation between its two cosets
+// split extended domain (prove_batch.hip): the pieces of the interpolation between its two cosets
 // (each for nb proofs: proof b's arrays `*_bs` elements after proof b-1's)
 int poly_fold(zg_ctx* ctx, uint32_t nb, const Fe* a, size_t a_bs, uint32_t len, uint32_t parts, const Fe& e, Fe* out,
               size_t out_bs);  // out[r] = sum_q a[r + q*len] e^q
@@ -226,25 +232,5 @@ int poly_diff_scale(zg_ctx* ctx, uint32_t nb, const Fe* u, size_t u_bs, const Fe
                     Fe* out, size_t out_bs, uint32_t len);  // (u*cu - v)*scale
 int poly_split_combine(zg_ctx* ctx, uint32_t nb, Fe* h, size_t h_bs, const Fe* b, size_t b_bs, uint32_t len, const Fe& c1,
                        uint32_t hi_at);  // h[j] -= c1 b[j]; h[hi_at + j] = b[j]
-// from msm.hip
-int msm_batch_dev(zg_ctx* ctx, const zg_bases* bases, const Fe* d_scalars, size_t stride, size_t batch, size_t n,
-                  XYZZ* d_out);
-int msm_batch2_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t batch, size_t n, XYZZ* d_out);
-int msm_batch3_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask);
-// groups of `per` vectors: vector v at d_scalars + (v / per) * outer + (v % per) * stride; split / run_mask by v % per
-int msm_batch4_dev(zg_ctx* ctx, const zg_bases* bases, const zg_bases* bases_b, size_t split, const Fe* d_scalars,
-                   size_t stride, size_t per, size_t outer, size_t batch, size_t n, XYZZ* d_out, uint64_t run_mask,
-                   uint32_t naf_width);
-int bases_enable_runs(zg_ctx* ctx, zg_bases* b);  // running-sum table for the run form (idempotent)
-// b->dense: one row per bit position, odd w-bit digits (strict: refuse a table made for another default width)
-int bases_enable_naf(zg_ctx* ctx, zg_bases* b, uint32_t w, bool strict = false);
-int bases_register_dev(zg_ctx* ctx, const Affine* d_bases, size_t n, uint32_t window_bits, zg_bases** out);
-// digit tables of the latency form (every multiple of every window; window_bits 0 = from n and the free memory, which may
-// decide on none); with_runs: for the running sums too (the set must have its running-sum table)
-int bases_enable_full(zg_ctx* ctx, zg_bases* b, uint32_t window_bits, bool with_runs);
-uint32_t default_full_bits(size_t n, double budget_bytes);  // 0 = no digit tables at this size / budget
-void xyzz_batch_normalise(const XYZZ* in, size_t count, zg_g1* out);
 
 }  // namespace zg

@@ -562,6 +562,25 @@ size_t poly_grand_product_tmp_elems(uint32_t n, uint32_t batch) {  // (room for 
     return strips > blocks ? strips : blocks;
 }
 
+// the host's shared inversion of up to FESET_MAX grand-product totals -- Montgomery's trick: prefix products, one inversion,
+// walk back (a zero total inverts to zero, as Fr::inv does)
+static void invert_totals(const Fe* h, uint32_t batch, FeSet& inv_set) {
+    Fe pre[FESET_MAX], acc = Fr::one();
+    for (uint32_t b = 0; b < batch; b++) {
+        pre[b] = acc;
+        if (!fe_is_zero(h[b])) acc = Fr::mul(acc, h[b]);
+    }
+    acc = Fr::inv(acc);
+    for (uint32_t b = batch; b-- > 0;) {
+        if (fe_is_zero(h[b])) {
+            inv_set.v[b] = fe_zero();
+            continue;
+        }
+        inv_set.v[b] = Fr::mul(acc, pre[b]);
+        acc = Fr::mul(acc, h[b]);
+    }
+}
+
 // the latency form's launch sequence (tmp: 2*batch*n + 2*batch*nblk + 2*batch elements)
 static int grand_product_blocks(zg_ctx* ctx, const Fe* num, const Fe* den, const Fe* d_z0, Fe* z, Fe* tmp, uint32_t n,
                                 uint32_t batch, uint32_t chain, uint32_t last, uint32_t per, size_t z_outer, int half) {
@@ -601,21 +620,7 @@ static int grand_product_blocks(zg_ctx* ctx, const Fe* num, const Fe* den, const
     memset(&inv_set, 0, sizeof(inv_set));
     if (host_inv) {
         ZG_HIP(hipStreamSynchronize(ctx->stream));
-        // Montgomery's trick: prefix products, one inversion, walk back (a zero total inverts to zero, as Fr::inv does)
-        Fe pre[FESET_MAX], acc = Fr::one();
-        for (uint32_t b = 0; b < batch; b++) {
-            pre[b] = acc;
-            if (!fe_is_zero(h[b])) acc = Fr::mul(acc, h[b]);
-        }
-        acc = Fr::inv(acc);
-        for (uint32_t b = batch; b-- > 0;) {
-            if (fe_is_zero(h[b])) {
-                inv_set.v[b] = fe_zero();
-                continue;
-            }
-            inv_set.v[b] = Fr::mul(acc, pre[b]);
-            acc = Fr::mul(acc, h[b]);
-        }
+        invert_totals(h, batch, inv_set);
     }
     ZG_LAUNCH_U(ctx, "grand_product_apply", bytes, bytes, gp_apply_kernel, dim3(nblk, batch), dim3(GP_BLOCK), 0, locn, locd, totn,
               totd, tinv, zlast, d_z0, z, n, nblk, chain, inv_set, host_inv ? 1u : 0u, per, z_outer);
@@ -657,21 +662,7 @@ int poly_grand_product(zg_ctx* ctx, const Fe* num, const Fe* den, const Fe* d_z0
     memset(&inv_set, 0, sizeof(inv_set));
     if (host_inv) {
         ZG_HIP(hipStreamSynchronize(ctx->stream));
-        // Montgomery's trick: prefix products, one inversion, walk back (a zero total inverts to zero, as Fr::inv does)
-        Fe pre[FESET_MAX], acc = Fr::one();
-        for (uint32_t b = 0; b < batch; b++) {
-            pre[b] = acc;
-            if (!fe_is_zero(h[b])) acc = Fr::mul(acc, h[b]);
-        }
-        acc = Fr::inv(acc);
-        for (uint32_t b = batch; b-- > 0;) {
-            if (fe_is_zero(h[b])) {
-                inv_set.v[b] = fe_zero();
-                continue;
-            }
-            inv_set.v[b] = Fr::mul(acc, pre[b]);
-            acc = Fr::mul(acc, h[b]);
-        }
+        invert_totals(h, batch, inv_set);
     }
     ZG_LAUNCH_U(ctx, "grand_product_apply", (double)batch * n * 128, bytes, gp_strip_apply_kernel, dim3((lanes + 255) / 256, batch), dim3(256), 0, num, den,
               locd, aux, tinv, zlast, d_z0, z, n, lanes, strip, chain, inv_set, host_inv ? 1u : 0u, per, z_outer);
@@ -1501,7 +1492,7 @@ int poly_scale(zg_ctx* ctx, const Fe* in, Fe* out, size_t count, const Fe& facto
     return ZG_OK;
 }
 
-// ---- interpolation across the two cosets of the split extended domain (prover.hip); proof b = blockIdx.y
+// ---- interpolation across the two cosets of the split extended domain (prove_batch.hip); proof b = blockIdx.y
 __global__ void fold_kernel(const Fe* a, size_t a_bs, uint32_t len, uint32_t parts, Fe e, Fe* out, size_t out_bs) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= len) return;
@@ -1552,3 +1543,97 @@ int poly_split_combine(zg_ctx* ctx, uint32_t nb, Fe* h, size_t h_bs, const Fe* b
 }
 
 }  // namespace zg
+
+using namespace zg;
+
+// ------------------------------------------------------------------ context-level entries (no prover): host-facing forms
+// of the launch helpers above
+extern "C" {
+
+int zg_grand_product_dev(zg_ctx* ctx, const void* d_num, const void* d_den, const zg_fr* z0, size_t n, void* d_z) {
+    ZG_REQUIRE(ctx && d_num && d_den && d_z && z0, ZG_ERR_INVALID_ARG, "zg_grand_product_dev: null argument");
+    ZG_REQUIRE(n < (1u << 28), ZG_ERR_UNSUPPORTED, "zg_grand_product_dev: n too large");
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    Fe* tmp = ws.get<Fe>(poly_grand_product_tmp_elems((uint32_t)n, 1) + 1);
+    if (ws.failed) return ZG_ERR_OOM;
+    Fe* z0d = tmp + poly_grand_product_tmp_elems((uint32_t)n, 1);
+    ZG_HIP(hipMemcpyAsync(z0d, z0, 32, hipMemcpyHostToDevice, ctx->stream));
+    ZG_TRY(poly_grand_product(ctx, (const Fe*)d_num, (const Fe*)d_den, z0d, (Fe*)d_z, tmp, (uint32_t)n, 1, 0, 0));
+    ZG_HIP(hipStreamSynchronize(ctx->stream));
+    return ZG_OK;
+}
+
+// Host-pointer form of the same (lookup::prover::commit_product / permutation::prover::commit's running product):
+// z[0] = z0, z[i+1] = z[i] * num[i] / den[i] with BatchInvert's rule for a zero denominator (ratio 0); z has n entries.
+int zg_grand_product(zg_ctx* ctx, const zg_fr* num, const zg_fr* den, const zg_fr* z0, size_t n, zg_fr* z) {
+    ZG_REQUIRE(ctx && num && den && z0 && z, ZG_ERR_INVALID_ARG, "zg_grand_product: null argument");
+    ZG_REQUIRE(n >= 1 && n < (1u << 28), ZG_ERR_UNSUPPORTED, "zg_grand_product: n out of range");
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    Fe* d = ws.get<Fe>(3 * n);
+    if (ws.failed) return ZG_ERR_OOM;
+    ZG_HIP(hipMemcpyAsync(d, num, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZG_HIP(hipMemcpyAsync(d + n, den, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZG_TRY(zg_grand_product_dev(ctx, d, d + n, z0, n, d + 2 * n));
+    ZG_HIP(hipMemcpy(z, d + 2 * n, n * 32, hipMemcpyDeviceToHost));
+    return ZG_OK;
+}
+
+int zg_eval_polys_dev(zg_ctx* ctx, const void* d_polys, size_t stride_elems, size_t n, const uint32_t* poly_index,
+                      const zg_fr* points, size_t count, zg_fr* out) {
+    ZG_REQUIRE(ctx && d_polys && poly_index && points && out, ZG_ERR_INVALID_ARG, "zg_eval_polys_dev: null argument");
+    if (!count) return ZG_OK;
+    ZG_REQUIRE(stride_elems == n || count == 0, ZG_ERR_UNSUPPORTED, "zg_eval_polys_dev: stride %zu != n %zu", stride_elems, n);
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    // the pairs are served PC_MAX_POINTS at a time, every pair with a powers row of its own (callers with shared
+    // points should use the prover)
+    Fe* pw = ws.get<Fe>((size_t)PC_MAX_POINTS * n);
+    uint32_t* di = ws.get<uint32_t>(2 * PC_MAX_POINTS);
+    Fe* de = ws.get<Fe>(PC_MAX_POINTS);
+    ProofConst* dpc = ws.get<ProofConst>(1);
+    if (ws.failed) return ZG_ERR_OOM;
+    PolySet ps;
+    ps.sh = (const Fe*)d_polys; ps.pp = nullptr; ps.nsh = 0xffffffffu; ps.n = n; ps.pp_bs = 0;
+    for (size_t c0 = 0; c0 < count; c0 += PC_MAX_POINTS) {
+        const uint32_t m = (uint32_t)std::min<size_t>(PC_MAX_POINTS, count - c0);
+        ProofConst hc;
+        memset(&hc, 0, sizeof(hc));
+        uint32_t idx[2 * PC_MAX_POINTS];
+        for (uint32_t i = 0; i < m; i++) {
+            hc.points[i] = to_fe(&points[c0 + i]);
+            idx[i] = poly_index[c0 + i];
+            idx[m + i] = i;
+        }
+        ZG_HIP(hipMemcpyAsync(dpc, &hc, sizeof(hc), hipMemcpyHostToDevice, ctx->stream));
+        ZG_HIP(hipMemcpyAsync(di, idx, 2 * m * 4, hipMemcpyHostToDevice, ctx->stream));
+        ZG_HIP(hipStreamSynchronize(ctx->stream));  // (hc and idx are stack memory)
+        ZG_TRY(poly_powers(ctx, dpc, 1, m, (uint32_t)n, pw, 0));
+        ZG_TRY(poly_dot(ctx, ps, 1, (uint32_t)n, di, di + m, pw, 0, m, de, 0));
+        ZG_HIP(hipMemcpyAsync(out + c0, de, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+        ZG_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return ZG_OK;
+}
+
+int zg_kate_division_dev(zg_ctx* ctx, const void* d_a, size_t n, const zg_fr* z, void* d_q) {
+    ZG_REQUIRE(ctx && d_a && z && d_q && n >= 1, ZG_ERR_INVALID_ARG, "zg_kate_division_dev: bad argument");
+    ZG_ENTER(ctx);
+    ZG_REQUIRE(n < (1u << 28), ZG_ERR_UNSUPPORTED, "zg_kate_division_dev: n too large");
+    WsScope ws(ctx);
+    Fe* tmp = ws.get<Fe>(poly_kate_tmp_elems((uint32_t)n, 1));
+    ProofConst* dpc = ws.get<ProofConst>(1);
+    if (ws.failed) return ZG_ERR_OOM;
+    ProofConst hc;
+    memset(&hc, 0, sizeof(hc));
+    hc.points[0] = to_fe(z);
+    ZG_HIP(hipMemcpyAsync(dpc, &hc, sizeof(hc), hipMemcpyHostToDevice, ctx->stream));
+    ZG_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t slot0 = 0;
+    ZG_TRY(poly_kate_division(ctx, dpc, 1, &slot0, 1, (const Fe*)d_a, n, 0, (Fe*)d_q, n, 0, tmp, (uint32_t)n));
+    ZG_HIP(hipStreamSynchronize(ctx->stream));
+    return ZG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,1017 @@
+// create_proof for one circuit instance on one MI355X -- replaces
+// halo2_proofs::plonk::create_proof::<KZGCommitmentScheme<Bn256>, ProverGWC, _, _, EvmTranscript, _>
+// as Wnn::proof calls it (/root/reference/src/wnn.rs:232-262; upstream v2023_04_20 src/plonk/prover.rs).
+//
+// Proofs are made in lock-step batches: one launch sequence serves `nb` circuit instances at once (a single proof
+// is the batch of one), each with its own Fiat-Shamir transcript on the host.
+//
+// Everything between "advice columns assigned" and "proof bytes" stays in HBM: columns, coefficient
+// forms, extended cosets, lookup/permutation products, h(X).  The host only sees what the Fiat-Shamir
+// transcript needs -- commitments (one 128-B XYZZ point each), evaluations (32 B each).  Even
+// lookup::prover::permute_expression_pair (a sort + BTreeMap walk upstream) runs on the device
+// (sort.hip).  Work that does not depend on the next challenge (iNTTs, coset NTTs) runs on a side
+// stream while the main stream works through the commitment MSM and the host hashes.
+#include <algorithm>
+#include <chrono>
+
+#include "prover.h"
+#include "field9.h"
+#include "transcript.h"
+
+using namespace zg;
+
+namespace {
+
+Fe rotate_omega(const PkDev& k, const Fe& x, int32_t rot) {
+    Fe w = rot >= 0 ? Fr::pow_u64(k.omega, (uint64_t)rot) : Fr::pow_u64(k.omega_inv, (uint64_t)(-(int64_t)rot));
+    return Fr::mul(x, w);
+}
+
+// ZG_LAT_GATE (ProveBatch::run).  OFF unless asked for: a kernel that waits for the host is only safe while every stream
+// of the process has a hardware queue of its own (GPU_MAX_HW_QUEUES, default 4): packets of streams that share a queue
+// run in order, so this prover's side stream -- which the host waits for before it opens the next gate -- may sit behind
+// another stream's wait for work that itself sits behind the gate.  The kernel's time limit turns that cycle into a
+// stall and a second, plain run of the proof (prove_batch_impl), never into a hang or a wrong proof.
+constexpr int LAT_GATE_DEFAULT = 0;
+constexpr int LAT_PULL_DEFAULT = 1;  // (ZG_LAT_PULL: a lone proof's small uploads by a one-wave kernel instead of a copy command)
+// Small host->device transfers go through the staging range of the pinned arena (PinnedArena): hipMemcpyAsync from
+// pageable memory blocks the calling thread until the stream has drained up to the copy, which serialises host and
+// GPU inside a proof and throttles concurrent proof streams.  Each region is written once per batch.
+void* stage(zg_prover* p, const void* src, size_t bytes) {
+    void* dst = p->pin.stage_take(bytes);
+    if (dst) memcpy(dst, src, bytes);
+    return dst;  // (nullptr: the caller falls back to a direct copy)
+}
+// Index lists that only depend on the circuit (which polynomial is opened where) come out the same for every
+// proof: upload one when its content differs from what that destination already holds.
+int h2d_list(zg_prover* p, uint32_t* d_dst, const std::vector<uint32_t>& list) {
+    std::vector<uint32_t>& held = p->uploaded_lists[d_dst];
+    if (held == list) return ZG_OK;
+    const void* s = stage(p, list.data(), list.size() * 4);
+    ZG_HIP(hipMemcpyAsync(d_dst, s ? s : list.data(), list.size() * 4, hipMemcpyHostToDevice, p->ctx->stream));
+    if (!s) ZG_HIP(hipStreamSynchronize(p->ctx->stream));  // (the source was pageable memory of the caller)
+    held = list;
+    return ZG_OK;
+}
+// (a lone proof's version of a small upload: ONE wave reads the staged bytes through the device's view of the pinned arena
+//  and writes them where they go -- a kernel dispatch instead of a copy command behind every transcript step)
+__global__ void pull_kernel(const uint4* __restrict__ src_mapped, uint4* __restrict__ dst, uint32_t n16) {
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src_mapped[i];
+}
+// The gate: ONE workgroup that waits until the host has written `seq` into the gate word (mapped, coherent host memory),
+// then copies the scalars the host staged BEFORE that store to where the kernels read them -- wait and upload in one
+// dispatch.  (hipStreamWaitValue32 + pull_kernel, the first version, were two: on this runtime the stream wait is itself
+// a spinning kernel, __amd_rocclr_streamOpsWait.)  Every wave reaches the end: a gate nobody opens within `max_ticks` of
+// the 100 MHz clock gives up, says so in *gave_up (the host then fails the proof) and leaves dst alone.
+__global__ void gate_pull_kernel(const uint32_t* gate, uint32_t seq, uint32_t* gave_up, uint64_t max_ticks, const uint4* __restrict__ src_mapped,
+                                 uint4* __restrict__ dst, uint32_t n16) {
+    __shared__ uint32_t open;
+    if (threadIdx.x == 0) {
+        const uint64_t t0 = wall_clock64();
+        uint32_t got = 1;
+        while (__hip_atomic_load(gate, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) != seq) {
+            if (wall_clock64() - t0 > max_ticks) {
+                got = 0;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        if (!got) __hip_atomic_store(gave_up, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        open = got;
+    }
+    __syncthreads();
+    if (!open) return;
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src_mapped[i];
+}
+constexpr uint64_t GATE_MAX_TICKS = 400000000ull;  // 4 s: a host thread that is merely descheduled comes back sooner
+int h2d(zg_prover* p, void* d_dst, const void* src, size_t bytes) {
+    const void* s = stage(p, src, bytes);
+    const int pull = knob(K_LAT_PULL);
+    if (s && p->use_side && (pull < 0 ? LAT_PULL_DEFAULT : pull) != 0 && bytes % 16 == 0 && bytes <= (1u << 16) && ((uintptr_t)d_dst & 15u) == 0) {
+        const uint4* dev_view = p->pin.dev_view(reinterpret_cast<const uint4*>(s));
+        ZG_LAUNCH(p->ctx, "pull", (double)bytes * 2, pull_kernel, dim3(1), dim3(256), 0, dev_view, (uint4*)d_dst, (uint32_t)(bytes / 16));
+        ZG_HIP(hipGetLastError());
+        return ZG_OK;
+    }
+    ZG_HIP(hipMemcpyAsync(d_dst, s ? s : src, bytes, hipMemcpyHostToDevice, p->ctx->stream));
+    if (!s) ZG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return ZG_OK;
+}
+// the bit-position table of a base set for the throughput form's commitments of full-size scalars (the sorted a' / s'
+// columns and the products in their run form, the random vectors), else the base set itself
+// (a lone proof keeps the window tables: from the 0.27 GB bit-position table, which no cache holds, its few waves wait on
+//  the gathers -- 3.27 against 3.01 ms with the same bucket count)
+static const zg_bases* naf_of(const zg_prover* p, const zg_bases* b) {
+    const zg_bases* d = bases_dense(b);
+    return d && d->naf_w && !p->ctx->msm_pair ? d : b;
+}
+
+// the table of g for the all-random commitments (the quotient pieces, the opening quotients): its bit-position table in
+// the throughput form, recoded at the width the table was made for
+static const zg_bases* dense_g(const zg_prover* p) { return naf_of(p, p->g); }
+
+// Commitments of a phase: one MSM launch sequence over m.batch = groups x per scalar vectors (msm_dev), against this
+// prover's point range of the base sets; the XYZZ results go to the host behind it.
+int commit(zg_prover* p, MsmJob m, int wait_ix) {
+    ZG_REQUIRE(m.batch <= p->maxv * (size_t)p->cap, ZG_ERR_INVALID_ARG, "zg_prover: %zu commitments in one phase", m.batch);
+    // The last kernel of the MSM writes its sums straight into the pinned host buffer the transcript reads (the memory is
+    // mapped into the device's address space): no copy command between the MSM and the host -- a command costs a lone
+    // proof its dispatch latency on top of its run time, ~9 us per commitment phase.  Only the in-library RCCL exchange
+    // keeps the sums on the device (all-gather and the additions follow on this stream) and copies the result out.
+    XYZZ* h_out = p->pin.dev_view(p->pin.results());
+    m.scalars += p->shard_lo;
+    m.n = p->shard_n;
+    m.out = p->rccl_comm ? p->xyzz : h_out;
+    ZG_TRY(msm_dev(p->ctx, m));
+    if (p->rccl_comm) ZG_TRY(shard_gather_sum(p, m.batch, h_out));  // (over xGMI, on this stream)
+    ZG_HIP(hipEventRecord(p->evs[wait_ix], p->ctx->stream));
+    return ZG_OK;
+}
+// ... and waits for ONLY that launch sequence; with a sharded SRS the partial commitments of all ranks are exchanged
+// (all-gather) and summed here -- EC addition is not a reduction operator of the collective library
+int wait_points(zg_prover* p, size_t count, std::vector<Jac>& out, int wait_ix) {
+    // (hipEventSynchronize already polls: the events are created without hipEventBlockingSync.  A hand-written
+    //  hipEventQuery loop in its place never saw the event complete on this runtime -- round 3, gpurun_out/r3_t3.log --
+    //  and bought nothing: the wait was never a sleep.)
+    ZG_HIP(hipEventSynchronize(p->evs[wait_ix]));
+    const XYZZ* local = p->pin.results();
+    out.resize(count);
+    if (p->world <= 1 || p->rccl_comm) {  // (whole sums already: a lone prover, or gathered and added on the device)
+        xyzz_batch_normalise(local, count, reinterpret_cast<zg_g1*>(out.data()));
+        return ZG_OK;
+    }
+    ZG_REQUIRE(p->exchange != nullptr, ZG_ERR_INVALID_ARG, "zg_prover: sharded prover without an exchange function");
+    std::vector<XYZZ> all((size_t)p->world * count);
+    const int st = p->exchange(p->exchange_user, local, count * sizeof(XYZZ), all.data());
+    ZG_REQUIRE(st == 0, ZG_ERR_HIP, "zg_prover: the exchange function failed with %d", st);
+    return zg_xyzz_sum_ranks(all.data(), p->world, count, reinterpret_cast<zg_g1*>(out.data()));
+}
+
+}  // namespace
+
+// the per-proof scalars of the batch, as the host holds them now, to the device (behind the work already queued)
+int zg::upload_consts(zg_prover* p, uint32_t nb) { return h2d(p, p->d_pc, p->hpc.data(), (size_t)nb * sizeof(ProofConst)); }
+
+extern "C" {
+
+// create_proof for `nb` circuit instances in lock step: every kernel launch below serves all nb proofs (grid rows /
+// vector groups per proof, scalars from d_pc[b]); the host keeps one transcript per proof and hands each its own
+// challenges.  nb = 1 is the single-proof path (zg_prover_prove / _dev): there is no other.
+// advice_host / advice_dev: per proof, one of them may be given (host columns are uploaded, foreign device columns
+// copied into the proof's slot); both null = the slot already holds the columns (zg_prover_advice_slot).
+// Host-side timeline of a batch (development aid, compiled in with -DZG_TICKS: `make EXTRA=-DZG_TICKS`): every ZG_TICK
+// records a label and the time since the batch began; the list goes to stderr when the batch is done.
+#ifdef ZG_TICKS
+struct TickLog {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    std::vector<std::pair<const char*, double>> v;
+    void tick(const char* l) { v.emplace_back(l, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count()); }
+    ~TickLog() {
+        double prev = 0;
+        for (auto& e : v) {
+            fprintf(stderr, "tick %9.1f us  +%7.1f  %s\n", e.second, e.second - prev, e.first);
+            prev = e.second;
+        }
+    }
+};
+#define ZG_TICK(l) ticks.tick(l)
+#else
+#define ZG_TICK(l) ((void)0)
+#endif
+
+// One lock-step batch of create_proofs (upstream plonk/prover.rs, `create_proof`): the state its phases share, and ONE member
+// function per phase -- round 3 had all of it in a single 510-line function.  A phase queues its kernels
+// on the prover's stream(s), waits for what the transcript needs (commitments as points, evaluations), feeds every proof's
+// EvmTranscript and leaves the next challenges in p->hpc[] / on the device (upload_consts).  Order and contents of the phases
+// are upstream's:
+//   load_inputs        instance + advice columns in place, blinding rows, the vanishing argument's random polynomial
+//   commit_advice      advice commitments                                   -> theta
+//   commit_permuted    lookup::commit_permuted (+ the random polynomial)    -> beta, gamma
+//   commit_products    permutation::commit, lookup::commit_product          -> y
+//   quotient           evaluate_h, h(X) in pieces, their commitments        -> x
+//   evaluations        eval_polynomial at x omega^rot                       -> v
+//   openings           ProverGWC::create_proof
+//   finish             proof bytes and statuses out
+// A nonzero return leaves p->in_flight set: the next batch drains the streams before it reuses the slots.
+struct ProveBatch {
+    using clk = std::chrono::steady_clock;
+    // ---- the call
+    zg_prover* p;
+    const zg_fr* const* advice_host;
+    void* const* advice_dev;
+    const zg_fr* const* instance;
+    size_t instance_len;
+    const uint8_t* keys;
+    uint8_t* const* proofs;
+    size_t proof_cap;
+    size_t* proof_lens;
+    int* statuses;
+    // ---- shapes
+    const PkDev& pk;
+    zg_ctx* ctx;
+    hipStream_t st;
+    uint32_t nb, n, k, ek, bf, usable, A, I, P, NL, S, Q;
+    bool hat;
+    bool split;         // extended-domain parts of this proof: the split pair in the throughput configuration, the single coset otherwise
+    bool phase_cosets;  // the coset forms of a phase's columns: on the side stream while that phase's commitments run (latency
+                        // form), or all at once before evaluate_h (throughput form)
+    uint32_t dlo, dhi;
+    size_t pp_bs, adv_bs, inst_bs, perm_bs, zs_bs, pw_bs, wp_bs;  // strides between consecutive proofs
+    // side stream: coefficient / coset forms of committed columns are computed there while the main stream runs the
+    // commitment MSM (p->use_side == false: everything stays on the main stream -- the throughput configuration, where other
+    // proofs in flight fill the gaps and every extra HIP stream costs a hardware queue)
+    zg_ctx* sx;
+    hipStream_t ss;
+    double parts_en, ext_unit;  // (profile charges: SURVEY.md 8d counts one coeff_to_extended as (n + 2^ext_k) * 32 B whatever parts it is computed on)
+    // ---- state carried from phase to phase
+    PolySet polys;
+    std::vector<EvmTranscript> tr;
+    std::vector<int> status;
+    std::vector<Jac> pts;
+    Fe* random_row = nullptr;  // (proof 0's; proof b's is perm_bs further)
+    Fe* adv = nullptr;
+    Cols base_cols;
+    std::vector<Jac> random_commit;
+    bool have_random = false;
+    struct Q1 { uint32_t poly, slot; };
+    std::vector<int32_t> rots;  // distinct opening points, in any order (the powers table is indexed by slot)
+    std::vector<Q1> evq;
+    size_t e_fixed = 0, e_random = 0, e_sigma = 0, e_pz = 0, e_lk = 0, e_written = 0, e_h = 0;
+    uint32_t npoints = 0;
+    uint32_t* d_hlist = nullptr;
+    const Fe* ev_all = nullptr;
+    uint32_t* h_err = nullptr;  // the lookups' error words on the host
+    uint32_t prod_per = 0;      // commitments per proof of the products phase (the random polynomial rides there without lookups)
+    uint32_t nsets = 0;         // opening point sets: list of set s at lists[s * 512 ..], its evaluation indices in list order
+    std::vector<uint32_t> lists, counts, set_slot;
+    std::vector<std::vector<size_t>> set_evs;
+    // ---- the gate (run())
+    enum Wait { W_ADVICE, W_PERMUTED, W_PRODUCTS, W_QUOTIENT, W_EVALS, W_GWC };
+    bool gated = false, armed = false;
+    bool no_gate = false;       // (the second run of a proof whose gate gave up)
+    bool gate_gave_up = false;  // finish(): a gate kernel ran into its time limit -- the proof was made on stale scalars
+    uint32_t gates_armed = 0;
+    void* gate_slot = nullptr;
+    zg_ctx::GateHold hold;  // what a blocking call inside a queued-ahead phase needs to let the gate go (common.h)
+    clk::time_point t_start, t_prev;
+#ifdef ZG_TICKS
+    TickLog ticks;
+#endif
+
+    ProveBatch(zg_prover* p_, size_t count, const zg_fr* const* advice_host_, void* const* advice_dev_, const zg_fr* const* instance_,
+               size_t instance_len_, const uint8_t* keys_, uint8_t* const* proofs_, size_t proof_cap_, size_t* proof_lens_, int* statuses_)
+        : p(p_), advice_host(advice_host_), advice_dev(advice_dev_), instance(instance_), instance_len(instance_len_), keys(keys_),
+          proofs(proofs_), proof_cap(proof_cap_), proof_lens(proof_lens_), statuses(statuses_), pk(*p_->pk), ctx(p_->ctx),
+          st(p_->ctx->stream), nb((uint32_t)count), tr(count), status(count, ZG_OK) {
+        n = pk.n; k = pk.k; ek = pk.ext_k; bf = pk.bf; usable = pk.usable;
+        A = pk.A; I = pk.I; P = pk.P; NL = pk.NL; S = pk.sets; Q = pk.qpd;
+        hat = pk.hat;
+        split = pk.nparts == 3 && (!p->use_side || p->lat_split);
+        phase_cosets = p->use_side || !split;
+        dlo = split ? 1u : 0u;
+        dhi = split ? 3u : 1u;
+        pp_bs = (size_t)p->npp * n; adv_bs = (size_t)A * n; inst_bs = (size_t)I * n; perm_bs = (size_t)(2 * NL + 1) * n;
+        zs_bs = (size_t)(S + NL + 1) * n; pw_bs = (size_t)p->max_points * n; wp_bs = (size_t)2 * p->max_points * n;
+        polys.sh = pk.sh_polys; polys.pp = p->pp; polys.nsh = p->nsh; polys.n = n; polys.pp_bs = pp_bs;
+        sx = p->use_side ? ctx->side : ctx;
+        ss = sx->stream;
+        parts_en = 0.0;
+        for (uint32_t di = dlo; di < dhi; di++) parts_en += (double)pk.dom[di].en;
+        ext_unit = ((double)n + (double)((size_t)1 << ek)) * 32.0;
+        t_start = t_prev = clk::now();
+    }
+
+    Fe* pp_at(uint32_t ix) const { return p->pp + (size_t)(ix - p->nsh) * n; }  // proof 0's polynomial ix (>= nsh)
+    void lap(int slot) {
+        auto now = clk::now();
+        p->phase_ms[slot] = std::chrono::duration<double, std::milli>(now - t_prev).count();
+        t_prev = now;
+    }
+    int fork() {  // side stream continues after everything queued on the main stream so far
+        if (!p->use_side) return ZG_OK;
+        ZG_HIP(hipEventRecord(p->ev_fork, st));
+        ZG_HIP(hipStreamWaitEvent(ss, p->ev_fork, 0));
+        return ZG_OK;
+    }
+    int join() {  // main stream continues after everything queued on the side stream so far
+        if (!p->use_side) return ZG_OK;
+        ZG_HIP(hipEventRecord(p->ev_join, ss));
+        ZG_HIP(hipStreamWaitEvent(st, p->ev_join, 0));
+        return ZG_OK;
+    }
+    // the commitments of a phase: `per` scalar vectors per proof (`stride` apart, proof b's `outer` after proof b-1's), all
+    // against `bases` in their plain form unless the caller says otherwise
+    MsmJob phase_msm(const zg_bases* bases, const Fe* scalars, size_t stride, size_t per, size_t outer) const {
+        MsmJob m;
+        m.bases = bases; m.split = per;
+        m.scalars = scalars; m.stride = stride; m.per = per; m.outer = outer;
+        m.batch = (size_t)nb * per;
+        return m;
+    }
+    // two-level layouts of the transforms: `per` arrays per proof
+    static Grouping grouping(uint32_t per, size_t in_outer, size_t out_outer) {
+        Grouping g;
+        g.per = per; g.in_outer = in_outer; g.out_outer = out_outer;
+        return g;
+    }
+    // coefficient forms (ix0 .. ix0 + per) of every proof -> their slabs on each part of the extended domain
+    int to_cosets(zg_ctx* c, uint32_t ix0, uint32_t per) {
+        for (uint32_t di = dlo; di < dhi; di++) {
+            const PkDev::Dom& d = pk.dom[di];
+            const Grouping g = grouping(per, pp_bs, (size_t)p->ncos * d.en);
+            c->unit_next = (double)nb * per * ext_unit * ((double)d.en / parts_en);
+            ZG_TRY(coeff_to_coset_dev(c, pp_at(ix0), n, n, p->dbuf[di].cos + (size_t)(ix0 - p->ix_adv) * d.en, d.en, (size_t)nb * per,
+                                      d.ek, hat, d.zpow, &g));
+        }
+        return ZG_OK;
+    }
+
+    // The phases of create_proof, each in two halves: X_queue() puts the phase's device work on the streams (it needs only
+    // the circuit and what the device already holds -- every challenge reaches the kernels through d_pc), X_absorb() waits
+    // for the phase's results, writes them into the transcripts and PUBLISHES the next challenge (publish(): hpc -> d_pc).
+    //
+    // Plain order: queue, absorb, queue, absorb ...  A lone proof with the gate (ZG_LAT_GATE) queues the NEXT phase before
+    // it absorbs this one: arm() reserves a staging slot and puts gate_pull_kernel on the stream (it waits for the gate
+    // word, then copies the slot to d_pc), the next phase's launches follow behind it, and publish() fills the slot and
+    // opens the gate -- between the host having a challenge and the device using it stands one store, not a launch
+    // sequence.  What follows the grand products' totals is never queued ahead: it starts with the HOST inverting them.
+    int run() {
+        const int st_run = run_phases();
+        p->gate_stats[0] += gated ? 1 : 0;
+        p->gate_stats[1] += gates_armed;
+        p->gate_stats[3] += hold.yields;
+        // An error that surfaced BEHIND a failed gate (a time limit, a yield) is the stale scalars' doing, not the caller's:
+        // drain what was queued and let prove_batch_impl make the proof again in the plain order.
+        if (st_run != ZG_OK && !gate_gave_up && gate_failed()) {
+            open_gate();
+            (void)prover_drain(p);
+            p->in_flight = false;
+            gate_gave_up = true;
+        }
+        if (gate_gave_up) p->gate_stats[2]++;
+        if (st_run != ZG_OK) p->warm_sig = 0;  // (whatever way a proof failed: the next one is a first proof)
+        return st_run;
+    }
+    int run_phases() {
+        begin();
+        ZG_TRY(load_inputs());
+        gated = gate_wanted();
+        ZG_TRY(advice_queue());
+        if (!gated) {
+            ZG_TRY(advice_absorb());
+            ZG_TRY(permuted_queue());
+            ZG_TRY(permuted_absorb());
+            ZG_TRY(products_terms_queue());
+            ZG_TRY(products_queue());
+            ZG_TRY(products_absorb());
+            ZG_TRY(evaluation_lists());
+            ZG_TRY(quotient_queue());
+            ZG_TRY(quotient_absorb());
+            ZG_TRY(evaluations_queue());
+            ZG_TRY(openings_lists());
+            ZG_TRY(evaluations_absorb());
+            ZG_TRY(openings_queue());
+        } else {
+            ZG_TRY(arm());
+            ZG_TRY(permuted_queue());    // behind theta
+            ZG_TRY(advice_absorb());
+            ZG_TRY(arm());
+            ZG_TRY(products_terms_queue());  // behind beta, gamma
+            ZG_TRY(permuted_absorb());
+            ZG_TRY(products_queue());  // (starts with the host's share of the grand products: never queued ahead)
+            ZG_TRY(evaluation_lists());
+            ZG_TRY(arm());
+            ZG_TRY(quotient_queue());    // behind y
+            ZG_TRY(products_absorb());
+            ZG_TRY(arm());
+            ZG_TRY(evaluations_queue());  // behind x
+            ZG_TRY(quotient_absorb());
+            ZG_TRY(openings_lists());
+            ZG_TRY(arm());
+            ZG_TRY(openings_queue());    // behind v
+            ZG_TRY(evaluations_absorb());
+        }
+        ZG_TRY(openings_absorb());
+        return finish();
+    }
+
+    // ---- the gate
+    uint64_t form_sig() const {
+        // (everything that shapes the proof's allocation requests and launch sequence: a proof whose signature differs from
+        //  the last completed one's is a FIRST proof -- it may create tables and workspace, with synchronisations -- and is
+        //  never gated: scheduling form, domain split, digit tables, batch, instance length, and the tuning generation,
+        //  which every zg_tuning_set bumps)
+        return 1u | (uint64_t)p->use_side << 1 | (uint64_t)split << 2 | (uint64_t)(p->g->full_table.load() != nullptr) << 3 |
+               (uint64_t)(p->gl->full_table.load() != nullptr) << 4 | (uint64_t)ctx->msm_pair << 5 | (uint64_t)(nb & 0xFFu) << 8 |
+               (uint64_t)(instance_len & 0xFFFFu) << 16 | (uint64_t)tuning_generation() << 32;
+    }
+    bool gate_wanted() {
+        const int v = knob(K_LAT_GATE);
+        if (no_gate || (v < 0 ? LAT_GATE_DEFAULT : v) == 0 || !p->use_side || nb != 1 || p->world > 1 || p->rccl_comm) return false;
+        if (p->warm_sig != form_sig()) return false;  // (first-use allocations and their synchronisations are behind us)
+        // (a runtime that completes every launch before it submits the next one would never reach publish())
+        const bool serialising = runtime_serialises_launches();
+        // room in the staging arena for the five gated uploads and the index lists behind them
+        const size_t need = 5 * ((size_t)nb * sizeof(ProofConst) + 64) + (256u << 10);
+        if (serialising || sizeof(ProofConst) % 16 != 0 || !p->pin.stage_has(need)) return false;
+        *p->pin.gave_up_word() = 0;  // (no gate kernel is in flight between proofs)
+        return true;
+    }
+    int arm() {
+        const size_t bytes = (size_t)nb * sizeof(ProofConst);
+        // (gate_wanted() checked the arena's room: a phase queued ahead WITHOUT its gate would run on the previous challenge)
+        gate_slot = gated && !armed ? p->pin.stage_take(bytes) : nullptr;
+        ZG_REQUIRE(gate_slot != nullptr, ZG_ERR_INVALID_ARG, "zg_prover_prove: no room to arm the gate");
+        if (++p->gate_seq == 0) ++p->gate_seq;
+        armed = true;  // (from here on somebody has to open it: ~ProveBatch)
+        hold.word = p->pin.gate_word();
+        hold.seq = p->gate_seq;
+        ctx->gate_hold = &hold;  // (... or gate_yield(), from a blocking call of the phase queued behind it)
+        if (ctx->side) ctx->side->gate_hold = &hold;
+        const uint4* dev_view = p->pin.dev_view(reinterpret_cast<const uint4*>(gate_slot));
+        // (ZG_LAT_GATE=2, for the tests: the proof's first gate is never opened by publish() and gives up after 0.2 s)
+        const bool lost = knob(K_LAT_GATE) == 2 && gates_armed == 0;
+        gates_armed++;
+        ZG_LAUNCH(ctx, "gate_pull", (double)bytes * 2, gate_pull_kernel, dim3(1), dim3(256), 0, p->pin.dev_view(p->pin.gate_word()),
+                  lost ? p->gate_seq ^ 0x80000000u : p->gate_seq, p->pin.dev_view(p->pin.gave_up_word()), lost ? GATE_MAX_TICKS / 20 : GATE_MAX_TICKS, dev_view, (uint4*)p->d_pc, (uint32_t)(bytes / 16));
+        ZG_HIP(hipGetLastError());
+        return ZG_OK;
+    }
+    void open_gate() {
+        if (!armed) return;
+        __atomic_store_n(p->pin.gate_word(), p->gate_seq, __ATOMIC_SEQ_CST);
+        armed = false;
+        hold.word = nullptr;
+    }
+    // a gate kernel ran into its time limit, or a blocking call let one go early: phases ran on the previous challenge
+    bool gate_failed() const { return gated && (*p->pin.gave_up_word() != 0 || hold.yielded); }
+    // the per-proof scalars as the host holds them now -> d_pc: through the armed gate, else behind the work already queued
+    int publish() {
+        if (!armed) return upload_consts(p, nb);
+        memcpy(gate_slot, p->hpc.data(), (size_t)nb * sizeof(ProofConst));
+        open_gate();  // (a gate that gate_yield() already opened copied the previous scalars: gate_failed(), the proof is re-made)
+        return ZG_OK;
+    }
+    // (an error return between arm() and publish(): the queue must drain whatever it then computes)
+    ~ProveBatch() {
+        open_gate();
+        if (ctx->gate_hold == &hold) ctx->gate_hold = nullptr;
+        if (ctx->side && ctx->side->gate_hold == &hold) ctx->side->gate_hold = nullptr;
+    }
+
+    void begin() {
+        p->have_last = false;
+        // (the previous batch left through an error return: drain what it queued before its staging arena and slots are reused)
+        if (p->in_flight) (void)prover_drain(p);
+        p->in_flight = true;
+        p->pin.stage_reset();
+    }
+
+    int load_inputs() {
+        ZG_TRY(advice_into_slots(p, nb, advice_host, advice_dev));
+
+        // ---- vk + instance values into the transcripts; instance polynomials
+        for (uint32_t b = 0; b < nb; b++) {
+            memset(&p->hpc[b], 0, sizeof(ProofConst));
+            memcpy(p->hpc[b].key, keys + 32 * (size_t)b, 32);
+            tr[b].common_scalar(pk.vk_repr);
+        }
+        ZG_TRY(upload_consts(p, nb));
+        // vanishing::Argument::commit's random polynomial depends on no challenge: generate it now and
+        // commit it inside the permuted-lookup batch (coefficient basis `g` next to `g_lagrange` vectors)
+        random_row = p->perm + (size_t)(2 * NL) * n;  // (proof 0's; proof b's is perm_bs further)
+        // (the same launch draws the blinding rows of the advice columns: commit_lagrange's input below)
+        adv = p->adv_val;
+        ZG_TRY(poly_random_and_blind(ctx, p->d_pc, nb, random_row, perm_bs, pp_at(p->ix_random), pp_bs, n, TAG_RANDOM_POLY, adv, adv_bs,
+                                     n, A, usable, bf + 1, TAG_ADVICE_BLIND));
+        if (I) {
+            for (uint32_t b = 0; b < nb; b++) {
+                Fe* iv = p->inst_val + b * inst_bs;
+                if (p->inst_filled[b] > instance_len) ZG_HIP(hipMemsetAsync(iv, 0, inst_bs * 32, st));  // (zeroed at create)
+                p->inst_filled[b] = instance_len;
+                for (uint32_t c = 0; c < I; c++) {
+                    const zg_fr* src = instance_len ? instance[b] + (size_t)c * instance_len : nullptr;
+                    for (size_t i = 0; i < instance_len; i++) tr[b].common_scalar(to_fe(&src[i]));
+                    if (instance_len) ZG_TRY(h2d(p, iv + (size_t)c * n, src, instance_len * 32));
+                }
+            }
+        }
+        base_cols.fixed = pk.fixed_val; base_cols.advice = adv; base_cols.instance = p->inst_val;
+        base_cols.log_size = k; base_cols.rot_scale = 1;
+        base_cols.adv_bs = adv_bs; base_cols.inst_bs = inst_bs;
+        return ZG_OK;
+    }
+
+    int advice_queue() {
+        // ---- advice: commit (Lagrange basis)
+        ZG_TRY(fork());
+        if (I) {
+            const Grouping g = grouping(I, inst_bs, pp_bs);
+            ZG_TRY(ntt_batch_to_dev(sx, p->inst_val, pp_at(p->ix_inst), n, (size_t)nb * I, k, pk.omega_inv, &pk.ifft_div, &g));
+            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_inst, I));
+        }
+        if (A) {
+            ZG_TRY(commit(p, phase_msm(p->gl, adv, n, A, adv_bs), W_ADVICE));
+            const Grouping g = grouping(A, adv_bs, pp_bs);
+            ZG_TRY(ntt_batch_to_dev(sx, adv, pp_at(p->ix_adv), n, (size_t)nb * A, k, pk.omega_inv, &pk.ifft_div, &g));
+            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_adv, A));
+        }
+        ZG_TICK("advice: queued");
+        return ZG_OK;
+    }
+    int advice_absorb() {
+        if (A) {
+            ZG_TRY(wait_points(p, (size_t)nb * A, pts, W_ADVICE));
+            ZG_TICK("advice: points on the host");
+            for (uint32_t b = 0; b < nb; b++)
+                for (uint32_t c = 0; c < A; c++) tr[b].write_point(pts[(size_t)b * A + c]);
+        }
+        for (uint32_t b = 0; b < nb; b++) p->hpc[b].theta = tr[b].squeeze();
+        ZG_TICK("theta");
+        ZG_TRY(publish());
+        ZG_TICK("theta uploaded");
+        lap(0);
+        return ZG_OK;
+    }
+
+    int permuted_queue() {
+        // ---- lookups: commit_permuted (+ the random polynomial's commitment)
+        if (NL) {
+            // permute_expression_pair on the device: canonical keys (written by the compression kernel itself, with
+            // the sentinel padding), bitonic sort of inputs and tables, scan-based construction of s' (sort.hip).
+            // raw rows [0, m) = inputs -> a', [m, 2m) = tables, m = nb * NL, row b * NL + l = lookup l of proof b.
+            const uint32_t m = nb * NL;
+            Fe *raw_in = p->raw, *raw_tab = p->raw + (size_t)m * n;
+            uint32_t* d_err = p->sort_u32 + (size_t)2 * m * n + 2 * m;  // behind permute_pairs' scratch: zeroed by the same fill
+            ZG_TRY(poly_lookup_compress(ctx, pk.dc, base_cols, p->d_pc, nb, p->cin, p->ctab, n, raw_in, raw_tab, usable));
+            auto t_sort = clk::now();
+            ZG_TRY(poly_sort_keys(ctx, p->raw, n, 2 * m));
+            ZG_TRY(poly_permute_pairs(ctx, raw_in, raw_tab, p->sraw, n, usable, m, p->sort_u32, p->sort_fe, d_err));
+            // perm[2l] = a'_l, perm[2l+1] = s'_l (Montgomery form) on the usable rows, then the blinding tail
+            // (blinding: a' rows get tag 2, s' rows tag 3, index = lookup * (bf+1) + j)
+            ZG_TRY(poly_permuted_finish(ctx, p->d_pc, nb, raw_in, p->sraw, p->perm, perm_bs, n, usable, bf + 1, NL, TAG_PERMUTED_INPUT,
+                                        TAG_PERMUTED_TABLE));
+            p->phase_ms[7] = std::chrono::duration<double, std::milli>(clk::now() - t_sort).count();
+            ZG_TRY(fork());
+            // the lookups' error words leave on the side stream, beside the commitments (an event of their own)
+            h_err = p->pin.lookup_errors();
+            ZG_HIP(hipMemcpyAsync(h_err, d_err, m * sizeof(uint32_t), hipMemcpyDeviceToHost, ss));
+            ZG_HIP(hipEventRecord(p->ev_err, ss));
+            // (a' and s' are sorted: equal neighbours everywhere, so the run form leaves one entry per distinct value)
+            const zg_bases *cgl = naf_of(p, p->gl), *cg = cgl == p->gl ? p->g : naf_of(p, p->g);  // (both or neither)
+            const uint64_t sorted_runs = cgl->run_table && 2 * NL < 64 ? (1ull << (2 * NL)) - 1ull : 0ull;
+            MsmJob msm = phase_msm(cgl, p->perm, n, 2 * NL + 1, perm_bs);
+            msm.bases_b = cg; msm.split = 2 * NL;  // (the random polynomial, last of each group, against g)
+            msm.run_mask = sorted_runs; msm.naf_width = p->naf_gl_w;
+            ZG_TRY(commit(p, msm, W_PERMUTED));
+            {
+                const Grouping g = grouping(2 * NL, perm_bs, pp_bs);
+                ZG_TRY(ntt_batch_to_dev(sx, p->perm, pp_at(p->ix_perm), n, (size_t)nb * 2 * NL, k, pk.omega_inv, &pk.ifft_div, &g));
+            }
+            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_perm, 2 * NL));
+        }
+        ZG_TICK("permuted: queued");
+        return ZG_OK;
+    }
+    int permuted_absorb() {
+        random_commit.resize(nb);
+        have_random = false;
+        if (NL) {
+            ZG_TRY(wait_points(p, (size_t)nb * (2 * NL + 1), pts, W_PERMUTED));
+            ZG_HIP(hipEventSynchronize(p->ev_err));
+            ZG_TICK("permuted: points on the host");
+            for (uint32_t b = 0; b < nb; b++) {
+                for (uint32_t l = 0; l < NL; l++)
+                    if (h_err[b * NL + l] && status[b] == ZG_OK) {
+                        set_error("zg_prover_prove: lookup %u of proof %u has an input outside its table (ConstraintSystemFailure)", l, b);
+                        status[b] = ZG_ERR_CONSTRAINT;
+                    }
+                const Jac* q = &pts[(size_t)b * (2 * NL + 1)];
+                for (uint32_t i = 0; i < 2 * NL; i++) tr[b].write_point(q[i]);
+                random_commit[b] = q[2 * NL];
+            }
+            have_random = true;
+            if (nb == 1 && status[0] != ZG_OK && gate_failed()) return ZG_ERR_HIP;  // (error words from behind a failed gate: run() re-makes the proof)
+            if (nb == 1 && status[0] != ZG_OK) {  // a lone proof stops here, as upstream's `?` does
+                open_gate();  // (whatever was queued ahead runs out on stale scalars: nobody reads its results)
+                (void)prover_drain(p);
+                if (statuses) statuses[0] = status[0];
+                proof_lens[0] = 0;
+                p->in_flight = false;
+                return status[0];
+            }
+        }
+        for (uint32_t b = 0; b < nb; b++) {
+            p->hpc[b].beta = tr[b].squeeze();
+            p->hpc[b].gamma = tr[b].squeeze();
+        }
+        ZG_TICK("beta, gamma");
+        ZG_TRY(publish());
+        ZG_TICK("beta, gamma uploaded");
+        lap(1);
+        return ZG_OK;
+    }
+
+    // ---- permutation products (sets chained through z[n - bf - 1]) and lookup products
+    // (in two parts: the terms and the running products up to their totals need beta and gamma only; what follows the
+    //  totals begins, in the latency form, with the HOST inverting them -- it cannot be queued ahead of anything)
+    int products_terms_queue() {
+        const uint32_t mb = S + NL;
+        if (S) ZG_TRY(poly_perm_terms(ctx, pk.dc, base_cols, p->d_pc, nb, pk.sigma_val, pk.omega_tw, p->num, p->den, mb, n));
+        // (a'_l / s'_l are interleaved in `perm`: two views with a stride of two columns)
+        ZG_TRY(poly_lookup_terms(ctx, p->d_pc, nb, p->cin, p->ctab, p->perm, p->perm + n, (size_t)2 * n, perm_bs, p->num, p->den, mb, S, n, NL));
+        // all running products of the batch in one scan sequence; per proof the S permutation sets are chained
+        // through row n - bf - 1, the lookup products start from one
+        if (mb) ZG_TRY(poly_grand_product(ctx, p->num, p->den, nullptr, p->zs, p->tmp, n, nb * mb, S, n - bf - 1, mb, zs_bs, 1));
+        ZG_TICK("product terms: queued");
+        return ZG_OK;
+    }
+    int products_queue() {
+        const uint32_t mb = S + NL;
+        if (mb) {
+            ZG_TRY(poly_grand_product(ctx, p->num, p->den, nullptr, p->zs, p->tmp, n, nb * mb, S, n - bf - 1, mb, zs_bs, 2));
+            ZG_TRY(poly_blind_rows2(ctx, p->d_pc, nb, p->zs, zs_bs, n, S, TAG_PERM_Z, NL, TAG_LOOKUP_Z, n - bf, bf));  // (lz follows pz)
+            // The products stay constant wherever a row changes nothing (every padding row of the circuit): they are
+            // committed in the run form, sum_i (z_i - z_{i+1}) Q_i over the running sums Q of g_lagrange.
+            const zg_bases *cgl = naf_of(p, p->gl), *cg = cgl == p->gl ? p->g : naf_of(p, p->g);
+            const uint64_t z_runs = cgl->run_table && mb < 64 ? (1ull << mb) - 1ull : 0ull;
+            ZG_TRY(fork());
+            prod_per = mb;
+            if (!have_random) {  // no lookups: the random polynomial rides here instead (row mb of zs)
+                for (uint32_t b = 0; b < nb; b++)
+                    ZG_HIP(hipMemcpyAsync(p->zs + b * zs_bs + (size_t)mb * n, random_row + b * perm_bs, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
+                prod_per = mb + 1;
+            }
+            MsmJob msm = phase_msm(cgl, p->zs, n, prod_per, zs_bs);
+            if (!have_random) msm.bases_b = cg, msm.split = mb;
+            msm.run_mask = z_runs; msm.naf_width = p->naf_gl_w;
+            ZG_TRY(commit(p, msm, W_PRODUCTS));
+            {
+                const Grouping g = grouping(mb, zs_bs, pp_bs);
+                ZG_TRY(ntt_batch_to_dev(sx, p->zs, pp_at(p->ix_pz), n, (size_t)nb * mb, k, pk.omega_inv, &pk.ifft_div, &g));
+            }
+            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_pz, mb));
+        } else if (!have_random) {  // neither lookups nor permutation: commit the random polynomial on its own
+            ZG_TRY(commit(p, phase_msm(p->g, random_row, n, 1, perm_bs), W_PRODUCTS));
+        }
+        ZG_TICK("products: queued");
+        return ZG_OK;
+    }
+    int products_absorb() {
+        const uint32_t mb = S + NL;
+        if (mb) {
+            ZG_TRY(wait_points(p, (size_t)nb * prod_per, pts, W_PRODUCTS));
+            ZG_TICK("products: points on the host");
+            for (uint32_t b = 0; b < nb; b++) {
+                const Jac* q = &pts[(size_t)b * prod_per];
+                for (uint32_t i = 0; i < mb; i++) tr[b].write_point(q[i]);
+                if (!have_random) random_commit[b] = q[mb];
+            }
+        } else if (!have_random) {
+            ZG_TRY(wait_points(p, nb, pts, W_PRODUCTS));
+            for (uint32_t b = 0; b < nb; b++) random_commit[b] = pts[b];
+        }
+        have_random = true;
+        for (uint32_t b = 0; b < nb; b++) tr[b].write_point(random_commit[b]);
+        for (uint32_t b = 0; b < nb; b++) evalh_consts(p->hpc[b], tr[b].squeeze(), hat, evalh_terms(pk));
+        ZG_TICK("y");
+        ZG_TRY(publish());
+        ZG_TICK("y uploaded");
+        lap(2);
+        return ZG_OK;
+    }
+
+    int quotient_queue() {
+        ZG_TRY(join());  // evaluate_h reads every coset the side stream produced
+        // (throughput configuration: nothing overlaps, so every witness polynomial goes to its cosets here, in one batch per
+        //  coset, instead of phase by phase)
+        if (!phase_cosets) ZG_TRY(to_cosets(ctx, p->ix_adv, p->ncos));
+        // ---- evaluate_h (+ division by X^n - 1) on every part of the extended domain, back to coefficients, h pieces
+        for (uint32_t di = dlo; di < dhi; di++) {
+            const EvalHArgs a = evalh_args(p, di);
+            ZG_TRY(poly_evaluate_h(ctx, a, pk.dom[di].en, nb, A + I + pk.F, (double)((size_t)1 << ek) * ((double)pk.dom[di].en / parts_en)));
+        }
+        p->have_last = true;
+        p->last_split = split;
+        p->last_nb = nb;
+        const double ext_inv_unit = (double)nb * 2.0 * (double)((size_t)1 << ek) * 32.0;  // (ext -> coeff, 2 * 8n * 32 B)
+        if (!split) {
+            ctx->unit_next = ext_inv_unit;
+            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[0].h, ek, (size_t)Q * n, pp_at(p->ix_hpiece), hat, 1, nb, pk.dom[0].en, pp_bs));
+        } else {
+            // h = A + (X^L1 - c1) B:  A (degree < L1) from the first coset, where X^L1 = c1 = shift1^L1;  B (degree < L2)
+            // from the second, where X^L1 = c2 and X^L2 = e are constants too:  B = (h - A) / (c2 - c1) there, with A
+            // folded modulo X^L2 - e before it is evaluated on those L2 points.
+            const PkDev::Dom &d1 = pk.dom[1], &d2 = pk.dom[2];
+            const uint32_t L1 = d1.en, L2 = d2.en;
+            const Fe zeta = fr_zeta(), zeta2 = Fr::sqr(zeta);
+            const Fe c1 = Fr::pow_u64(zeta, L1), c2 = Fr::pow_u64(zeta2, L1), e = Fr::pow_u64(zeta2, L2);
+            Fe* hp = pp_at(p->ix_hpiece);
+            const size_t tb = (size_t)3 * L2;
+            Fe *fold = p->split_tmp, *a2 = fold + L2, *bc = a2 + L2;
+            ctx->unit_next = ext_inv_unit;  // (the three transforms of the split form stand for ONE extended_to_coeff)
+            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[1].h, d1.ek, L1, hp, hat, 1, nb, L1, pp_bs));  // A, in place of the low pieces
+            ZG_TRY(poly_fold(ctx, nb, hp, pp_bs, L2, L1 / L2, e, fold, tb));                       // A mod (X^L2 - e)
+            ctx->unit_next = 0.0;
+            ZG_TRY(coeff_to_coset_dev(ctx, fold, tb, L2, a2, tb, nb, d2.ek, false, 2));            // A on the second coset
+            const Fe unhat = hat ? Fr::inv(Fr::from_u64(32)) : Fr::one();
+            ZG_TRY(poly_diff_scale(ctx, nb, p->dbuf[2].h, L2, unhat, a2, tb, Fr::inv(Fr::sub(c2, c1)), a2, tb, L2));  // B on the second coset
+            ctx->unit_next = 0.0;
+            ZG_TRY(coset_to_coeff_dev(ctx, a2, d2.ek, L2, bc, false, 2, nb, tb, tb));              // B
+            ZG_TRY(poly_split_combine(ctx, nb, hp, pp_bs, bc, tb, L2, c1, L1));                    // h = A - c1 B + X^L1 B
+        }
+        ctx->msm_dense_hint = true;  // (the quotient pieces are random vectors: every digit of every window is an addition)
+        const int st_h = commit(p, phase_msm(dense_g(p), pp_at(p->ix_hpiece), n, Q, pp_bs), W_QUOTIENT);
+        ctx->msm_dense_hint = false;
+        ZG_TRY(st_h);
+        ZG_TICK("h: queued");
+        return ZG_OK;
+    }
+    // (h's commitments, then x and the opening points: needs evaluation_lists())
+    int quotient_absorb() {
+        ZG_TRY(wait_points(p, (size_t)nb * Q, pts, W_QUOTIENT));
+        ZG_TICK("h: points on the host");
+        for (uint32_t b = 0; b < nb; b++)
+            for (uint32_t i = 0; i < Q; i++) tr[b].write_point(pts[(size_t)b * Q + i]);
+        for (uint32_t b = 0; b < nb; b++) {
+            ProofConst& c = p->hpc[b];
+            const Fe x = tr[b].squeeze();
+            c.xn = Fr::pow_u64(x, n);
+            for (uint32_t i = 0; i < npoints; i++) c.points[i] = rotate_omega(pk, x, rots[i]);
+        }
+        ZG_TICK("x");
+        ZG_TRY(publish());
+        ZG_TICK("x uploaded");
+        lap(3);
+        return ZG_OK;
+    }
+
+    // ---- evaluations: which polynomial is evaluated at which opening point (circuit only)
+    int evaluation_lists() {
+        // distinct opening points, in any order (the powers table is indexed by slot)
+        rots = {0, 1, -1, -(int32_t)(bf + 1)};
+        auto rot_slot = [&](int32_t r) -> uint32_t {
+            for (size_t i = 0; i < rots.size(); i++)
+                if (rots[i] == r) return (uint32_t)i;
+            rots.push_back(r);
+            return (uint32_t)rots.size() - 1;
+        };
+        evq.clear();  // evaluations in transcript order, then h_poly at x
+        for (auto& q : pk.advice_queries) evq.push_back({p->ix_adv + q.column, rot_slot(q.rotation)});
+        e_fixed = evq.size();
+        for (auto& q : pk.fixed_queries) evq.push_back({p->ix_fixed + q.column, rot_slot(q.rotation)});
+        e_random = evq.size();
+        evq.push_back({p->ix_random, 0});
+        e_sigma = evq.size();
+        for (uint32_t c = 0; c < P; c++) evq.push_back({p->ix_sigma + c, 0});
+        e_pz = evq.size();
+        for (uint32_t s = 0; s < S; s++) {
+            evq.push_back({p->ix_pz + s, 0});
+            evq.push_back({p->ix_pz + s, 1});
+            if (s + 1 < S) evq.push_back({p->ix_pz + s, 3});
+        }
+        e_lk = evq.size();
+        for (uint32_t l = 0; l < NL; l++) {
+            evq.push_back({p->ix_lz + l, 0});            // z(x)
+            evq.push_back({p->ix_lz + l, 1});            // z(omega x)
+            evq.push_back({p->ix_perm + 2 * l, 0});      // a'(x)
+            evq.push_back({p->ix_perm + 2 * l, 2});      // a'(omega^-1 x)
+            evq.push_back({p->ix_perm + 2 * l + 1, 0});  // s'(x)
+        }
+        e_written = evq.size();
+        evq.push_back({p->ix_hpoly, 0});
+        e_h = e_written;
+        npoints = (uint32_t)rots.size();
+        ZG_REQUIRE(npoints <= p->max_points, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u distinct rotations are queried (max %u)", npoints,
+                   p->max_points);
+        ZG_REQUIRE(evq.size() <= p->max_evals, ZG_ERR_UNSUPPORTED, "zg_prover_prove: too many evaluations");
+
+        return ZG_OK;
+    }
+    int evaluations_queue() {
+        // vanishing.evaluate: h(X) = sum_i xn^i h_i(X)
+        d_hlist = p->d_idx + (size_t)4 * p->max_evals;
+        {
+            std::vector<uint32_t> list(Q);
+            for (uint32_t i = 0; i < Q; i++) list[i] = p->ix_hpiece + (Q - 1 - i);
+            ZG_TRY(h2d_list(p, d_hlist, list));
+            ZG_TRY(poly_horner_combine_xn(ctx, polys, p->d_pc, nb, d_hlist, Q, pp_at(p->ix_hpoly), pp_bs, n));
+        }
+        ZG_TRY(poly_powers(ctx, p->d_pc, nb, npoints, n, p->pw, pw_bs));
+        std::vector<uint32_t> idx(2 * evq.size());
+        for (size_t i = 0; i < evq.size(); i++) {
+            idx[i] = evq[i].poly;
+            idx[evq.size() + i] = evq[i].slot;
+        }
+        ZG_TRY(h2d_list(p, p->d_idx, idx));
+        // (the evaluations too are written where the host reads them: no copy command behind the kernel)
+        uint32_t distinct_polys = 0;
+        {
+            std::vector<uint32_t> seen(idx.begin(), idx.begin() + evq.size());
+            std::sort(seen.begin(), seen.end());
+            distinct_polys = (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+        }
+        ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + evq.size(), p->pw, pw_bs, (uint32_t)evq.size(),
+                        p->pin.dev_view(p->pin.evals()), p->max_evals, distinct_polys, npoints));
+        ev_all = p->pin.evals();
+        ZG_HIP(hipEventRecord(p->evs[W_EVALS], st));
+        ZG_TICK("evals: queued");
+        return ZG_OK;
+    }
+    // (the evaluations into the transcripts, then v and each point set's v-weighted evaluation: needs openings_lists())
+    int evaluations_absorb() {
+        ZG_HIP(hipEventSynchronize(p->evs[W_EVALS]));
+        ZG_TICK("evals on the host");
+        for (uint32_t b = 0; b < nb; b++) {
+            const Fe* ev = ev_all + (size_t)b * p->max_evals;
+            for (size_t i = 0; i < e_written; i++) tr[b].write_scalar(ev[i]);
+            ProofConst& c = p->hpc[b];
+            c.v = tr[b].squeeze();
+            for (uint32_t s = 0; s < nsets; s++) {
+                Fe eval_batch = fe_zero();
+                for (size_t e : set_evs[s]) eval_batch = Fr::add(Fr::mul(eval_batch, c.v), ev[e]);
+                c.subs[s] = eval_batch;
+            }
+        }
+        ZG_TICK("v");
+        ZG_TRY(publish());
+        ZG_TICK("v uploaded");
+        lap(4);
+        return ZG_OK;
+    }
+
+    int openings_lists() {
+        // ---- opening queries in create_proof's order: (poly, point slot, index of the evaluation)
+        struct OQ { uint32_t poly, slot; size_t ev; };
+        std::vector<OQ> oq;
+        for (size_t i = 0; i < e_fixed; i++) oq.push_back({evq[i].poly, evq[i].slot, i});
+        {
+            size_t e = e_pz;
+            std::vector<size_t> e_last(S, 0), e_cur(S, 0), e_next(S, 0);
+            for (uint32_t s = 0; s < S; s++) {
+                e_cur[s] = e++;
+                e_next[s] = e++;
+                if (s + 1 < S) e_last[s] = e++;
+            }
+            for (uint32_t s = 0; s < S; s++) {
+                oq.push_back({p->ix_pz + s, 0, e_cur[s]});
+                oq.push_back({p->ix_pz + s, 1, e_next[s]});
+            }
+            for (uint32_t s = S; s-- > 0;) {
+                if (s + 1 == S) continue;
+                oq.push_back({p->ix_pz + s, 3, e_last[s]});
+            }
+        }
+        for (uint32_t l = 0; l < NL; l++) {
+            const size_t e5 = e_lk + 5 * l;
+            oq.push_back({p->ix_lz + l, 0, e5 + 0});
+            oq.push_back({p->ix_perm + 2 * l, 0, e5 + 2});
+            oq.push_back({p->ix_perm + 2 * l + 1, 0, e5 + 4});
+            oq.push_back({p->ix_perm + 2 * l, 2, e5 + 3});
+            oq.push_back({p->ix_lz + l, 1, e5 + 1});
+        }
+        for (size_t i = e_fixed; i < e_random; i++) oq.push_back({evq[i].poly, evq[i].slot, i});
+        for (uint32_t c = 0; c < P; c++) oq.push_back({p->ix_sigma + c, 0, e_sigma + c});
+        oq.push_back({p->ix_hpoly, 0, e_h});
+        oq.push_back({p->ix_random, 0, e_random});
+
+        // ---- ProverGWC::create_proof: the point sets (circuit only), then per proof its v-weighted evaluation batches
+        nsets = 0;
+        lists.clear(); counts.clear(); set_slot.clear(); set_evs.clear();
+        {
+            std::vector<char> done(oq.size(), 0);
+            for (size_t first = 0; first < oq.size(); first++) {
+                if (done[first]) continue;
+                const uint32_t slot = oq[first].slot;
+                lists.resize((size_t)(nsets + 1) * 512, 0);
+                set_evs.emplace_back();
+                uint32_t cnt = 0;
+                for (size_t j = first; j < oq.size(); j++) {
+                    if (done[j] || oq[j].slot != slot) continue;
+                    done[j] = 1;
+                    ZG_REQUIRE(cnt < 512, ZG_ERR_UNSUPPORTED, "zg_prover_prove: more than 512 polynomials opened at one point");
+                    lists[(size_t)nsets * 512 + cnt++] = oq[j].poly;
+                    set_evs.back().push_back(oq[j].ev);
+                }
+                counts.push_back(cnt);
+                set_slot.push_back(slot);
+                nsets++;
+            }
+        }
+        ZG_REQUIRE(nsets <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u opening points", nsets);
+        ZG_TICK("opening sets listed");
+        return ZG_OK;
+    }
+    int openings_queue() {
+        // poly_batch of every point set in one launch: set s -> wpoly[2s]
+        // (their own region of d_idx, behind the evaluation lists: nothing else writes there between proofs)
+        uint32_t* d_lists = d_hlist + 64;
+        ZG_TRY(h2d_list(p, d_lists, lists));
+        ZG_TRY(poly_horner_combine_sets(ctx, polys, p->d_pc, nb, d_lists, 512, counts.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, n));
+        // one batched kate_division: poly s at wpoly[2s], quotient at wpoly[2s+1]
+        ZG_TRY(poly_kate_division(ctx, p->d_pc, nb, set_slot.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n,
+                                  wp_bs, p->ktmp, n));
+        // the witness polynomials sit at odd slots: stride 2n
+        ctx->msm_dense_hint = true;  // (so are the opening quotients)
+        const int st_w = commit(p, phase_msm(dense_g(p), p->wpoly + n, (size_t)2 * n, nsets, wp_bs), W_GWC);
+        ctx->msm_dense_hint = false;
+        ZG_TRY(st_w);
+        ZG_TICK("gwc: queued");
+        return ZG_OK;
+    }
+    int openings_absorb() {
+        ZG_TRY(wait_points(p, (size_t)nb * nsets, pts, W_GWC));
+        ZG_TICK("gwc: points on the host");
+        for (uint32_t b = 0; b < nb; b++)
+            for (uint32_t s = 0; s < nsets; s++) tr[b].write_point(pts[(size_t)b * nsets + s]);
+        return ZG_OK;
+    }
+
+    int finish() {
+        int first_bad = ZG_OK;
+        if (gate_failed()) {  // (every gate kernel has ended: the last commitments came from behind them)
+            set_error(hold.yielded ? "zg_prover_prove: a phase queued ahead of its challenge had to allocate or synchronise; its gate was let go (ZG_LAT_GATE)"
+                                   : "zg_prover_prove: a phase waited more than 4 s for its challenge and ran without it (ZG_LAT_GATE)");
+            gate_gave_up = true;  // (nothing is handed out: prove_batch_impl makes the proof again in the plain order)
+            p->in_flight = false;
+            return ZG_ERR_HIP;
+        }
+        for (uint32_t b = 0; b < nb; b++) {
+            if (status[b] == ZG_OK && tr[b].failed) {
+                set_error("zg_prover_prove: a commitment of proof %u is the identity point; EvmTranscript cannot absorb it", b);
+                status[b] = ZG_ERR_INVALID_ARG;
+            }
+            if (status[b] == ZG_OK && tr[b].stream.size() > proof_cap) {
+                set_error("zg_prover_prove: proof buffer too small (%zu > %zu)", tr[b].stream.size(), proof_cap);
+                status[b] = ZG_ERR_INVALID_ARG;
+            }
+            if (status[b] == ZG_OK) {
+                memcpy(proofs[b], tr[b].stream.data(), tr[b].stream.size());
+                proof_lens[b] = tr[b].stream.size();
+            } else {
+                proof_lens[b] = 0;
+                if (first_bad == ZG_OK) first_bad = status[b];
+            }
+            if (statuses) statuses[b] = status[b];
+        }
+        ZG_TICK("proof bytes out");
+        lap(5);
+        p->phase_ms[6] = std::chrono::duration<double, std::milli>(clk::now() - t_start).count();
+        p->in_flight = false;
+        p->warm_sig = first_bad == ZG_OK ? form_sig() : 0;
+        return first_bad;
+    }
+};
+
+static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advice_host, void* const* advice_dev,
+                            const zg_fr* const* instance, size_t instance_len, const uint8_t* keys /* [count][32] */,
+                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, int* statuses) {
+    ZG_REQUIRE(p && proofs && proof_lens && keys, ZG_ERR_INVALID_ARG, "zg_prover_prove: null argument");
+    ZG_TRY(batch_args_ok("zg_prover_prove", "proofs", p, count, instance, instance_len));
+    ZG_REQUIRE(p->world > 1 || p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG,
+               "zg_prover_prove: the base sets hold %u of %u points and no shard was declared (zg_prover_set_shard)", p->shard_n, p->pk->n);
+    ZG_ENTER(p->ctx);
+    {
+        ProveBatch job(p, count, advice_host, advice_dev, instance, instance_len, keys, proofs, proof_cap, proof_lens, statuses);
+        const int st = job.run();
+        if (!job.gate_gave_up) return st;
+    }
+    // A gate ran into its time limit (the host thread was away for seconds, or a stream that shares a hardware queue with
+    // this prover's stood in the way -- LAT_GATE_DEFAULT): the phases behind it ran on the previous challenge.  The inputs
+    // are where they were (the blinding rows are a function of the key): the same proof again, every phase after its challenge.
+    ProveBatch again(p, count, advice_host, advice_dev, instance, instance_len, keys, proofs, proof_cap, proof_lens, statuses);
+    again.no_gate = true;
+    return again.run();
+}
+
+int zg_prover_prove_batch(zg_prover* p, size_t count, const zg_fr* const* advice, const zg_fr* const* instance,
+                          size_t instance_len, const uint8_t* rng_keys, uint8_t* const* proofs, size_t proof_cap,
+                          size_t* proof_lens, int* statuses) {
+    return prove_batch_impl(p, count, advice, nullptr, instance, instance_len, rng_keys, proofs, proof_cap, proof_lens, statuses);
+}
+
+int zg_prover_prove_batch_dev(zg_prover* p, size_t count, void* const* d_advice, const zg_fr* const* instance,
+                              size_t instance_len, const uint8_t* rng_keys, uint8_t* const* proofs, size_t proof_cap,
+                              size_t* proof_lens, int* statuses) {
+    return prove_batch_impl(p, count, nullptr, d_advice, instance, instance_len, rng_keys, proofs, proof_cap, proof_lens, statuses);
+}
+
+int zg_prover_prove_dev(zg_prover* p, void* d_advice, const zg_fr* instance, size_t instance_len, const uint8_t rng_key[32],
+                        uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    ZG_REQUIRE(p && proof && proof_len && rng_key && (d_advice || p->pk->A == 0), ZG_ERR_INVALID_ARG, "zg_prover_prove: null argument");
+    void* adv[1] = {d_advice};
+    const zg_fr* inst[1] = {instance};
+    uint8_t* out[1] = {proof};
+    return prove_batch_impl(p, 1, nullptr, adv, instance ? inst : nullptr, instance_len, rng_key, out, proof_cap, proof_len, nullptr);
+}
+
+int zg_prover_prove(zg_prover* p, const zg_fr* advice, const zg_fr* instance, size_t instance_len, const uint8_t rng_key[32],
+                    uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    ZG_REQUIRE(p && proof && proof_len && rng_key && (advice || p->pk->A == 0), ZG_ERR_INVALID_ARG, "zg_prover_prove: null argument");
+    const zg_fr* adv[1] = {advice};
+    const zg_fr* inst[1] = {instance};
+    uint8_t* out[1] = {proof};
+    return prove_batch_impl(p, 1, adv, nullptr, instance ? inst : nullptr, instance_len, rng_key, out, proof_cap, proof_len, nullptr);
+}
+
+}  // extern "C"

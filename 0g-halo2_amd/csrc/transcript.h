@@ -14,8 +14,6 @@
 
 namespace zg {
 
-void keccak256(const uint8_t* data, size_t len, uint8_t out[32]);
-
 inline void fe_to_be_bytes_fr(const Fe& a, uint8_t out[32]) {
     Fe r = Fr::to_raw(a);
     for (int i = 0; i < 8; i++)

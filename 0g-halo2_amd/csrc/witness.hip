@@ -21,7 +21,7 @@
 // global barrier.  ZG_WITNESS_LDS = 0 keeps every operand in HBM (the round-2 kernel's behaviour, for A/B).
 // `witness_finish`: one lane per advice cell -- the slot its cell shows, reduced below r, into the Montgomery form, or
 // zero for a cell the circuit leaves unassigned -- plus the instance values (class scores) for the host's transcript.
-#include "common.h"
+#include "prover.h"
 #include "field.h"
 
 namespace zg {
@@ -896,18 +896,18 @@ static int images_into_slots(const char* who, zg_prover* p, zg_witness_plan* pla
     }
     // The program writes [n_advice][2^k] columns into the prover's slots: a plan recorded for another model (other k or
     // column count) would overrun them, so its shape must be the prover's circuit's, on the prover's device.
-    const ProverShape sh = prover_shape(p);
+    const PkDev& sh = *p->pk;
     ZG_REQUIRE(plan->ctx->device == sh.device, ZG_ERR_INVALID_ARG, "%s: the plan lives on device %d, the prover on %d", who,
                plan->ctx->device, sh.device);
-    ZG_REQUIRE(plan->k == sh.k && plan->n_advice == sh.n_advice, ZG_ERR_INVALID_ARG,
+    ZG_REQUIRE(plan->k == sh.k && plan->n_advice == sh.A, ZG_ERR_INVALID_ARG,
                "%s: the plan writes %u advice columns of 2^%u rows, the prover's circuit has %u of 2^%u", who, plan->n_advice,
-               plan->k, sh.n_advice, sh.k);
-    ZG_REQUIRE((plan->n_instance == 0 || sh.n_instance == 1) && plan->n_instance <= sh.usable_rows, ZG_ERR_INVALID_ARG,
+               plan->k, sh.A, sh.k);
+    ZG_REQUIRE((plan->n_instance == 0 || sh.I == 1) && plan->n_instance <= sh.usable, ZG_ERR_INVALID_ARG,
                "%s: the plan yields %u instance values for a circuit with %u instance column(s) of %u usable rows", who,
-               plan->n_instance, sh.n_instance, sh.usable_rows);
+               plan->n_instance, sh.I, sh.usable);
     // The witness runs on the plan's stream, the proofs on the prover's: when those differ (or a batch left through an
     // error return and its kernels may still read the slots) the prover's streams are drained before the slots are rewritten.
-    if (sh.in_flight || plan->ctx != sh.ctx) ZG_TRY(prover_drain(p));
+    if (p->in_flight || plan->ctx != p->ctx) ZG_TRY(prover_drain(p));
     return zg_witness_run_dev(plan, images, count, slots, outputs);
 }
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """ZG_LAT_GATE off against on for lone proofs of one prover, interleaved in ONE process on one box:
     python tools/gate_ab.py [tiny|small|medium|large] [rounds]
-Checks that both settings give the same proof bytes for the same key, then prints the median latency of each.
+Checks that both settings give the same proof bytes for the same key, then prints the median latency of each and,
+on its last line, what the gate did (zg_prover_gate_stats).
 Run it under `timeout -k 10 SECONDS`: a gate that never opened would leave the stream waiting."""
 import os
 import statistics
@@ -35,4 +36,5 @@ for r in range(rounds):
 zg.tuning_set("ZG_LAT_GATE", -1)
 print(f"{c.model} k={c.k}: gate off {statistics.median(lat[0]):.4f} ms, gate on {statistics.median(lat[1]):.4f} ms "
       f"(medians of {len(lat[0])}; same proof bytes)")
+print("gate stats", p.gate_stats())  # (a healthy run: no yield, no proof made again in the plain order)
 p.close()

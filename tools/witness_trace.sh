@@ -7,7 +7,8 @@ set -e
 cd "$(dirname "$0")/../0g-halo2_amd"
 hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -I../include -DZG_WITNESS_TRACE -c csrc/witness.hip -o /tmp/witness_trace.o
 mkdir -p ../tools/ab
-hipcc -shared -fPIC --offload-arch=gfx950 -o ../tools/ab/libzg_trace.so csrc/ctx.o csrc/msm.o csrc/ntt.o csrc/params.o csrc/poly.o csrc/prover.o csrc/sort.o /tmp/witness_trace.o
+# (every object of the product's build but its witness.o: build the library first)
+hipcc -shared -fPIC --offload-arch=gfx950 -o ../tools/ab/libzg_trace.so $(ls csrc/*.o | grep -v '/witness\.o$') /tmp/witness_trace.o
 cd ..
 ZG_HALO2_LIB=$PWD/tools/ab/libzg_trace.so python3 tools/witness_time.py ${1:-tiny} 2> /tmp/witness_trace.txt > /dev/null
 python3 - <<EOF
