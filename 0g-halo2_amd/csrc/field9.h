@@ -368,6 +368,34 @@ __device__ __forceinline__ Fe f9_reduce_pack(const F9& v) {
     return f9_pack(a);
 }
 
+// x * c for a signed integer c of magnitude <= F9_SMALL_MAX, without a Montgomery product: the result is x * c in
+// whatever form x is in (a small integer coefficient needs no 2^261 factor of its own).  18 multiply-adds instead of 162.
+//   in:  x normalised (l[0..7] in [0, 2^29)), |x| < 2^258 -- a cell, or the output of Field9::mul.
+//   out: normalised, value in [0, 2p): inside Field9::mul's output range (-2^256, 2^256 + p), so every consumer of a
+//        product takes it as it is.
+// Proof.  v = x c has |v| < 2^270 and |v / p| < 2^16.4 (p > 2^253.6).  x / 2^232 = l[8] + l[7] 2^-29 up to 2^-29, so the
+// estimate below is v / p up to: five float roundings (two conversions / the sum, the product by c -- c itself is exact
+// below 2^24 --, the constant and its product), 5 * 2^-24 * 2^16.4 < 0.026, plus the dropped limbs' 2^-29 * 2^12 * 3.2e-7.
+// With the bias of 0.05 the estimate lies in (v/p - 0.08, v/p - 0.02): its floor q is floor(v/p) or one less, and
+// v - q p lies in [0, 2p).  The limb pass holds |x_i c| < 2^41 and |q p_i| < 2^47 in its 64-bit words; the last limb of a
+// value below 2p is below 2^23.
+constexpr int32_t F9_SMALL_MAX = 1 << 12;
+template <class P>
+__device__ __forceinline__ F9 f9_mul_small(const F9& x, int32_t c) {
+    const float top = (float)x.l[8] + (float)x.l[7] * 1.862645149230957e-09f;  // x / 2^232
+    const int32_t q = (int32_t)floorf(top * (float)c * 3.153175148504101e-07f - 0.05f);
+    F9 a;
+    int64_t cy = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int64_t w = (int64_t)x.l[i] * (int64_t)c - (int64_t)q * (int64_t)P::p(i) + cy;
+        a.l[i] = (int32_t)((uint32_t)w & (uint32_t)MASK29);
+        cy = w >> 29;
+    }
+    a.l[8] = (int32_t)((int64_t)x.l[8] * (int64_t)c - (int64_t)q * (int64_t)P::p(8) + cy);
+    return a;
+}
+
 // XYZZ point in the nine-limb form (coordinates x * 2^261, normalised); identity <=> zz limbs all zero
 struct alignas(16) XYZZ9 {
     F9 x, y, zz, zzz;

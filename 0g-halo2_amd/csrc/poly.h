@@ -9,9 +9,12 @@ namespace zg {
 struct alignas(16) DMono {
     Fe coeff;
     uint32_t n_factors;
-    uint32_t coeff_is_one;  // 1: coefficient +1, 2: coefficient -1 (the nine-limb evaluation subtracts instead of multiplying)
+    // 1: coefficient +1, 2: coefficient -1 (the nine-limb evaluation adds / subtracts instead of multiplying);
+    // 3 (monos_hat only): the coefficient is the integer `small`, |small| <= F9_SMALL_MAX (field9.h): f9_mul_small
+    uint32_t coeff_is_one;
     uint32_t factors[ZG_MAX_FACTORS];
-    uint32_t pad[2];
+    int32_t small;
+    uint32_t pad;
 };
 static_assert(sizeof(DMono) == 80, "DMono layout");
 
@@ -46,12 +49,20 @@ struct Cols {
 // (kernels read their proof's entry through the scalar cache: the proof index is workgroup-uniform).
 constexpr uint32_t PC_MAX_POINTS = 16;
 constexpr uint32_t EH_MAX_YPOW = 48;  // evaluate_h's grouped form: powers of y, one per term after the gates (+ 1)
+// evaluate_h's scaled permutation term (EvalHArgs::sigma_sc): the most permutation columns / sets it holds constants for
+constexpr uint32_t EH_MAX_PCOLS = 16, EH_MAX_PSETS = 8;
 struct alignas(16) ProofConst {
     uint32_t key[8];            // blinding key (ChaCha20), rand_fr
     Fe theta, beta, gamma;      // library (2^256 Montgomery) form: lookup compression, product terms
     Fe eh_y, eh_beta, eh_gamma, eh_theta;  // the form evaluate_h computes in (x 2^5 for the nine-limb kernel)
     Fe eh_delta_start[2];       // beta * zeta^zpow for zpow = 1, 2, same form
     Fe eh_ypow[EH_MAX_YPOW];    // y^j, same form (the weights of the permutation / lookup terms, EvalHArgs::n_terms)
+    // scaled permutation term, per coset shift zeta^a (index a - 1), same form: both factors of column `col` are divided by
+    // K = beta delta^col zeta^a, so eh_pcol[a - 1][col] = K^-1 and eh_pw[a - 1][s] = y^e_s * prod_(col in set s) K
+    // (the weight of set s's term); eh_scaled = 0 (beta = 0, or more columns than fit): the unscaled term
+    Fe eh_pcol[2][EH_MAX_PCOLS];
+    Fe eh_pw[2][EH_MAX_PSETS];
+    uint32_t eh_scaled, eh_pad[7];
     Fe xn;                      // x^n (vanishing::evaluate's Horner variable)
     Fe v;                       // GWC's v
     Fe points[PC_MAX_POINTS];   // opening points x * omega^rotation, by slot
@@ -62,6 +73,9 @@ struct EvalHArgs {
     DevCircuit c;
     Cols cols;  // extended cosets
     const Fe* sigma_cos;
+    // sigma_cos' column `col` times (delta^col zeta^zpow)^-1: the grouped nine-limb kernel reads it INSTEAD of sigma_cos
+    // for a proof with pc->eh_scaled (null: the unscaled permutation term for every proof)
+    const Fe* sigma_sc;
     const Fe* pz_cos;
     const Fe* lz_cos;
     const Fe* pin_cos;   // lookup l's permuted input / table cosets: pin_cos + l * perm_stride, ptab_cos + l * perm_stride

@@ -796,15 +796,20 @@ __device__ __forceinline__ F9 eval_poly9(const DevCircuit& c, const DMono* monos
     for (uint32_t m = p.first; m < p.first + p.count; m++) {
         const DMono* mo = monos + m;
         const uint32_t nf = mo->n_factors;
-        const bool unit = mo->coeff_is_one != 0 && nf > 0;
-        const bool neg = unit && mo->coeff_is_one == 2;
+        const uint32_t kind = mo->coeff_is_one;  // (wave-uniform, like everything read from the monomial)
+        const bool small = kind == 3 && nf > 0;  // a small integer coefficient: its first cell times it, no product
+        const bool unit = (kind == 1 || kind == 2 || small) && nf > 0;
+        const bool neg = kind == 2 && nf > 0;
         const uint32_t terms = nf + (unit ? 0u : 1u);  // operands of the product
-        if (terms == 1) {  // a bare cell or a bare constant
-            add(unit ? cell(mo->factors[0]) : f9_unpack(mo->coeff), neg);
+        if (terms == 1) {  // a bare cell (times a small integer) or a bare constant
+            F9 t = unit ? cell(mo->factors[0]) : f9_unpack(mo->coeff);
+            if (small) t = f9_mul_small<Fr9Params>(t, mo->small);
+            add(t, neg);
             continue;
         }
         uint32_t f = 0;
         F9 l = unit ? cell(mo->factors[f++]) : f9_unpack(mo->coeff);
+        if (small) l = f9_mul_small<Fr9Params>(l, mo->small);
         for (; f + 1 < nf; f++) l = Fr9::mul(l, cell(mo->factors[f]));
         const F9 r = cell(mo->factors[nf - 1]);
         if (held) {
@@ -849,11 +854,19 @@ int poly_gate_factor(zg_ctx* ctx, const Fe* col, uint32_t rot_off, uint32_t en, 
 //     h_num = G y^T + l0 * sum_i y^e_i a_i + llast * sum_i y^e_i b_i + lactive * sum_i y^e_i c_i,
 // with the powers of y from pc->eh_ypow: one product per term (two terms per Montgomery reduction) + four at the
 // end -- the same field element, since the arithmetic is exact.
+//
+// Grid: one workgroup per (row tile, proof), the proof index the fast dimension.  Workgroups are dealt to the 8 XCDs
+// round-robin, so -- as in ntt_pass_kernel -- workgroup L is renumbered to put consecutive numbers on ONE XCD: the nb
+// proofs of a tile then run side by side behind one L2, and the key's lines of that tile (fixed cosets, gate slabs, sigma,
+// l-polynomials: two thirds of what a row reads) are fetched once per batch instead of once per proof.
 template <bool GROUPED>
-__global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t en) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t en, uint32_t nb) {
+    uint32_t bid = blockIdx.x;
+    if ((gridDim.x & 7u) == 0) bid = (bid & 7u) * (gridDim.x >> 3) + (bid >> 3);
+    const uint32_t tile = bid / nb;
+    const uint32_t idx = tile * blockDim.x + threadIdx.x;
     if (idx >= en) return;
-    const EvalHProof pr = evalh_proof(a, blockIdx.y);
+    const EvalHProof pr = evalh_proof(a, bid - tile * nb);
     const ProofConst* pc = pr.pc;  // (scalars are re-read where they are used: workgroup-uniform scalar loads)
     const DevCircuit& c = a.c;
     const uint32_t mask = en - 1;
@@ -930,8 +943,16 @@ __global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t 
                 const F9 t = f9_sub(ld9(pr.pz_cos + (size_t)s * en + idx), ld9(pr.pz_cos + (size_t)(s - 1) * en + r_last));
                 acc1(s0, --w, t);
             }
-            F9 current_delta = Fr9::mul(f9_unpack(pc->eh_delta_start[a.zpow - 1]), ld9(a.ext_tw + idx));
-            const F9 delta = f9_unpack(a.delta);
+            // Scaled (pc->eh_scaled, workgroup-uniform): both factors of a column divided by K = beta delta^col zeta^a,
+            //     (beta sigma + v + gamma) / K = sigma_sc + t,   (v + beta delta^col zeta^a w^idx + gamma) / K = w^idx + t,
+            // t = (v + gamma) K^-1 with K^-1 = pc->eh_pcol: three products per column, and the set's weight pc->eh_pw
+            // carries prod K -- the same term, exactly.  Operand bounds: v + gamma and sigma_sc + t / w^idx + t are sums
+            // of two normalised values (limbs < 2^30, magnitude < 2^258) beside a normalised operand, as Fr9::mul allows;
+            // Fr9::mul2 wants all four below 2^29, so the last column's sums are normalised.
+            const bool scaled = a.sigma_sc != nullptr && pc->eh_scaled != 0;
+            // w^idx (scaled) or beta zeta^a w^idx, which then walks up by delta (unscaled)
+            F9 current_delta = ld9(a.ext_tw + idx);
+            if (!scaled) current_delta = Fr9::mul(f9_unpack(pc->eh_delta_start[a.zpow - 1]), current_delta);
             for (uint32_t s = 0; s < c.n_sets; s++) {
                 uint32_t c0 = s * c.chunk, c1 = c0 + c.chunk;
                 if (c1 > c.n_perm) c1 = c.n_perm;
@@ -941,18 +962,26 @@ __global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t 
                     const zg_query q = c.perm_cols[col];
                     const Fe* base = q.kind == ZG_FIXED ? pr.cols.fixed : q.kind == ZG_ADVICE ? pr.cols.advice : pr.cols.instance;
                     const F9 v = ld9(base + ((size_t)q.column << a.cols.log_size) + idx);
-                    const F9 sg = ld9(a.sigma_cos + (size_t)col * en + idx);
-                    const F9 fl = f9_norm(f9_add(f9_add(Fr9::mul(f9_unpack(pc->eh_beta), sg), v), f9_unpack(pc->eh_gamma)));
-                    const F9 fr = f9_norm(f9_add(f9_add(v, current_delta), f9_unpack(pc->eh_gamma)));
-                    current_delta = Fr9::mul(current_delta, delta);
+                    F9 fl, fr;
+                    if (scaled) {
+                        const F9 t = Fr9::mul(f9_add(v, f9_unpack(pc->eh_gamma)), f9_unpack(pc->eh_pcol[a.zpow - 1][col]));
+                        fl = f9_add(ld9(a.sigma_sc + (size_t)col * en + idx), t);
+                        fr = f9_add(current_delta, t);
+                    } else {
+                        const F9 sg = ld9(a.sigma_cos + (size_t)col * en + idx);
+                        fl = f9_norm(f9_add(f9_add(Fr9::mul(f9_unpack(pc->eh_beta), sg), v), f9_unpack(pc->eh_gamma)));
+                        fr = f9_norm(f9_add(f9_add(v, current_delta), f9_unpack(pc->eh_gamma)));
+                        current_delta = Fr9::mul(current_delta, f9_unpack(a.delta));
+                    }
                     if (col + 1 < c1) {
                         left = Fr9::mul(left, fl);
                         right = Fr9::mul(right, fr);
                     } else {
-                        left = Fr9::mul2<true>(left, fl, right, fr);
+                        left = Fr9::mul2<true>(left, f9_norm(fl), right, f9_norm(fr));
                     }
                 }
-                acc1(sa, --w, left);
+                --w;
+                sa = f9_norm(f9_add(sa, Fr9::mul(scaled ? f9_unpack(pc->eh_pw[a.zpow - 1][s]) : yw(w), left)));
             }
         }
         for (uint32_t l = 0; l < c.n_lookups; l++) {
@@ -1049,9 +1078,9 @@ int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, u
     ZG_REQUIRE(!a.hat || c.n_gates == 0 || (a.gates_hat != nullptr && a.gate_common != nullptr && a.gate_uni != nullptr && a.uni_coef != nullptr && a.gate_slab != nullptr && a.gate_slabs != nullptr), ZG_ERR_INVALID_ARG,
                "evaluate_h: the factored gate table is missing");
     if (a.hat && a.n_terms)
-        ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<true>, dim3((en + 255) / 256, nb), dim3(256), 0, a, en);
+        ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<true>, dim3((en + 255) / 256 * nb), dim3(256), 0, a, en, nb);
     else if (a.hat)
-        ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<false>, dim3((en + 255) / 256, nb), dim3(256), 0, a, en);
+        ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<false>, dim3((en + 255) / 256 * nb), dim3(256), 0, a, en, nb);
     else
         ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h_kernel, dim3((en + 255) / 256, nb), dim3(256), 0, a, en);
     ZG_HIP(hipGetLastError());

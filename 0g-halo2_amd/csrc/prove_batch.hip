@@ -673,7 +673,7 @@ struct ProveBatch {
         }
         have_random = true;
         for (uint32_t b = 0; b < nb; b++) tr[b].write_point(random_commit[b]);
-        for (uint32_t b = 0; b < nb; b++) evalh_consts(p->hpc[b], tr[b].squeeze(), hat, evalh_terms(pk));
+        for (uint32_t b = 0; b < nb; b++) evalh_consts(p->hpc[b], tr[b].squeeze(), pk);
         ZG_TICK("y");
         ZG_TRY(publish());
         ZG_TICK("y uploaded");

@@ -32,7 +32,7 @@ struct PkDev {
     struct SlabJob { uint32_t gate, query, first, count; };
     std::vector<SlabJob> slab_jobs;  // filled when the gates are factored, run once the fixed cosets exist
     Fe vk_repr{};
-    Fe omega{}, omega_inv{}, ifft_div{};
+    Fe omega{}, omega_inv{}, ifft_div{}, delta_inv{};
     Fe *fixed_val = nullptr, *sigma_val = nullptr, *omega_tw = nullptr;
     Fe* sh_polys = nullptr;  // coefficient forms [F + P][n]: fixed, then sigma
     // The extended domain evaluate_h works on.  Either EvaluationDomain's own coset zeta * <omega_(2^ext_k)> (8n points
@@ -41,7 +41,9 @@ struct PkDev {
     struct Dom {
         uint32_t ek = 0, en = 0;
         int zpow = 1;  // the coset shift is zeta^zpow
-        Fe *fixed_cos = nullptr, *sigma_cos = nullptr, *l0 = nullptr, *llast = nullptr, *lactive = nullptr,
+        // sigma_sc: sigma_cos' column col times (delta^col zeta^zpow)^-1, what evaluate_h's scaled permutation term reads
+        // in sigma_cos' place (evalh_perm_scaled; null otherwise)
+        Fe *fixed_cos = nullptr, *sigma_cos = nullptr, *sigma_sc = nullptr, *l0 = nullptr, *llast = nullptr, *lactive = nullptr,
            *gate_slabs = nullptr, *t_eval = nullptr, *ext_tw = nullptr;
     };
     Dom dom[3];           // [0]: the single coset; [1], [2]: the two parts of the split domain (when it applies)
@@ -178,7 +180,8 @@ int advice_into_slots(zg_prover* p, uint32_t nb, const zg_fr* const* advice_host
 int upload_consts(zg_prover* p, uint32_t nb);
 // evaluate_h's host side (prover.hip)
 uint32_t evalh_terms(const PkDev& pk);
-void evalh_consts(ProofConst& c, const Fe& y, bool hat, uint32_t n_terms);
+bool evalh_perm_scaled(const PkDev& pk);  // the key holds sigma_sc and ProofConst has room for the circuit's columns
+void evalh_consts(ProofConst& c, const Fe& y, const PkDev& pk);
 EvalHArgs evalh_args(const zg_prover* p, uint32_t di);
 // shard.hip: ONE all-gather of a phase's partial sums (p->xyzz) over the prover's communicator, then the additions into `out`
 int shard_gather_sum(zg_prover* p, size_t count, XYZZ* out);

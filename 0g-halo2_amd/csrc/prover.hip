@@ -65,19 +65,52 @@ uint32_t evalh_terms(const PkDev& pk) {
     return grouped && pk.hat && t >= 1 && t <= 40 && t + 1 <= EH_MAX_YPOW ? t : 0;
 }
 
-void evalh_consts(ProofConst& c, const Fe& y, bool hat, uint32_t n_terms) {
+// The default (grouped, nine-limb) kernel divides both factors of a permutation column by K = beta delta^col zeta^a:
+// (beta sigma + v + gamma) / K = sigma_sc + t and (v + beta delta^col zeta^a w^i + gamma) / K = w^i + t with
+// t = (v + gamma) K^-1 -- three products per column instead of four and no delta chain; the set's term gets prod K back
+// in its weight.  Needs the sigma_sc slabs of the key and room in ProofConst for the circuit's columns and sets.
+bool evalh_perm_scaled(const PkDev& pk) {
+    return evalh_terms(pk) != 0 && pk.P >= 1 && pk.P <= EH_MAX_PCOLS && pk.sets <= EH_MAX_PSETS;
+}
+
+void evalh_consts(ProofConst& c, const Fe& y, const PkDev& pk) {
+    const bool hat = pk.hat;
+    const uint32_t n_terms = evalh_terms(pk);
     const Fe zeta = fr_zeta(), zeta2 = Fr::sqr(zeta);
     c.eh_y = y; c.eh_beta = c.beta; c.eh_gamma = c.gamma; c.eh_theta = c.theta;
     c.eh_delta_start[0] = Fr::mul(c.beta, zeta);   // beta * coset shift
     c.eh_delta_start[1] = Fr::mul(c.beta, zeta2);
+    c.eh_scaled = 0;
     if (hat) {
         const Fe c261 = Fr9Params::c261_fe();
         for (Fe* cst : {&c.eh_y, &c.eh_beta, &c.eh_gamma, &c.eh_theta, &c.eh_delta_start[0], &c.eh_delta_start[1]})
             *cst = Fr::mul(*cst, c261);
+        Fe ypw[EH_MAX_YPOW];
         Fe pw = Fr::one();
         for (uint32_t j = 0; j <= n_terms && j < EH_MAX_YPOW; j++) {
+            ypw[j] = pw;
             c.eh_ypow[j] = Fr::mul(pw, c261);
             pw = Fr::mul(pw, y);
+        }
+        if (evalh_perm_scaled(pk) && !fe_is_zero(c.beta)) {  // (beta = 0 has no inverse: that proof's rows take the unscaled term)
+            const Fe shift[2] = {zeta, zeta2}, shift_inv[2] = {zeta2, zeta};  // (zeta^3 = 1)
+            const Fe beta_inv = Fr::inv(c.beta), delta = fr_delta();
+            Fe dpow = Fr::one(), dipow = Fr::one();
+            for (uint32_t s = 0; s < pk.sets; s++) {
+                Fe prod[2] = {Fr::one(), Fr::one()};
+                for (uint32_t col = s * pk.chunk; col < std::min(pk.P, (s + 1) * pk.chunk); col++) {
+                    for (int a = 0; a < 2; a++) {
+                        c.eh_pcol[a][col] = Fr::mul(Fr::mul(Fr::mul(beta_inv, dipow), shift_inv[a]), c261);
+                        prod[a] = Fr::mul(prod[a], Fr::mul(Fr::mul(c.beta, dpow), shift[a]));
+                    }
+                    dpow = Fr::mul(dpow, delta);
+                    dipow = Fr::mul(dipow, pk.delta_inv);
+                }
+                // set s's term is the kernel's term number n_terms - sets - 2 - s counted from the last (evaluate_h9_kernel)
+                const uint32_t e = n_terms - pk.sets - 2 - s;
+                for (int a = 0; a < 2; a++) c.eh_pw[a][s] = Fr::mul(Fr::mul(ypw[e], prod[a]), c261);
+            }
+            c.eh_scaled = 1;
         }
     }
 }
@@ -97,6 +130,7 @@ EvalHArgs evalh_args(const zg_prover* p, uint32_t di) {
     a.cols.log_size = d.ek; a.cols.rot_scale = (int32_t)(d.en / n);
     a.cols.adv_bs = a.cols.inst_bs = (size_t)p->ncos * d.en;
     a.sigma_cos = d.sigma_cos;
+    a.sigma_sc = d.sigma_sc;
     a.pz_cos = cos + (size_t)(A + I) * d.en;
     a.lz_cos = a.pz_cos + (size_t)S * d.en;
     // the a'/s' cosets are interleaved, [2l] = a'_l and [2l+1] = s'_l: two views with a stride of two slabs
@@ -214,6 +248,31 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
 // power of f and, when every group is a scalar multiple of the lowest one, U(x) = sum_k uc[k-1] x^k --
 // the shape halo2's selector compression leaves behind (selector -> q * prod_{u != t} (u - q)).  Failing
 // that, one occurrence of f is split off and the rest stays expanded.  Coefficients are in the 2^261 form.
+// What the nine-limb evaluation does with a coefficient given in the 2^261 form (DMono::coeff_is_one): 1 / 2 for +1 / -1,
+// 3 for any other integer c with |c| <= F9_SMALL_MAX, negative ones stored as r - |c| (DMono::small = c), 0 otherwise.
+void classify_coeff9(DMono& d) {
+    const Fe raw_one{{1, 0, 0, 0, 0, 0, 0, 0}};
+    const Fe unhat = Fr::inv(Fr::from_u64(32));  // x * 2^261 -> the library form x * 2^256
+    auto small_int = [&](const Fe& hat, int32_t* out) {  // the plain integer, if it is at most F9_SMALL_MAX
+        const Fe v = Fr::mul(Fr::mul(hat, unhat), raw_one);
+        for (int i = 1; i < 8; i++)
+            if (v.l[i]) return false;
+        *out = (int32_t)v.l[0];
+        return v.l[0] <= (uint32_t)F9_SMALL_MAX;
+    };
+    int32_t c = 0;
+    d.small = 0;
+    if (small_int(d.coeff, &c)) {
+        d.coeff_is_one = c == 1 ? 1 : 3;
+        d.small = c;
+    } else if (small_int(Fr::neg(d.coeff), &c)) {
+        d.coeff_is_one = c == 1 ? 2 : 3;
+        d.small = -c;
+    } else {
+        d.coeff_is_one = 0;
+    }
+}
+
 struct GateFactor {
     std::vector<DMono> inner;
     std::vector<Fe> uc;
@@ -276,10 +335,9 @@ GateFactor factor_gate(const std::vector<DMono>& monos, zg_poly g, uint32_t f, c
                 if (cnt > best_n) best = i, best_n = cnt;
             }
             const Fe d = base[best].coeff, d_inv = Fr::inv(d);
-            const Fe one_hat = Fr::mul(Fr::one(), c261);
             for (DMono& o : base) {
                 o.coeff = Fr::mul(Fr::mul(o.coeff, d_inv), c261);  // (o / d) back in the 2^261 form
-                o.coeff_is_one = fe_eq(o.coeff, one_hat) ? 1 : fe_eq(o.coeff, Fr::neg(one_hat)) ? 2 : 0;
+                classify_coeff9(o);
             }
             for (Fe& u : out.uc) u = Fr::mul(u, Fr::mul(d, Fr::inv(c261)));  // (d carries the 2^261 factor already)
             out.inner = std::move(base);
@@ -290,7 +348,7 @@ GateFactor factor_gate(const std::vector<DMono>& monos, zg_poly g, uint32_t f, c
         for (uint32_t m = g.first; m < g.first + g.count; m++) out.inner.push_back(strip(monos[m], false));
     }
     for (const DMono& d : out.inner) {
-        const uint32_t operands = d.n_factors + (d.coeff_is_one && d.n_factors ? 0u : 1u);
+        const uint32_t operands = d.n_factors + (d.coeff_is_one && d.n_factors ? 0u : 1u);  // (a small integer is no operand)
         out.cost += operands ? operands - 1 : 0;
     }
     if (!out.uc.empty() && !tabulated) out.cost += (uint32_t)out.uc.size();  // Horner in the kernel
@@ -334,6 +392,7 @@ int key_shape(PkDev* pk, const zg_ctx* ctx, const zg_circuit* cs, const zg_fr* v
     pk->ifft_div = Fr::inv(Fr::from_u64(pk->n));
     pk->hat = knob(K_EVALH9) != 0;
     pk->grouped = knob(K_EVALH_GROUPED) != 0;
+    pk->delta_inv = Fr::inv(fr_delta());
     return ZG_OK;
 }
 
@@ -444,7 +503,10 @@ int factored_view(PkDev* pk, const zg_circuit* cs, std::vector<DMono>& monos) {
     // hat implies that monos_hat, gates_hat, gate_common, gate_uni, uni_coef and gate_slab are ALL allocated here,
     // whatever the circuit holds (no gates, no lookups); poly_evaluate_h refuses a launch without them.
     const Fe c261 = Fr9Params::c261_fe();
-    for (auto& d : monos) d.coeff = Fr::mul(d.coeff, c261);
+    for (auto& d : monos) {
+        d.coeff = Fr::mul(d.coeff, c261);
+        classify_coeff9(d);
+    }
     std::vector<zg_poly> gates_hat(cs->n_gates);
     std::vector<uint32_t> common(cs->n_gates, 0xffffffffu);
     std::vector<zg_poly> gate_uni(cs->n_gates, zg_poly{0, 0});  // count 0: the factor is the cell itself
@@ -467,6 +529,25 @@ int factored_view(PkDev* pk, const zg_circuit* cs, std::vector<DMono>& monos) {
         }
         common[gi] = f;
     }
+#ifdef ZG_TICKS
+    {   // per row of evaluate_h: the coefficient products of the factored tables, as eval_poly9 will see them
+        uint32_t full = 0, small = 0, cells = 0;
+        auto tally = [&](zg_poly q) {
+            for (uint32_t m = q.first; m < q.first + q.count; m++) {
+                const DMono& d = monos[m];
+                if (!d.n_factors) continue;
+                full += d.coeff_is_one == 0;
+                small += d.coeff_is_one == 3;
+                cells += d.n_factors - 1;
+            }
+        };
+        for (uint32_t gi = 0; gi < cs->n_gates; gi++) tally(gates_hat[gi]);
+        for (uint32_t l = 0; l < cs->n_lookups; l++)
+            for (uint32_t e = 0; e < cs->lookups[l].width; e++) tally(cs->lookups[l].inputs[e]), tally(cs->lookups[l].tables[e]);
+        fprintf(stderr, "evaluate_h tables: per row %u products by a full coefficient, %u by a small integer, %u between cells\n",
+                full, small, cells);
+    }
+#endif
     ZG_TRY(key_alloc(pk, &pk->gate_uni, cs->n_gates ? cs->n_gates : 1));
     ZG_TRY(key_alloc(pk, &pk->uni_coef, uni_coef.size() ? uni_coef.size() : 1));
     if (cs->n_gates) ZG_HIP(hipMemcpy(pk->gate_uni, gate_uni.data(), cs->n_gates * sizeof(zg_poly), hipMemcpyHostToDevice));
@@ -573,6 +654,7 @@ int alloc_key_slabs(PkDev* pk) {
         PkDev::Dom& d = pk->dom[di];
         ZG_TRY(key_alloc(pk, &d.fixed_cos, (size_t)F * d.en));
         ZG_TRY(key_alloc(pk, &d.sigma_cos, (size_t)P * d.en));
+        if (evalh_perm_scaled(*pk)) ZG_TRY(key_alloc(pk, &d.sigma_sc, (size_t)P * d.en));
         ZG_TRY(key_alloc(pk, &d.l0, (size_t)d.en));
         ZG_TRY(key_alloc(pk, &d.llast, (size_t)d.en));
         ZG_TRY(key_alloc(pk, &d.lactive, (size_t)d.en));
@@ -589,6 +671,21 @@ int key_columns(zg_ctx* ctx, PkDev* pk, const zg_fr* values, uint32_t count, Fe*
     for (uint32_t di = 0; di < pk->nparts; di++) {
         PkDev::Dom& d = pk->dom[di];
         ZG_TRY(coeff_to_coset_dev(ctx, polys, n, n, d.*cos, d.en, count, d.ek, pk->hat, d.zpow));
+    }
+    return ZG_OK;
+}
+
+// evaluate_h's scaled permutation term: sigma_sc[col] = sigma_cos[col] * (delta^col zeta^zpow)^-1 on every part
+int key_sigma_scaled(zg_ctx* ctx, PkDev* pk) {
+    if (!evalh_perm_scaled(*pk)) return ZG_OK;
+    const Fe zeta = fr_zeta(), zeta2 = Fr::sqr(zeta);
+    for (uint32_t di = 0; di < pk->nparts; di++) {
+        PkDev::Dom& d = pk->dom[di];
+        Fe f = d.zpow == 1 ? zeta2 : zeta;  // zeta^-zpow (zeta^3 = 1)
+        for (uint32_t col = 0; col < pk->P; col++) {
+            ZG_TRY(poly_scale(ctx, d.sigma_cos + (size_t)col * d.en, d.sigma_sc + (size_t)col * d.en, d.en, f));
+            f = Fr::mul(f, pk->delta_inv);
+        }
     }
     return ZG_OK;
 }
@@ -756,6 +853,7 @@ static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fi
     ZG_TRY(key_columns(ctx, pk, fixed_values, pk->F, pk->fixed_val, pk->sh_polys, &PkDev::Dom::fixed_cos));
     if (pk->hat) ZG_TRY(key_gate_slabs(ctx, pk, cs));
     ZG_TRY(key_columns(ctx, pk, sigma_values, pk->P, pk->sigma_val, pk->sh_polys + (size_t)pk->F * pk->n, &PkDev::Dom::sigma_cos));
+    ZG_TRY(key_sigma_scaled(ctx, pk));
     ZG_TRY(key_l_polynomials(ctx, pk));
     ZG_TRY(key_t_evals(ctx, pk));
     ZG_HIP(hipStreamSynchronize(ctx->stream));
@@ -963,7 +1061,7 @@ int zg_prover_evaluate_h(zg_prover* p, const zg_fr* advice_polys, const zg_fr* i
     ProofConst& c = p->hpc[0];
     memset(&c, 0, sizeof(c));
     c.theta = to_fe(theta); c.beta = to_fe(beta); c.gamma = to_fe(gamma);
-    evalh_consts(c, to_fe(y), pk.hat, evalh_terms(pk));
+    evalh_consts(c, to_fe(y), pk);
     p->pin.stage_reset();
     ZG_TRY(upload_consts(p, 1));
     const PkDev::Dom& d = pk.dom[0];
