@@ -129,6 +129,24 @@ __global__ __launch_bounds__(256) void check_copies_kernel(DevCircuit c, Cols co
     flag_rows(bad, row, n, bm + ((size_t)b * nc + c.n_gates + c.n_lookups + pc) * w, totals + 3 * b + ZG_FAIL_COPY);
 }
 
+// permutation::keygen::Assembly::build_pk's values, one lane per cell: sigma[i] = delta^next_col[i] * omega^next_row[i]
+// (dpow[c] = delta^c, tw[r] = omega^r: the resident twiddle table).  A cell whose indices name no label gets 0 and the
+// smallest such cell index is left in *bad (0xffffffff: none).
+__global__ __launch_bounds__(256) void permutation_sigma_kernel(const uint32_t* __restrict__ next_col, const uint32_t* __restrict__ next_row,
+                                                                const Fe* __restrict__ tw, const Fe* __restrict__ dpow, uint32_t n,
+                                                                uint32_t n_perm, uint32_t cells, Fe* __restrict__ sigma,
+                                                                uint32_t* __restrict__ bad) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    const uint32_t c = next_col[i], r = next_row[i];
+    if (c >= n_perm || r >= n) {
+        atomicMin(bad, i);
+        sigma[i] = fe_zero();
+        return;
+    }
+    sigma[i] = Fr::mul(ldg(dpow + c), ldg(tw + r));
+}
+
 // ------------------------------------------------------------------ the table side of the lookups
 // vals + b * vals_bs + off[s] + e * n + row = table polynomial e of slot s's lookup at `row`
 __global__ __launch_bounds__(256) void check_table_eval_kernel(DevCircuit c, Cols cols_all, TabSlots sl, Fe* __restrict__ vals,
@@ -513,6 +531,47 @@ int zg_permutation_mapping(uint32_t k, uint32_t n_perm, const zg_fr* sigma_value
         next_col[i] = next[i] / n;
         next_row[i] = next[i] % n;
     }
+    return ZG_OK;
+}
+
+int zg_permutation_sigma(zg_ctx* ctx, uint32_t k, uint32_t n_perm, const uint32_t* next_col, const uint32_t* next_row,
+                         zg_fr* sigma_out) {
+    ZG_REQUIRE(ctx, ZG_ERR_INVALID_ARG, "zg_permutation_sigma: ctx is null");
+    ZG_REQUIRE(k >= 1 && k <= 22, ZG_ERR_INVALID_ARG, "zg_permutation_sigma: k=%u", k);
+    ZG_REQUIRE(n_perm == 0 || (next_col && next_row && sigma_out), ZG_ERR_INVALID_ARG, "zg_permutation_sigma: null argument");
+    if (!n_perm) return ZG_OK;
+    const uint32_t n = 1u << k;
+    ZG_REQUIRE((uint64_t)n_perm * n < (1ull << 32) - 1, ZG_ERR_UNSUPPORTED, "zg_permutation_sigma: %u columns of 2^%u rows", n_perm, k);
+    const uint32_t cells = n_perm * n;
+    ZG_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    Fe* tw = nullptr;
+    ZG_TRY(get_twiddles(ctx, k, host_domain_omega(k), &tw));
+    std::vector<Fe> dpow(n_perm);
+    Fe d = Fr::one();
+    for (uint32_t c = 0; c < n_perm; c++) {
+        dpow[c] = d;
+        d = Fr::mul(d, fr_delta());
+    }
+    WsScope ws(ctx);
+    uint32_t* d_next = ws.get<uint32_t>((size_t)2 * cells + 1);  // columns, rows, the error word
+    Fe* d_dpow = ws.get<Fe>(n_perm);
+    Fe* d_sigma = ws.get<Fe>(cells);
+    if (ws.failed) return ZG_ERR_OOM;
+    uint32_t* d_bad = d_next + (size_t)2 * cells;
+    uint32_t bad = 0xffffffffu;
+    ZG_HIP(hipMemcpyAsync(d_next, next_col, (size_t)cells * 4, hipMemcpyHostToDevice, st));
+    ZG_HIP(hipMemcpyAsync(d_next + cells, next_row, (size_t)cells * 4, hipMemcpyHostToDevice, st));
+    ZG_HIP(hipMemcpyAsync(d_bad, &bad, 4, hipMemcpyHostToDevice, st));
+    ZG_HIP(hipMemcpyAsync(d_dpow, dpow.data(), (size_t)n_perm * sizeof(Fe), hipMemcpyHostToDevice, st));
+    ZG_LAUNCH(ctx, "permutation_sigma", (double)cells * 40.0, permutation_sigma_kernel, dim3((cells + 255) / 256), dim3(256), 0, d_next,
+              d_next + cells, tw, d_dpow, n, n_perm, cells, d_sigma, d_bad);
+    ZG_HIP(hipGetLastError());
+    ZG_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    ZG_HIP(hipStreamSynchronize(st));  // (the host arrays above are read until here)
+    ZG_REQUIRE(bad == 0xffffffffu, ZG_ERR_INVALID_ARG, "zg_permutation_sigma: column %u, row %u maps to (%u, %u), outside %u columns of %u rows",
+               bad / n, bad % n, next_col[bad], next_row[bad], n_perm, n);
+    ZG_HIP(hipMemcpy(sigma_out, d_sigma, (size_t)cells * sizeof(Fe), hipMemcpyDeviceToHost));
     return ZG_OK;
 }
 

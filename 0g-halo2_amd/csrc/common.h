@@ -115,6 +115,8 @@ struct zg_ctx {
     zg_ctx* side = nullptr;  // optional second stream + workspace pool (created on demand, same device)
     // MSM bucket reduction with two lanes per EC addition (latency) or one (throughput); see msm.hip
     bool msm_pair = true;
+    // g_coset of the stand-alone extended-domain transforms (zg_ctx_set_coset_generator); a prover keeps the one it was created under
+    zg::Fe coset_gen = zg::fr_zeta();
     // SURVEY-unit bytes of the NEXT transform plan run on this context (-1: the plan's own in + out; ntt.hip consumes it)
     double unit_next = -1.0;
     bool msm_dense_hint = false;  // set by a caller around an MSM whose vectors are all random (latency form: one lane per task)

@@ -324,6 +324,31 @@ int zg_ctx_profile_collect(zg_ctx* ctx, zg_kernel_stat* out, size_t cap, size_t*
     return ZG_OK;
 }
 
+int zg_fr_cube_root(uint32_t which, zg_fr* out) {
+    ZG_REQUIRE(which <= 1 && out, ZG_ERR_INVALID_ARG, "zg_fr_cube_root: root %u of 2", which);
+    const Fe z = which ? Fr::sqr(fr_zeta()) : fr_zeta();
+    memcpy(out, &z, 32);
+    return ZG_OK;
+}
+
+int zg_ctx_set_coset_generator(zg_ctx* ctx, const zg_fr* g_coset) {
+    ZG_REQUIRE(ctx && g_coset, ZG_ERR_INVALID_ARG, "zg_ctx_set_coset_generator: null argument");
+    Fe g;
+    memcpy(&g, g_coset, 32);
+    ZG_REQUIRE(fe_eq(g, fr_zeta()) || fe_eq(g, Fr::sqr(fr_zeta())), ZG_ERR_INVALID_ARG,
+               "zg_ctx_set_coset_generator: not a primitive cube root of unity");
+    ZG_ENTER(ctx);
+    ctx->coset_gen = g;
+    return ZG_OK;
+}
+
+int zg_ctx_coset_generator(zg_ctx* ctx, zg_fr* out) {
+    ZG_REQUIRE(ctx && out, ZG_ERR_INVALID_ARG, "zg_ctx_coset_generator: null argument");
+    ZG_ENTER(ctx);
+    memcpy(out, &ctx->coset_gen, 32);
+    return ZG_OK;
+}
+
 int zg_domain_omega(uint32_t log_n, zg_fr* omega, zg_fr* omega_inv) {
     ZG_REQUIRE(log_n <= FR_S, ZG_ERR_INVALID_ARG, "zg_domain_omega: log_n %u > 28", log_n);
     Fe w = host_domain_omega(log_n);

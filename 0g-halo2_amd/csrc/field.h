@@ -430,7 +430,7 @@ ZG_HD Fe fr_delta() {  // 7^(2^28)
     return Fe{{0xefd78855u, 0x9a0c322bu, 0x249b563cu, 0x46e82d14u, 0xe0b0b7a7u, 0x5983a663u,
                0xaaa111adu, 0x22ab452bu}};
 }
-ZG_HD Fe fr_zeta() {  // 7^((r-1)/3): the coset generator of EvaluationDomain
+ZG_HD Fe fr_zeta() {  // 7^((r-1)/3): the DEFAULT coset generator (zg_fr_cube_root(0)); the one in use is the context's or the key's
     return Fe{{0x4a0329b3u, 0x93e7cedeu, 0x7a96c167u, 0x7d4fdca7u, 0xb19a750au, 0x8be4ba08u,
                0xa5661c25u, 0x1cbd5653u}};
 }

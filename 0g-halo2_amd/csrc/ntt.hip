@@ -758,14 +758,14 @@ int ntt_batch_dev(zg_ctx* ctx, Fe* d_a, size_t stride, size_t batch, uint32_t lo
 // entries with j % 3 == 0, n of the 8n loaded)
 int coeff_to_extended_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, Fe* d_out, size_t out_stride,
                           size_t batch, uint32_t k, uint32_t ext_k, bool hat) {
-    return coeff_to_coset_dev(ctx, d_in, in_stride, 1u << k, d_out, out_stride, batch, ext_k, hat, 1, nullptr);
+    return coeff_to_coset_dev(ctx, d_in, in_stride, 1u << k, d_out, out_stride, batch, ext_k, hat, ctx->coset_gen, nullptr);
 }
 
-// The general form: `in_len` coefficients (<= 2^ext_k) evaluated on the coset zeta^zeta_pow * <omega_(2^ext_k)>
-// (zeta_pow = 1: EvaluationDomain's own coset; 2: the second coset of the prover's split extended domain).
+// The general form: `in_len` coefficients (<= 2^ext_k) evaluated on the coset shift * <omega_(2^ext_k)>, shift a
+// primitive cube root of unity (the generator g_coset: EvaluationDomain's own coset; its square: the second coset of
+// the prover's split extended domain).
 int coeff_to_coset_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, uint32_t in_len, Fe* d_out, size_t out_stride,
-                       size_t batch, uint32_t ext_k, bool hat, int zeta_pow, const Grouping* grp) {
-    ZG_REQUIRE(zeta_pow == 1 || zeta_pow == 2, ZG_ERR_INVALID_ARG, "coeff_to_coset: zeta power %d", zeta_pow);
+                       size_t batch, uint32_t ext_k, bool hat, const Fe& shift, const Grouping* grp) {
     ZG_REQUIRE(in_len <= (1u << ext_k), ZG_ERR_INVALID_ARG, "coeff_to_coset: %u coefficients for 2^%u points", in_len, ext_k);
     ZG_TRY(ensure_lds_attr(ctx));
     WsScope ws(ctx);
@@ -780,8 +780,8 @@ int coeff_to_coset_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, uint32_t i
     p.out_len = 1u << ext_k;
     p.coset_in = 1;
     p.zin0 = Fr::one();
-    p.zin1 = zeta_pow == 1 ? fr_zeta() : Fr::sqr(fr_zeta());   // shift^1
-    p.zin2 = zeta_pow == 1 ? Fr::sqr(fr_zeta()) : fr_zeta();   // shift^2 (zeta^4 = zeta)
+    p.zin1 = shift;
+    p.zin2 = Fr::sqr(shift);
     if (hat) {
         const Fe c32 = Fr::from_u64(32);
         p.coset_in = 2;
@@ -804,13 +804,12 @@ int coeff_to_coset_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, uint32_t i
 int extended_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t k, uint32_t ext_k, size_t out_len,
                           Fe* d_out, bool unhat) {
     (void)k;
-    return coset_to_coeff_dev(ctx, d_evals, ext_k, out_len, d_out, unhat, 1, 1, 0, 0);
+    return coset_to_coeff_dev(ctx, d_evals, ext_k, out_len, d_out, unhat, ctx->coset_gen, 1, 0, 0);
 }
 
 // `batch` arrays: evaluations at d_evals + b * in_stride (in_stride = 0: 2^ext_k), coefficients to d_out + b * out_stride
-int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len, Fe* d_out, bool unhat, int zeta_pow,
+int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len, Fe* d_out, bool unhat, const Fe& shift,
                        size_t batch, size_t in_stride, size_t out_stride) {
-    ZG_REQUIRE(zeta_pow == 1 || zeta_pow == 2, ZG_ERR_INVALID_ARG, "coset_to_coeff: zeta power %d", zeta_pow);
     ZG_TRY(ensure_lds_attr(ctx));
     WsScope ws(ctx);
     size_t n = (size_t)1 << ext_k;
@@ -826,8 +825,8 @@ int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len,
     p.scale_out = true;
     p.scale = Fr::inv(Fr::from_u64((uint64_t)n * (unhat ? 32u : 1u)));
     p.coset_out = true;
-    p.zout1 = zeta_pow == 1 ? Fr::sqr(fr_zeta()) : fr_zeta();  // shift^-1
-    p.zout2 = zeta_pow == 1 ? fr_zeta() : Fr::sqr(fr_zeta());  // shift^-2
+    p.zout1 = Fr::sqr(shift);  // shift^-1 (shift^3 = 1)
+    p.zout2 = shift;           // shift^-2
     Fe* tmp = nullptr;
     if (ntt_needs_tmp(ext_k)) {
         tmp = ws.get<Fe>(batch * n);

@@ -235,8 +235,8 @@ int coeff_to_extended_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, Fe* d_o
                           size_t batch, uint32_t k, uint32_t ext_k, bool hat);
 int extended_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t k, uint32_t ext_k, size_t out_len, Fe* d_out, bool unhat);
 int coeff_to_coset_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, uint32_t in_len, Fe* d_out, size_t out_stride,
-                       size_t batch, uint32_t ext_k, bool hat, int zeta_pow, const Grouping* grp = nullptr);
-int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len, Fe* d_out, bool unhat, int zeta_pow,
+                       size_t batch, uint32_t ext_k, bool hat, const Fe& shift, const Grouping* grp = nullptr);
+int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len, Fe* d_out, bool unhat, const Fe& shift,
                        size_t batch = 1, size_t in_stride = 0, size_t out_stride = 0);
 // split extended domain (prove_batch.hip): the pieces of the interpolation between its two cosets
 // (each for nb proofs: proof b's arrays `*_bs` elements after proof b-1's)

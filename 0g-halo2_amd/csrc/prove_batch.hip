@@ -69,14 +69,17 @@ __global__ void gate_pull_kernel(const uint32_t* gate, uint32_t seq, uint32_t* g
     if (threadIdx.x == 0) {
         const uint64_t t0 = wall_clock64();
         uint32_t got = 1;
-        while (__hip_atomic_load(gate, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) != seq) {
+        // (open at `seq` OR LATER, in the sequence numbers' modular order: where nothing stands between two gates -- a circuit
+        //  without lookups or permutation queues nothing behind theta and needs no device result before beta -- the host may
+        //  have opened the NEXT gate before this kernel's first look at the word)
+        while ((int32_t)(__hip_atomic_load(gate, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - seq) < 0) {
             if (wall_clock64() - t0 > max_ticks) {
                 got = 0;
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
         }
-        if (!got) __hip_atomic_store(gave_up, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!got) __hip_atomic_store(gave_up, seq | 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);  // (any non-zero word)
         open = got;
     }
     __syncthreads();
@@ -321,7 +324,7 @@ struct ProveBatch {
             const Grouping g = grouping(per, pp_bs, (size_t)p->ncos * d.en);
             c->unit_next = (double)nb * per * ext_unit * ((double)d.en / parts_en);
             ZG_TRY(coeff_to_coset_dev(c, pp_at(ix0), n, n, p->dbuf[di].cos + (size_t)(ix0 - p->ix_adv) * d.en, d.en, (size_t)nb * per,
-                                      d.ek, hat, d.zpow, &g));
+                                      d.ek, hat, pk.shift(d.zpow), &g));
         }
         return ZG_OK;
     }
@@ -433,7 +436,7 @@ struct ProveBatch {
         const bool lost = knob(K_LAT_GATE) == 2 && gates_armed == 0;
         gates_armed++;
         ZG_LAUNCH(ctx, "gate_pull", (double)bytes * 2, gate_pull_kernel, dim3(1), dim3(256), 0, p->pin.dev_view(p->pin.gate_word()),
-                  lost ? p->gate_seq ^ 0x80000000u : p->gate_seq, p->pin.dev_view(p->pin.gave_up_word()), lost ? GATE_MAX_TICKS / 20 : GATE_MAX_TICKS, dev_view, (uint4*)p->d_pc, (uint32_t)(bytes / 16));
+                  lost ? p->gate_seq + 0x40000000u : p->gate_seq, p->pin.dev_view(p->pin.gave_up_word()), lost ? GATE_MAX_TICKS / 20 : GATE_MAX_TICKS, dev_view, (uint4*)p->d_pc, (uint32_t)(bytes / 16));
         ZG_HIP(hipGetLastError());
         return ZG_OK;
     }
@@ -697,27 +700,27 @@ struct ProveBatch {
         const double ext_inv_unit = (double)nb * 2.0 * (double)((size_t)1 << ek) * 32.0;  // (ext -> coeff, 2 * 8n * 32 B)
         if (!split) {
             ctx->unit_next = ext_inv_unit;
-            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[0].h, ek, (size_t)Q * n, pp_at(p->ix_hpiece), hat, 1, nb, pk.dom[0].en, pp_bs));
+            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[0].h, ek, (size_t)Q * n, pp_at(p->ix_hpiece), hat, pk.zeta, nb, pk.dom[0].en, pp_bs));
         } else {
             // h = A + (X^L1 - c1) B:  A (degree < L1) from the first coset, where X^L1 = c1 = shift1^L1;  B (degree < L2)
             // from the second, where X^L1 = c2 and X^L2 = e are constants too:  B = (h - A) / (c2 - c1) there, with A
             // folded modulo X^L2 - e before it is evaluated on those L2 points.
             const PkDev::Dom &d1 = pk.dom[1], &d2 = pk.dom[2];
             const uint32_t L1 = d1.en, L2 = d2.en;
-            const Fe zeta = fr_zeta(), zeta2 = Fr::sqr(zeta);
+            const Fe zeta = pk.zeta, zeta2 = Fr::sqr(zeta);
             const Fe c1 = Fr::pow_u64(zeta, L1), c2 = Fr::pow_u64(zeta2, L1), e = Fr::pow_u64(zeta2, L2);
             Fe* hp = pp_at(p->ix_hpiece);
             const size_t tb = (size_t)3 * L2;
             Fe *fold = p->split_tmp, *a2 = fold + L2, *bc = a2 + L2;
             ctx->unit_next = ext_inv_unit;  // (the three transforms of the split form stand for ONE extended_to_coeff)
-            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[1].h, d1.ek, L1, hp, hat, 1, nb, L1, pp_bs));  // A, in place of the low pieces
+            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[1].h, d1.ek, L1, hp, hat, zeta, nb, L1, pp_bs));  // A, in place of the low pieces
             ZG_TRY(poly_fold(ctx, nb, hp, pp_bs, L2, L1 / L2, e, fold, tb));                       // A mod (X^L2 - e)
             ctx->unit_next = 0.0;
-            ZG_TRY(coeff_to_coset_dev(ctx, fold, tb, L2, a2, tb, nb, d2.ek, false, 2));            // A on the second coset
+            ZG_TRY(coeff_to_coset_dev(ctx, fold, tb, L2, a2, tb, nb, d2.ek, false, zeta2));            // A on the second coset
             const Fe unhat = hat ? Fr::inv(Fr::from_u64(32)) : Fr::one();
             ZG_TRY(poly_diff_scale(ctx, nb, p->dbuf[2].h, L2, unhat, a2, tb, Fr::inv(Fr::sub(c2, c1)), a2, tb, L2));  // B on the second coset
             ctx->unit_next = 0.0;
-            ZG_TRY(coset_to_coeff_dev(ctx, a2, d2.ek, L2, bc, false, 2, nb, tb, tb));              // B
+            ZG_TRY(coset_to_coeff_dev(ctx, a2, d2.ek, L2, bc, false, zeta2, nb, tb, tb));              // B
             ZG_TRY(poly_split_combine(ctx, nb, hp, pp_bs, bc, tb, L2, c1, L1));                    // h = A - c1 B + X^L1 B
         }
         ctx->msm_dense_hint = true;  // (the quotient pieces are random vectors: every digit of every window is an addition)

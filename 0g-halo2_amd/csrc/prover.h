@@ -33,6 +33,10 @@ struct PkDev {
     std::vector<SlabJob> slab_jobs;  // filled when the gates are factored, run once the fixed cosets exist
     Fe vk_repr{};
     Fe omega{}, omega_inv{}, ifft_div{}, delta_inv{};
+    // g_coset, the generator of the extended coset: the creating context's at zg_prover_create* (zg_ctx_set_coset_generator),
+    // a primitive cube root of unity -- so zeta^2 = zeta^-1 is the other one.  "zeta" below and in the kernels is THIS value.
+    Fe zeta{};
+    Fe shift(int zpow) const { return zpow == 1 ? zeta : Fr::sqr(zeta); }  // zeta^zpow, zpow = 1 or 2
     Fe *fixed_val = nullptr, *sigma_val = nullptr, *omega_tw = nullptr;
     Fe* sh_polys = nullptr;  // coefficient forms [F + P][n]: fixed, then sigma
     // The extended domain evaluate_h works on.  Either EvaluationDomain's own coset zeta * <omega_(2^ext_k)> (8n points

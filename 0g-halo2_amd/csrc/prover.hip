@@ -76,7 +76,7 @@ bool evalh_perm_scaled(const PkDev& pk) {
 void evalh_consts(ProofConst& c, const Fe& y, const PkDev& pk) {
     const bool hat = pk.hat;
     const uint32_t n_terms = evalh_terms(pk);
-    const Fe zeta = fr_zeta(), zeta2 = Fr::sqr(zeta);
+    const Fe zeta = pk.zeta, zeta2 = Fr::sqr(zeta);
     c.eh_y = y; c.eh_beta = c.beta; c.eh_gamma = c.gamma; c.eh_theta = c.theta;
     c.eh_delta_start[0] = Fr::mul(c.beta, zeta);   // beta * coset shift
     c.eh_delta_start[1] = Fr::mul(c.beta, zeta2);
@@ -164,6 +164,7 @@ void free_slots(zg_prover* p) {
     p->slot_owned.clear();
     if (p->pin.host) (void)hipHostFree(p->pin.host);
     p->pin = PinnedArena{};
+    p->gate_seq = 0;  // (the gate word goes with the arena: a new one starts at zero, and a gate opens at its number or later)
     p->cap = 0;
     p->uploaded_lists.clear();
     p->warm_sig = 0;  // (new buffers: the next proof is a first proof again -- ProveBatch::gate_wanted)
@@ -393,6 +394,7 @@ int key_shape(PkDev* pk, const zg_ctx* ctx, const zg_circuit* cs, const zg_fr* v
     pk->hat = knob(K_EVALH9) != 0;
     pk->grouped = knob(K_EVALH_GROUPED) != 0;
     pk->delta_inv = Fr::inv(fr_delta());
+    pk->zeta = ctx->coset_gen;
     return ZG_OK;
 }
 
@@ -670,7 +672,7 @@ int key_columns(zg_ctx* ctx, PkDev* pk, const zg_fr* values, uint32_t count, Fe*
     ZG_TRY(ntt_batch_to_dev(ctx, val, polys, n, count, pk->k, pk->omega_inv, &pk->ifft_div));
     for (uint32_t di = 0; di < pk->nparts; di++) {
         PkDev::Dom& d = pk->dom[di];
-        ZG_TRY(coeff_to_coset_dev(ctx, polys, n, n, d.*cos, d.en, count, d.ek, pk->hat, d.zpow));
+        ZG_TRY(coeff_to_coset_dev(ctx, polys, n, n, d.*cos, d.en, count, d.ek, pk->hat, pk->shift(d.zpow)));
     }
     return ZG_OK;
 }
@@ -678,10 +680,9 @@ int key_columns(zg_ctx* ctx, PkDev* pk, const zg_fr* values, uint32_t count, Fe*
 // evaluate_h's scaled permutation term: sigma_sc[col] = sigma_cos[col] * (delta^col zeta^zpow)^-1 on every part
 int key_sigma_scaled(zg_ctx* ctx, PkDev* pk) {
     if (!evalh_perm_scaled(*pk)) return ZG_OK;
-    const Fe zeta = fr_zeta(), zeta2 = Fr::sqr(zeta);
     for (uint32_t di = 0; di < pk->nparts; di++) {
         PkDev::Dom& d = pk->dom[di];
-        Fe f = d.zpow == 1 ? zeta2 : zeta;  // zeta^-zpow (zeta^3 = 1)
+        Fe f = pk->shift(3 - d.zpow);  // zeta^-zpow (zeta^3 = 1)
         for (uint32_t col = 0; col < pk->P; col++) {
             ZG_TRY(poly_scale(ctx, d.sigma_cos + (size_t)col * d.en, d.sigma_sc + (size_t)col * d.en, d.en, f));
             f = Fr::mul(f, pk->delta_inv);
@@ -724,9 +725,9 @@ int key_l_polynomials(zg_ctx* ctx, PkDev* pk) {
     ZG_TRY(ntt_batch_dev(ctx, t3, n, 3, pk->k, pk->omega_inv, &pk->ifft_div));
     for (uint32_t di = 0; di < pk->nparts; di++) {
         PkDev::Dom& d = pk->dom[di];
-        ZG_TRY(coeff_to_coset_dev(ctx, t3, n, n, d.l0, d.en, 1, d.ek, pk->hat, d.zpow));
-        ZG_TRY(coeff_to_coset_dev(ctx, t3 + n, n, n, d.llast, d.en, 1, d.ek, pk->hat, d.zpow));
-        ZG_TRY(coeff_to_coset_dev(ctx, t3 + 2 * n, n, n, lblind, d.en, 1, d.ek, pk->hat, d.zpow));
+        ZG_TRY(coeff_to_coset_dev(ctx, t3, n, n, d.l0, d.en, 1, d.ek, pk->hat, pk->shift(d.zpow)));
+        ZG_TRY(coeff_to_coset_dev(ctx, t3 + n, n, n, d.llast, d.en, 1, d.ek, pk->hat, pk->shift(d.zpow)));
+        ZG_TRY(coeff_to_coset_dev(ctx, t3 + 2 * n, n, n, lblind, d.en, 1, d.ek, pk->hat, pk->shift(d.zpow)));
         ZG_TRY(poly_lactive(ctx, d.lactive, d.llast, lblind, d.en, pk->hat));
     }
     ZG_HIP(hipStreamSynchronize(ctx->stream));
@@ -742,7 +743,7 @@ int key_t_evals(zg_ctx* ctx, PkDev* pk) {
         uint32_t t_len = 1u << (d.ek - pk->k);
         std::vector<Fe> te(t_len);
         Fe ext_omega = host_domain_omega(d.ek);
-        const Fe shift = d.zpow == 1 ? fr_zeta() : Fr::sqr(fr_zeta());
+        const Fe shift = pk->shift(d.zpow);
         Fe cur = Fr::pow_u64(shift, n), step = Fr::pow_u64(ext_omega, n);
         for (uint32_t i = 0; i < t_len; i++) {
             te[i] = Fr::inv(Fr::sub(cur, Fr::one()));
@@ -1009,7 +1010,7 @@ int zg_prover_fetch_slot(zg_prover* p, size_t slot, uint32_t what, uint32_t inde
         WsScope ws(p->ctx);
         Fe* tmp = ws.get<Fe>(count);
         if (!tmp) return ZG_ERR_OOM;
-        ZG_TRY(coeff_to_coset_dev(p->ctx, hp, (size_t)pk.qpd * n, (uint32_t)(pk.qpd * n), tmp, count, 1, pk.ext_k, false, 1));
+        ZG_TRY(coeff_to_coset_dev(p->ctx, hp, (size_t)pk.qpd * n, (uint32_t)(pk.qpd * n), tmp, count, 1, pk.ext_k, false, pk.zeta));
         ZG_HIP(hipStreamSynchronize(p->ctx->stream));
         ZG_HIP(hipMemcpy(out, tmp, count * 32, hipMemcpyDeviceToHost));
         return ZG_OK;
@@ -1025,6 +1026,52 @@ int zg_prover_fetch_slot(zg_prover* p, size_t slot, uint32_t what, uint32_t inde
     }
     ZG_HIP(hipStreamSynchronize(p->ctx->stream));
     ZG_HIP(hipMemcpy(out, src, count * 32, hipMemcpyDeviceToHost));
+    return ZG_OK;
+}
+
+int zg_prover_coset_generator(const zg_prover* p, zg_fr* out) {
+    ZG_REQUIRE(p && out, ZG_ERR_INVALID_ARG, "zg_prover_coset_generator: null argument");
+    memcpy(out, &p->pk->zeta, 32);
+    return ZG_OK;
+}
+
+// What keygen_pk derived, as halo2's ProvingKey holds it: the coefficient forms as they stand, the extended families from
+// the single-coset slabs (dom[0]: kept beside the split parts, and beside sigma_sc) with the nine-limb form's 2^5 taken off.
+int zg_prover_export_key(zg_prover* p, uint32_t family, uint32_t index, zg_fr* out, size_t cap_elems) {
+    ZG_REQUIRE(p && out, ZG_ERR_INVALID_ARG, "zg_prover_export_key: null argument");
+    zg_ctx* ctx = p->ctx;
+    ZG_ENTER(ctx);
+    const PkDev& pk = *p->pk;
+    const PkDev::Dom& d = pk.dom[0];
+    const Fe* src = nullptr;
+    uint32_t limit = 1;
+    bool extended = true;
+    switch (family) {
+        case ZG_KEY_FIXED_POLY: src = pk.sh_polys; limit = pk.F; extended = false; break;
+        case ZG_KEY_SIGMA_POLY: src = pk.sh_polys + (size_t)pk.F * pk.n; limit = pk.P; extended = false; break;
+        case ZG_KEY_FIXED_COSET: src = d.fixed_cos; limit = pk.F; break;
+        case ZG_KEY_SIGMA_COSET: src = d.sigma_cos; limit = pk.P; break;
+        case ZG_KEY_L0: src = d.l0; break;
+        case ZG_KEY_L_LAST: src = d.llast; break;
+        case ZG_KEY_L_ACTIVE_ROW: src = d.lactive; break;
+        default: ZG_REQUIRE(false, ZG_ERR_INVALID_ARG, "zg_prover_export_key: unknown family %u", family);
+    }
+    ZG_REQUIRE(index < limit, ZG_ERR_INVALID_ARG, "zg_prover_export_key: index %u of a family of %u", index, limit);
+    const size_t count = extended ? d.en : pk.n;
+    ZG_REQUIRE(cap_elems >= count, ZG_ERR_INVALID_ARG, "zg_prover_export_key: need %zu elements", count);
+    src += (size_t)index * count;
+    hipStream_t st = ctx->stream;
+    if (extended && pk.hat) {
+        WsScope ws(ctx);
+        Fe* tmp = ws.get<Fe>(count);
+        if (!tmp) return ZG_ERR_OOM;
+        ZG_TRY(poly_scale(ctx, src, tmp, count, Fr::inv(Fr::from_u64(32))));
+        ZG_HIP(hipMemcpyAsync(out, tmp, count * 32, hipMemcpyDeviceToHost, st));
+        ZG_HIP(hipStreamSynchronize(st));
+        return ZG_OK;
+    }
+    ZG_HIP(hipMemcpyAsync(out, src, count * 32, hipMemcpyDeviceToHost, st));
+    ZG_HIP(hipStreamSynchronize(st));
     return ZG_OK;
 }
 
@@ -1065,7 +1112,7 @@ int zg_prover_evaluate_h(zg_prover* p, const zg_fr* advice_polys, const zg_fr* i
     p->pin.stage_reset();
     ZG_TRY(upload_consts(p, 1));
     const PkDev::Dom& d = pk.dom[0];
-    ZG_TRY(coeff_to_coset_dev(ctx, p->pp + (size_t)(p->ix_adv - p->nsh) * n, n, n, p->dbuf[0].cos, d.en, p->ncos, d.ek, pk.hat, d.zpow));
+    ZG_TRY(coeff_to_coset_dev(ctx, p->pp + (size_t)(p->ix_adv - p->nsh) * n, n, n, p->dbuf[0].cos, d.en, p->ncos, d.ek, pk.hat, pk.shift(d.zpow)));
     const EvalHArgs a = evalh_args(p, 0);
     ZG_TRY(poly_evaluate_h(ctx, a, d.en, 1, pk.A + pk.I + pk.F, (double)d.en));
     WsScope ws(ctx);

@@ -76,6 +76,8 @@ ABI_SYMBOLS = [
     "zg_tuning_set", "zg_tuning_get", "zg_tuning_names", "zg_bases_enable_digit_table", "zg_prover_enable_digit_tables",
     "zg_prover_vk_commitments", "zg_verifier_create", "zg_verifier_destroy", "zg_verifier_verify_batch", "zg_pairing_check",
     "zg_prover_check_batch", "zg_prover_check_batch_dev", "zg_prover_check_images", "zg_permutation_mapping",
+    "zg_fr_cube_root", "zg_ctx_set_coset_generator", "zg_ctx_coset_generator", "zg_prover_coset_generator",
+    "zg_permutation_sigma", "zg_prover_export_key",
 ]
 
 def tuning_names() -> list:
@@ -137,6 +139,29 @@ def permutation_mapping(sigma_values: np.ndarray, k: int):
     next_row = np.zeros((m, 1 << k), np.uint32)
     _check(load().zg_permutation_mapping(c_uint32(k), c_uint32(m), _ptr(sigma_values), _ptr(next_col), _ptr(next_row)))
     return next_col, next_row
+
+
+def permutation_sigma(ctx: "Ctx", next_col: np.ndarray, next_row: np.ndarray, k: int) -> np.ndarray:
+    """zg_permutation_sigma (on the device): the inverse of permutation_mapping -- (next_col, next_row), uint32[n_perm, 2^k]
+    each -> sigma values uint64[n_perm, 2^k, 4], sigma[c][r] = delta^next_col[c][r] * omega^next_row[c][r].  Raises ZgError
+    when an index is out of range."""
+    next_col = np.ascontiguousarray(next_col, dtype=np.uint32).reshape(-1, 1 << k)
+    next_row = np.ascontiguousarray(next_row, dtype=np.uint32).reshape(-1, 1 << k)
+    assert next_col.shape == next_row.shape
+    m = next_col.shape[0]
+    sigma = np.zeros((m, 1 << k, 4), np.uint64)
+    _check(ctx.lib.zg_permutation_sigma(ctx.h, c_uint32(k), c_uint32(m), _ptr(next_col), _ptr(next_row), _ptr(sigma)))
+    return sigma
+
+
+def fr_cube_root(which: int = 0) -> np.ndarray:
+    """zg_fr_cube_root: 0 = 7^((r-1)/3), the default coset generator; 1 = its square.  Montgomery limbs."""
+    out = np.zeros(4, np.uint64)
+    _check(load().zg_fr_cube_root(c_uint32(which), _ptr(out)))
+    return out
+
+
+KEY_FIXED_POLY, KEY_SIGMA_POLY, KEY_FIXED_COSET, KEY_SIGMA_COSET, KEY_L0, KEY_L_LAST, KEY_L_ACTIVE_ROW = range(7)
 
 
 def _check(status: int) -> None:
@@ -264,6 +289,16 @@ class Ctx:
 
     def sync(self):
         _check(self.lib.zg_ctx_sync(self.h))
+
+    def set_coset_generator(self, g_coset: np.ndarray):
+        """zg_ctx_set_coset_generator: g_coset of the extended-domain transforms on this context and of the provers created
+        on it from now on; one of the two fr_cube_root values, anything else raises ZgError."""
+        _check(self.lib.zg_ctx_set_coset_generator(self.h, _ptr(_fr(g_coset))))
+
+    def coset_generator(self) -> np.ndarray:
+        out = np.zeros(4, np.uint64)
+        _check(self.lib.zg_ctx_coset_generator(self.h, _ptr(out)))
+        return out
 
     def drop_workspace(self) -> int:
         """zg_ctx_trim: the free blocks of the workspace pool go back to the device allocator; returns the bytes freed"""
@@ -758,6 +793,25 @@ class Prover:
         sigma = np.zeros((c.n_perm_columns, 8), np.uint64)
         _check(self.ctx.lib.zg_prover_vk_commitments(self.h, _ptr(fixed), _ptr(sigma)))
         return fixed, sigma
+
+    def coset_generator(self) -> np.ndarray:
+        """zg_prover_coset_generator: g_coset of the proving key (the creating context's, when the key was made)."""
+        out = np.zeros(4, np.uint64)
+        _check(self.ctx.lib.zg_prover_coset_generator(self.h, _ptr(out)))
+        return out
+
+    def export_key(self, family: int, index: int = 0) -> np.ndarray:
+        """zg_prover_export_key: one array of what keygen_pk derived -- KEY_FIXED_POLY / KEY_SIGMA_POLY: uint64[2^k, 4]
+        coefficients; KEY_FIXED_COSET / KEY_SIGMA_COSET / KEY_L0 / KEY_L_LAST / KEY_L_ACTIVE_ROW: uint64[2^ext_k, 4] on
+        coset_generator() * <extended_omega>."""
+        c = self.image.c
+        count = self.n
+        if family not in (KEY_FIXED_POLY, KEY_SIGMA_POLY):
+            while count < self.n * (c.cs_degree - 1):
+                count *= 2
+        out = np.zeros((count, 4), np.uint64)
+        _check(self.ctx.lib.zg_prover_export_key(self.h, c_uint32(family), c_uint32(index), _ptr(out), c_size_t(count)))
+        return out
 
     def fetch(self, what: int, index: int, count: int, slot: int = 0) -> np.ndarray:
         out = np.zeros((count, 4), np.uint64)

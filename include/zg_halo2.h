@@ -236,14 +236,14 @@ int zg_intt_batch(zg_ctx *ctx, zg_fr *const *a, size_t batch, uint32_t log_n,
 int zg_ntt_batch_dev(zg_ctx *ctx, void *d_a, size_t stride_elems, size_t batch, uint32_t log_n,
                      const zg_fr *omega, const zg_fr *divisor);
 
-/* EvaluationDomain::coeff_to_extended: coefficient i is multiplied by zeta^(i mod 3)
- * (g_coset = Fr::ZETA), zero-padded from 2^k to 2^ext_k and transformed with extended_omega. */
+/* EvaluationDomain::coeff_to_extended: coefficient i is multiplied by g_coset^(i mod 3) (g_coset: the context's
+ * generator, zg_ctx_set_coset_generator), zero-padded from 2^k to 2^ext_k and transformed with extended_omega. */
 int zg_coeff_to_extended(zg_ctx *ctx, const zg_fr *coeffs, uint32_t k, uint32_t ext_k, zg_fr *out);
 int zg_coeff_to_extended_batch_dev(zg_ctx *ctx, const void *d_coeffs, size_t in_stride_elems,
                                    void *d_out, size_t out_stride_elems, size_t batch, uint32_t k,
                                    uint32_t ext_k);
 /* EvaluationDomain::extended_to_coeff: inverse transform on the extended domain, multiplication by
- * 2^-ext_k and by zeta^-(i mod 3), truncated to out_len (= n * quotient_poly_degree). evals is
+ * 2^-ext_k and by g_coset^-(i mod 3), truncated to out_len (= n * quotient_poly_degree). evals is
  * clobbered. */
 int zg_extended_to_coeff(zg_ctx *ctx, zg_fr *evals, uint32_t k, uint32_t ext_k, size_t out_len,
                          zg_fr *out);
@@ -252,6 +252,24 @@ int zg_extended_to_coeff_dev(zg_ctx *ctx, void *d_evals, uint32_t k, uint32_t ex
 
 /* The standard domain roots: omega = ROOT_OF_UNITY^(2^(28-log_n)) and its inverse. */
 int zg_domain_omega(uint32_t log_n, zg_fr *omega, zg_fr *omega_inv);
+
+/* ------------------------------------------------------------------ evaluation domain
+ * EvaluationDomain's extended coset is g_coset * <extended_omega>, with g_coset = <Fr as WithSmallOrderMulGroup<3>>::ZETA
+ * upstream: one of the TWO primitive cube roots of unity of Fr, each the other's square.  The library takes it as a
+ * parameter.  The DEFAULT is zg_fr_cube_root(0) = 7^((r-1)/3) = 0x...b99c90dd, because that is the value the golden vectors
+ * and the oracle were made with; whether upstream's literal is this one or its square (0x30644e72...36636f23) has not
+ * been verified against halo2curves here, so no constant in the source decides it: a shim passes
+ * <Fr as WithSmallOrderMulGroup<3>>::ZETA at run time.  Proof bytes do NOT depend on the
+ * choice (the quotient h is unique); what does are the arrays of the arithmetic-level entries -- zg_coeff_to_extended*,
+ * zg_extended_to_coeff*, zg_prover_evaluate_h, zg_prover_fetch(what = 0) and the extended families of
+ * zg_prover_export_key -- which a caller mixes with its own pk.fixed_cosets / l0 only under the same generator. */
+/* Host helper: which = 0: 7^((r-1)/3), the default; which = 1: its square.  Montgomery form. */
+int zg_fr_cube_root(uint32_t which, zg_fr *out);
+/* g_coset of this context: governs zg_coeff_to_extended* and zg_extended_to_coeff* on it (and on its side stream), and is
+ * captured by zg_prover_create*.  Accepts exactly the two primitive cube roots of unity; anything else (0, 1, 7, a value
+ * not below r) is ZG_ERR_INVALID_ARG and leaves the setting as it was.  Provers that already exist are not touched. */
+int zg_ctx_set_coset_generator(zg_ctx *ctx, const zg_fr *g_coset);
+int zg_ctx_coset_generator(zg_ctx *ctx, zg_fr *out);
 
 /* ------------------------------------------------------------------ circuit description
  * What halo2 keeps in `ConstraintSystem` + `ProvingKey` (halo2_proofs v2023_04_20
@@ -338,6 +356,21 @@ int zg_prover_create_shared(zg_ctx *ctx, const zg_circuit *circuit, const zg_fr 
  * batches. */
 int zg_prover_fork(const zg_prover *parent, zg_ctx *ctx, zg_prover **out);
 void zg_prover_destroy(zg_prover *p);
+/* g_coset of the prover's proving key: the generator of the context it was created on, at that time
+ * (zg_ctx_set_coset_generator).  A fork shares the key and so its generator, whatever its own context says; changing a
+ * context later changes no existing prover. */
+int zg_prover_coset_generator(const zg_prover *p, zg_fr *out);
+/* What keygen_pk derives (halo2_proofs src/plonk/keygen.rs: pk.fixed_polys / fixed_cosets, pk.permutation.polys / cosets,
+ * pk.l0 / l_last / l_active_row), copied from the prover's resident key to the host.  ZG_KEY_FIXED_POLY / ZG_KEY_SIGMA_POLY:
+ * [2^k] coefficients of fixed column / permutation column `index`; ZG_KEY_FIXED_COSET / ZG_KEY_SIGMA_COSET and ZG_KEY_L0 /
+ * ZG_KEY_L_LAST / ZG_KEY_L_ACTIVE_ROW (index 0): [2^ext_k] values.  Every array is in plain Montgomery form and halo2's
+ * order; the extended ones sit on the single coset g_coset * <extended_omega> of the prover's generator, whichever layout
+ * evaluate_h reads (split parts, 2^5-scaled nine-limb slabs, scaled sigma).  An index outside its family (any index of
+ * the sigma families of a circuit without permutation columns) is ZG_ERR_INVALID_ARG.  Works on forks; reads the key
+ * only, so a later proof is not disturbed.  The commitments are zg_prover_vk_commitments. */
+enum { ZG_KEY_FIXED_POLY = 0, ZG_KEY_SIGMA_POLY = 1, ZG_KEY_FIXED_COSET = 2, ZG_KEY_SIGMA_COSET = 3, ZG_KEY_L0 = 4,
+       ZG_KEY_L_LAST = 5, ZG_KEY_L_ACTIVE_ROW = 6 };
+int zg_prover_export_key(zg_prover *p, uint32_t family, uint32_t index, zg_fr *out, size_t cap_elems);
 
 /* Lock-step batches.  A prover has `max_batch` proof slots (1 after creation); zg_prover_prove_batch makes up to
  * that many proofs of the same circuit AT ONCE: every kernel launch of create_proof serves all of them (the
@@ -441,7 +474,7 @@ int zg_prover_enable_digit_tables(zg_prover *p, uint64_t max_bytes, uint64_t *by
  * coefficient forms upstream hands its evaluator -- advice_polys [n_advice][2^k], instance_polys [n_instance][2^k],
  * perm_z_polys [sets][2^k] (permutation::Committed product polys), lookup_z_polys [lookups][2^k] and permuted_polys
  * [2 * lookups][2^k] (a'_0, s'_0, a'_1, ...) -- and the challenges theta, beta, gamma, y; h_out receives h on
- * EvaluationDomain's extended coset, 2^ext_k values.  Host pointers (the arithmetic-level entry: ~60 MiB cross PCIe
+ * EvaluationDomain's extended coset (of the prover's generator, zg_prover_coset_generator), 2^ext_k values.  Host pointers (the arithmetic-level entry: ~60 MiB cross PCIe
  * at k = 14); slot 0 of the prover is used as scratch. */
 int zg_prover_evaluate_h(zg_prover *p, const zg_fr *advice_polys, const zg_fr *instance_polys, const zg_fr *perm_z_polys,
                          const zg_fr *lookup_z_polys, const zg_fr *permuted_polys, const zg_fr *theta, const zg_fr *beta,
@@ -549,6 +582,12 @@ int zg_prover_check_images(zg_prover *p, zg_witness_plan *plan, const uint8_t *i
  * ZG_ERR_INVALID_ARG when a value is no such product. */
 int zg_permutation_mapping(uint32_t k, uint32_t n_perm, const zg_fr *sigma_values, uint32_t *next_col,
                            uint32_t *next_row);
+/* The other direction, on the device: permutation::keygen::Assembly::build_pk's values (halo2_proofs
+ * src/plonk/permutation/keygen.rs), sigma_out[c][r] = delta^next_col[c][r] * omega^next_row[c][r] -- the exact inverse of
+ * zg_permutation_mapping, same [n_perm][2^k] layout, host pointers.  ZG_ERR_INVALID_ARG when a column index is >= n_perm
+ * or a row index >= 2^k.  The order-dependent merging of cycles (Assembly::copy) stays with the caller. */
+int zg_permutation_sigma(zg_ctx *ctx, uint32_t k, uint32_t n_perm, const uint32_t *next_col, const uint32_t *next_row,
+                         zg_fr *sigma_out);
 
 /* ------------------------------------------------------------------ verifier
  * Replaces halo2_proofs::plonk::verify_proof::<KZGCommitmentScheme<Bn256>, VerifierGWC, _, EvmTranscript,

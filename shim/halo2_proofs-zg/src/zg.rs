@@ -258,6 +258,10 @@ fn build_handle(params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Affine>) -> Option<
     let mut prover = std::ptr::null_mut();
     unsafe {
         check(zg_ctx_create(device(), &mut ctx)).ok()?;
+        // EvaluationDomain's g_coset as THIS build of halo2curves defines it: the library's default is one of the two
+        // primitive cube roots of unity and no constant on its side decides which one upstream's literal is
+        let g_coset: Fr = <Fr as ff::WithSmallOrderMulGroup<3>>::ZETA;
+        check(zg_ctx_set_coset_generator(ctx, &g_coset)).ok()?;
         check(zg_prover_create(ctx, &c, fixed.as_ptr(), sigma.as_ptr(), params.get_g().as_ptr(), params.g_lagrange.as_ptr(),
                                &vk_repr, &mut prover)).ok()?;
         Some(Handle { ctx, prover, proof_cap: zg_prover_proof_size(prover), n_advice: cs.num_advice_columns(), n, _flat: flat })
