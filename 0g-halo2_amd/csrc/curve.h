@@ -200,4 +200,16 @@ ZG_HD XYZZ xyzz_mul_raw(const Affine& p, const uint32_t k[8]) {
     return acc;
 }
 
+// k * P for a base in XYZZ form (a full addition per set bit): what a butterfly of the G1 transform multiplies is a sum
+// of earlier passes, not an affine point (g1_fft.hip)
+ZG_HD XYZZ xyzz_mul_raw_xyzz(const XYZZ& p, const uint32_t k[8]) {
+    XYZZ acc = xyzz_identity();
+    for (int i = 7; i >= 0; i--)
+        for (int b = 31; b >= 0; b--) {
+            acc = xyzz_dbl(acc);
+            if ((k[i] >> b) & 1) acc = xyzz_add(acc, p);
+        }
+    return acc;
+}
+
 }  // namespace zg

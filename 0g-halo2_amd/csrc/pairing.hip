@@ -231,7 +231,54 @@ Fq12 final_exp(const Fq12& f) {
     return f12_pow(t, HARD, 12);                // ^((p^4 - p^2 + 1)/r)
 }
 
+// affine group law on the twist (no line values): what the subgroup test of g2_point_fault walks
+G2 g2_dbl(const G2& t) {
+    if (t.inf || f2_is_zero(t.y)) return {f2_zero(), f2_zero(), true};
+    const Fq2 xx = f2_sqr(t.x);
+    const Fq2 lam = f2_mul(f2_add(f2_add(xx, xx), xx), f2_inv(f2_add(t.y, t.y)));
+    const Fq2 x3 = f2_sub(f2_sqr(lam), f2_add(t.x, t.x));
+    return {x3, f2_sub(f2_mul(lam, f2_sub(t.x, x3)), t.y), false};
+}
+G2 g2_add(const G2& t, const G2& q) {
+    if (q.inf) return t;
+    if (t.inf) return q;
+    if (f2_eq(t.x, q.x)) return f2_eq(t.y, q.y) ? g2_dbl(t) : G2{f2_zero(), f2_zero(), true};
+    const Fq2 lam = f2_mul(f2_sub(q.y, t.y), f2_inv(f2_sub(q.x, t.x)));
+    const Fq2 x3 = f2_sub(f2_sub(f2_sqr(lam), t.x), q.x);
+    return {x3, f2_sub(f2_mul(lam, f2_sub(t.x, x3)), t.y), false};
+}
+
+bool fq_canonical(const Fe& v) {
+    for (int i = 7; i >= 0; i--) {
+        if (v.l[i] < FqParams::p(i)) return true;
+        if (v.l[i] > FqParams::p(i)) return false;
+    }
+    return false;
+}
+
 }  // namespace
+
+// Is q a point a verifying key may hold -- canonical coordinates, on y^2 = x^3 + 3/(9+u), not the identity, and in the
+// subgroup of order r (the twist's cofactor is ~2^254: a point of the curve need not be)?  nullptr = yes, else why not.
+const char* g2_point_fault(const zg_g2_affine& q) {
+    G2 g;
+    std::memcpy(&g.x, &q.x, sizeof(Fq2));
+    std::memcpy(&g.y, &q.y, sizeof(Fq2));
+    g.inf = false;
+    if (!fq_canonical(g.x.c0) || !fq_canonical(g.x.c1) || !fq_canonical(g.y.c0) || !fq_canonical(g.y.c1))
+        return "a coordinate is not below q";
+    if (f2_is_zero(g.x) && f2_is_zero(g.y)) return "the identity";
+    const Fq2 xi = {Fq::from_u64(9), Fq::one()};
+    const Fq2 b = f2_mul_fq(f2_inv(xi), Fq::from_u64(3));
+    if (!f2_eq(f2_sqr(g.y), f2_add(f2_mul(f2_sqr(g.x), g.x), b))) return "not on the twist y^2 = x^3 + 3/(9+u)";
+    G2 acc = {f2_zero(), f2_zero(), true};  // r * Q, left to right over the bits of r
+    for (int i = 7; i >= 0; i--)
+        for (int bit = 31; bit >= 0; bit--) {
+            acc = g2_dbl(acc);
+            if ((FrParams::p(i) >> bit) & 1) acc = g2_add(acc, g);
+        }
+    return acc.inf ? nullptr : "outside the subgroup of order r";
+}
 
 // prod_i e(p_i, q_i) == 1; identities contribute 1
 bool pairing_product_is_one(const Affine* p, const zg_g2_affine* q, size_t n) {

@@ -126,7 +126,9 @@ enum {
     TAG_PERM_Z = 4,
     TAG_LOOKUP_Z = 5,
     TAG_RANDOM_POLY = 6,
-    TAG_VERIFY_BATCH = 7  // the verifier's batch weights r_b (verify.hip), not a blinding scalar
+    TAG_VERIFY_BATCH = 7,  // the verifier's batch weights r_b (verify.hip), not a blinding scalar
+    TAG_SRS_POWERS = 8,    // zg_params_check: the weights r_i of the powers relation (params.hip)
+    TAG_SRS_LAGRANGE = 9   // zg_params_check: the coefficients c_j of the Lagrange relation
 };
 inline Fe to_fe(const zg_fr* s) {
     Fe r;
@@ -137,6 +139,8 @@ inline Fe to_fe(const zg_fr* s) {
 Fe rand_fr_host(const uint32_t* key, uint32_t tag, uint64_t index);
 
 // ---- launch helpers (all asynchronous on ctx->stream) ----
+// out[i] = rand_fr(key, tag, i), i < count (Montgomery form): a vector of scalars drawn on the device under one key
+int poly_rand_fill(zg_ctx* ctx, const uint32_t key[8], uint32_t tag, Fe* out, uint32_t count);
 // Lock-step batches: `nb` proofs, proof b's scalars in pc[b], its arrays `*_bs` elements after proof b-1's.
 // The two draws a proof starts with: the vanishing argument's random polynomial (n values, to out and out2) and
 // the blinding rows [row0, row0 + nrows) of the ncols advice columns.

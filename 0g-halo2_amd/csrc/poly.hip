@@ -89,6 +89,22 @@ int poly_blind_rows2(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, Fe* base, s
     return ZG_OK;
 }
 
+struct RandKey {  // a ChaCha20 key passed by value in kernel arguments
+    uint32_t w[8];
+};
+__global__ void rand_fill_kernel(RandKey key, uint32_t tag, Fe* out, uint32_t count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) stg(out + i, rand_fr(key.w, tag, i));
+}
+int poly_rand_fill(zg_ctx* ctx, const uint32_t key[8], uint32_t tag, Fe* out, uint32_t count) {
+    if (count == 0) return ZG_OK;
+    RandKey rk;
+    memcpy(rk.w, key, sizeof(rk.w));
+    ZG_LAUNCH(ctx, "rand_fill", (double)count * 32, rand_fill_kernel, dim3((count + 255) / 256), dim3(256), 0, rk, tag, out, count);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
 // The two draws a proof starts with, in one launch: the vanishing argument's random polynomial (n values,
 // written to out and out2) and the blinding rows of the advice columns.  Proof b = blockIdx.y.
 __global__ void random_and_blind_kernel(const ProofConst* __restrict__ pc, Fe* out, size_t out_bs, Fe* out2, size_t out2_bs,

@@ -77,8 +77,12 @@ ABI_SYMBOLS = [
     "zg_prover_vk_commitments", "zg_verifier_create", "zg_verifier_destroy", "zg_verifier_verify_batch", "zg_pairing_check",
     "zg_prover_check_batch", "zg_prover_check_batch_dev", "zg_prover_check_images", "zg_permutation_mapping",
     "zg_fr_cube_root", "zg_ctx_set_coset_generator", "zg_ctx_coset_generator", "zg_prover_coset_generator",
-    "zg_permutation_sigma", "zg_prover_export_key",
+    "zg_permutation_sigma", "zg_prover_export_key", "zg_params_lagrange", "zg_params_lagrange_dev", "zg_params_check",
 ]
+
+# zg_params_check: bits of `failed`
+SRS_G1_MALFORMED, SRS_G1_IDENTITY, SRS_G2, SRS_POWERS, SRS_LAGRANGE = 1, 2, 4, 8, 16
+
 
 def tuning_names() -> list:
     """Names of the library's tuning knobs (include/zg_halo2.h, "tuning")."""
@@ -339,6 +343,38 @@ class Ctx:
 
     def params_new_dev(self, k: int, s: np.ndarray, d_g: int, d_gl: int):
         _check(self.lib.zg_params_new_dev(self.h, c_uint32(k), _ptr(_fr(s)), c_void_p(d_g), c_void_p(d_gl)))
+
+    def params_lagrange(self, k: int, g: np.ndarray) -> np.ndarray:
+        """zg_params_lagrange: g_to_lagrange of the FIRST 2^k points of g (uint64[>= 2^k, 8]) -> g_lagrange uint64[2^k, 8].
+        No scalar is needed; a larger SRS is downsized by passing it as it is."""
+        n = 1 << k
+        g = np.ascontiguousarray(np.asarray(g).reshape(-1, 8)[:n], dtype=np.uint64)
+        assert g.shape[0] == n, f"{g.shape[0]} points for k = {k}"
+        gl = np.zeros((n, 8), np.uint64)
+        _check(self.lib.zg_params_lagrange(self.h, c_uint32(k), _ptr(g), _ptr(gl)))
+        return gl
+
+    def params_lagrange_dev(self, k: int, d_g: int, d_gl: int):
+        """zg_params_lagrange_dev: device addresses (2^k * 64 B each, distinct); asynchronous on the context stream."""
+        _check(self.lib.zg_params_lagrange_dev(self.h, c_uint32(k), c_void_p(d_g), c_void_p(d_gl)))
+
+    def params_check(self, k: int, g: np.ndarray, g_lagrange, g2: np.ndarray, s_g2: np.ndarray, key):
+        """zg_params_check: is (g, g_lagrange or None, g2, s_g2) a structured reference string of 2^k points?
+        -> (verdict, failed): verdict 1 = accepted; failed = SRS_* bits saying why not (zg_last_error names the first
+        offending point).  key: 32 bytes from a CSPRNG (an int in tests, as rng_key).  g[0] need not be the generator."""
+        n = 1 << k
+        g = np.ascontiguousarray(np.asarray(g).reshape(-1, 8), dtype=np.uint64)
+        assert g.shape[0] == n, f"{g.shape[0]} points for k = {k}"
+        gl = None
+        if g_lagrange is not None:
+            gl = np.ascontiguousarray(np.asarray(g_lagrange).reshape(-1, 8), dtype=np.uint64)
+            assert gl.shape[0] == n, f"{gl.shape[0]} Lagrange points for k = {k}"
+        g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
+        s_g2 = np.ascontiguousarray(s_g2, dtype=np.uint64).reshape(16)
+        verdict, failed = c_int(-1), c_uint32(0)
+        _check(self.lib.zg_params_check(self.h, c_uint32(k), _ptr(g), _ptr(gl) if gl is not None else None, _ptr(g2),
+                                        _ptr(s_g2), rng_key(key), ctypes.byref(verdict), ctypes.byref(failed)))
+        return verdict.value, failed.value
 
     # ---- MSM ----
     def set_msm_latency(self, latency: bool):

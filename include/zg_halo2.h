@@ -43,6 +43,8 @@ typedef struct { uint64_t l[4]; } zg_fr;
 typedef struct { uint64_t l[4]; } zg_fq;
 typedef struct { zg_fq x, y; } zg_g1_affine;
 typedef struct { zg_fq x, y, z; } zg_g1;
+typedef struct { zg_fq c0, c1; } zg_fq2;        /* c0 + c1 u, u^2 = -1 (bn256::Fq2)                          */
+typedef struct { zg_fq2 x, y; } zg_g2_affine;   /* bn256::G2Affine on y^2 = x^3 + 3/(9+u); (0,0) = identity */
 
 typedef struct zg_ctx zg_ctx;       /* one GPU: stream, workspace, twiddle cache        */
 typedef struct zg_bases zg_bases;   /* HBM-resident base set (ParamsKZG::g / g_lagrange) */
@@ -219,6 +221,44 @@ int zg_g1_sum(const zg_g1 *parts, size_t count, zg_g1 *out);
  * OsRng; here the caller supplies it so that runs are reproducible. */
 int zg_params_new(zg_ctx *ctx, uint32_t k, const zg_fr *s, zg_g1_affine *g, zg_g1_affine *g_lagrange);
 int zg_params_new_dev(zg_ctx *ctx, uint32_t k, const zg_fr *s, void *d_g, void *d_g_lagrange);
+
+/* halo2_proofs::poly::kzg::commitment: g_to_lagrange(g[..2^k], k), as ParamsKZG::downsize and
+ * ParamsKZG::from_parts-style imports use it: best_fft over G1 with omega_inv, then * 2^-k.
+ * Reads the FIRST 2^k points of g (so a larger SRS is downsized by passing its prefix);
+ * writes 2^k affine points, identity = (0,0).  No scalar is needed.
+ * k <= 24 (else ZG_ERR_UNSUPPORTED).  The result is bit-exact: canonical affine Montgomery coordinates, whatever the
+ * order of the additions.  The input may hold identities and repeated points: this is a transform, not a validation
+ * (points off the curve give points off the curve; zg_params_check is the validation).  The _dev form takes device
+ * pointers (2^k * 64 B each; d_g == d_g_lagrange is ZG_ERR_INVALID_ARG), is asynchronous on the context stream like
+ * every _dev entry, and its output can go straight into zg_bases_register_dev. */
+int zg_params_lagrange(zg_ctx *ctx, uint32_t k, const zg_g1_affine *g, zg_g1_affine *g_lagrange);
+int zg_params_lagrange_dev(zg_ctx *ctx, uint32_t k, const void *d_g, void *d_g_lagrange);
+
+/* Is this an SRS?  *verdict = 1 accepted / 0 rejected; *failed = why (ZG_SRS_* bits below, 0 when accepted).
+ * g: 2^k points, g_lagrange: 2^k points or NULL (then ZG_SRS_LAGRANGE is not evaluated), g2 / s_g2: ParamsVerifierKZG's.
+ *   ZG_SRS_G1_MALFORMED  a G1 coordinate's limbs are not below q, or a point is off y^2 = x^3 + 3 (g or g_lagrange;
+ *                        an identity in g_lagrange is a point of the curve)
+ *   ZG_SRS_G1_IDENTITY   some g[i] is the identity
+ *   ZG_SRS_G2            g2 or s_g2 is non-canonical, off the twist, the identity, or outside the r-torsion (r Q != inf)
+ *   ZG_SRS_POWERS        g is no geometric sequence under s_g2: with r_i = rand_fr(key, TAG_SRS_POWERS, i), i < 2^k - 1,
+ *                        A = sum r_i g[i] and B = sum r_i g[i+1] (one MSM batch over one base set),
+ *                        e(B, g2) e(-A, s_g2) != 1.  k = 0 has no such relation and passes it.
+ *   ZG_SRS_LAGRANGE      g_lagrange is not the Lagrange basis of g: with c_j = rand_fr(key, TAG_SRS_LAGRANGE, j) and
+ *                        e = the evaluations of sum c_j X^j on the domain (device NTT), sum e_i g_lagrange[i] != sum c_j g[j]
+ * The first three are decided point by point, and zg_last_error() names the first offending index; the two relations are
+ * evaluated, each on its own, only when those three are clear.  The scalars are drawn on the device, as the prover's
+ * blinding rows are; the base sets the check registers are freed before it returns; the pairing runs on the host after
+ * the context lock is released.  k <= 22 (what a base set holds), else ZG_ERR_UNSUPPORTED.
+ * `key` MUST come from the caller's CSPRNG: whoever made the file and knows the key can choose errors that cancel in the
+ * weighted sums.  What the check does NOT do: it does not require g[0] to be the curve generator (a ceremony may start
+ * from another point, and the verifier takes g0 as an argument anyway), and it does not replace the verification of a
+ * ceremony's own transcript -- it says that the file is A structured reference string, not whose.
+ * Returns the zg_status of the call itself: a rejected SRS is not an error of the call. */
+enum { ZG_SRS_G1_MALFORMED = 1, ZG_SRS_G1_IDENTITY = 2, ZG_SRS_G2 = 4, ZG_SRS_POWERS = 8, ZG_SRS_LAGRANGE = 16 };
+int zg_params_check(zg_ctx *ctx, uint32_t k, const zg_g1_affine *g,
+                    const zg_g1_affine *g_lagrange /* may be NULL */,
+                    const zg_g2_affine *g2, const zg_g2_affine *s_g2,
+                    const uint8_t key[32], int *verdict, uint32_t *failed);
 
 /* ------------------------------------------------------------------ NTT
  * Replaces halo2_proofs::arithmetic::best_fft and the EvaluationDomain wrappers
@@ -596,8 +636,6 @@ int zg_permutation_sigma(zg_ctx *ctx, uint32_t k, uint32_t n_perm, const uint32_
  * (/root/reference/src/wnn.rs:265-280), for a batch of proofs of one circuit.  The proofs' transcripts are replayed
  * and their opening terms multiplied out on the device; a random linear combination reduces the batch to one
  * two-pairing check on the host (DESIGN.md section "Verification"). */
-typedef struct { zg_fq c0, c1; } zg_fq2;        /* c0 + c1 u, u^2 = -1 (bn256::Fq2)                          */
-typedef struct { zg_fq2 x, y; } zg_g2_affine;   /* bn256::G2Affine on y^2 = x^3 + 3/(9+u); (0,0) = identity */
 typedef struct zg_verifier zg_verifier;
 
 /* keygen_vk's commitments (halo2_proofs src/plonk/keygen.rs: params.commit_lagrange of each fixed column and each
