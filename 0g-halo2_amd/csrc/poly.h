@@ -67,6 +67,7 @@ struct alignas(16) ProofConst {
     Fe v;                       // GWC's v
     Fe points[PC_MAX_POINTS];   // opening points x * omega^rotation, by slot
     Fe subs[PC_MAX_POINTS];     // eval_batch of GWC point set s
+    Fe fold_w;                  // a proof of several circuits: the weight of this slot's quotient in the proof's (poly_fold_slots)
 };
 
 struct EvalHArgs {
@@ -210,6 +211,14 @@ struct FeSet {  // a few field elements passed by value in kernel arguments
 int poly_horner_combine_sets(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, uint32_t nb, const uint32_t* d_lists,
                              uint32_t list_stride, const uint32_t* counts, uint32_t nsets, Fe* out, size_t out_stride,
                              size_t out_bs, uint32_t n);
+// A proof of several circuit instances (create_proof's `circuits` slice; the slots are the circuits, pc[0] the proof's scalars):
+// h[i] <- sum_c pc[c].fold_w * h[c * h_bs + i], i < len, c < nb <= FOLD_MAX_SLOTS
+constexpr uint32_t FOLD_MAX_SLOTS = 64;
+int poly_fold_slots(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, Fe* h, size_t h_bs, uint32_t len);
+// GWC: set s = Horner in pc[0].v over d_lists[firsts[s] .. + counts[s]) (entry = slot << 16 | polynomial index, any
+// length), minus pc[0].subs[s] at X^0; out + s * out_stride
+int poly_combine_pairs(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, const uint32_t* d_lists, const uint32_t* firsts,
+                       const uint32_t* counts, uint32_t nsets, Fe* out, size_t out_stride, uint32_t n);
 // kate_division of `nsets` polynomials per proof: a + b * a_bs + s * a_stride divided by (X - pc[b].points[slot[s]])
 size_t poly_kate_tmp_elems(uint32_t n, uint32_t batch);
 int poly_kate_division(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const uint32_t* slots, uint32_t nsets, const Fe* a,

@@ -1339,6 +1339,112 @@ int poly_horner_combine_sets(zg_ctx* ctx, const PolySet& polys, const ProofConst
     return ZG_OK;
 }
 
+// ------------------------------------------------------------------ proofs of several circuit instances
+// (create_proof's `circuits` slice: the slots of a lock-step batch are the circuits of ONE proof, prove_batch.hip)
+//
+// The quotient of the whole proof from the slots' own: h[0][i] <- sum_c pc[c].fold_w * h[c][i], one part of the extended
+// domain per launch.  A streaming kernel -- nb * 32 B read and 32 B written per row -- in the lazy-sum form: nb products
+// of 81 multiply-adds and ONE Montgomery reduction per row (Dot9), the weights unpacked once per workgroup.  The rows may
+// be in the nine-limb kernel's 2^5-scaled packed form: the sum is linear, so a plain weight keeps whatever form they have.
+__global__ __launch_bounds__(256) void fold_slots_kernel(const ProofConst* __restrict__ pc, uint32_t nb, Fe* __restrict__ h, size_t h_bs,
+                                                         uint32_t len) {
+    __shared__ F9 w9[FOLD_MAX_SLOTS];
+    if (threadIdx.x < nb) w9[threadIdx.x] = f9_unpack(Fr::mul(pc[threadIdx.x].fold_w, Fr9Params::c261_fe()));
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    Dot9<Fr9Params> acc;
+    acc.zero();
+    uint32_t c = 0;
+    for (; c + 3 <= nb; c += 3) {
+        const Fe h0 = ldg(h + (size_t)c * h_bs + i), h1 = ldg(h + (size_t)(c + 1) * h_bs + i), h2 = ldg(h + (size_t)(c + 2) * h_bs + i);
+        acc.mac(f9_unpack(h0), w9[c]);
+        acc.mac(f9_unpack(h1), w9[c + 1]);
+        acc.mac(f9_unpack(h2), w9[c + 2]);
+        acc.carry();
+    }
+    for (; c < nb; c++) {
+        acc.mac(ld9(h + (size_t)c * h_bs + i), w9[c]);
+        acc.carry();
+    }
+    stg(h + i, f9_reduce_pack<Fr9Params>(acc.reduce()));
+}
+
+int poly_fold_slots(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, Fe* h, size_t h_bs, uint32_t len) {
+    if (nb <= 1 || !len) return ZG_OK;
+    ZG_REQUIRE(nb <= FOLD_MAX_SLOTS, ZG_ERR_UNSUPPORTED, "poly_fold_slots: %u circuits in one proof (max %u)", nb, FOLD_MAX_SLOTS);
+    ZG_LAUNCH(ctx, "fold_slots", (double)(nb + 1) * len * 32, fold_slots_kernel, dim3((len + 255) / 256), dim3(256), 0, pc, nb, h, h_bs,
+              len);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+// GWC over (circuit, polynomial) pairs: set s = blockIdx.y is Horner in pc[0].v over the entries lists[first[s] ..
+// first[s] + count[s]) -- entry = slot << 16 | polynomial index -- minus pc[0].subs[s] at X^0, to out + s * out_stride.
+// A list has no bound: it is taken in chunks of HC9_MAX terms, each one dot product against the table of v's powers
+// (one reduction per chunk, as combine9_kernel), and the chunks are chained by one product with v^HC9_MAX.  The first
+// chunk is the short one, so every later chunk is whole.
+struct PairSets {
+    uint32_t first[HC_MAX_SETS], count[HC_MAX_SETS];
+};
+__global__ __launch_bounds__(256) void combine_pairs_kernel(PolySet ps, const ProofConst* __restrict__ pc,
+                                                            const uint32_t* __restrict__ lists, PairSets sets, Fe* __restrict__ out,
+                                                            size_t out_stride, uint32_t n) {
+    __shared__ F9 vp[HC9_MAX];
+    __shared__ Fe v_chunk;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+    if (threadIdx.x < HC9_MAX) vp[threadIdx.x] = f9_unpack(Fr::mul(Fr::pow_u64(pc[0].v, threadIdx.x), Fr9Params::c261_fe()));
+    if (threadIdx.x == HC9_MAX) v_chunk = Fr::pow_u64(pc[0].v, HC9_MAX);
+    __syncthreads();
+    if (i >= n) return;
+    const uint32_t* list = lists + sets.first[s];
+    const uint32_t count = sets.count[s];
+    auto at = [&](uint32_t j) {
+        const uint32_t e = list[j];
+        return poly_of(ps, e & 0xffffu, e >> 16) + i;
+    };
+    Fe r = fe_zero();
+    uint32_t chunk = count % HC9_MAX ? count % HC9_MAX : HC9_MAX;
+    for (uint32_t j0 = 0; j0 < count; j0 += chunk, chunk = HC9_MAX) {
+        Dot9<Fr9Params> acc;
+        acc.zero();
+        uint32_t t = 0;
+        for (; t + 3 <= chunk; t += 3) {
+            const Fe p0 = ldg(at(j0 + t)), p1 = ldg(at(j0 + t + 1)), p2 = ldg(at(j0 + t + 2));
+            acc.mac(f9_unpack(p0), vp[chunk - 1 - t]);
+            acc.mac(f9_unpack(p1), vp[chunk - 2 - t]);
+            acc.mac(f9_unpack(p2), vp[chunk - 3 - t]);
+            acc.carry();
+        }
+        for (; t < chunk; t++) {
+            acc.mac(f9_unpack(ldg(at(j0 + t))), vp[chunk - 1 - t]);
+            acc.carry();
+        }
+        const Fe part = f9_reduce_pack<Fr9Params>(acc.reduce());
+        r = j0 ? Fr::add(Fr::mul(r, v_chunk), part) : part;
+    }
+    if (i == 0) r = Fr::sub(r, pc[0].subs[s]);
+    stg(out + (size_t)s * out_stride + i, r);
+}
+
+int poly_combine_pairs(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, const uint32_t* d_lists, const uint32_t* firsts,
+                       const uint32_t* counts, uint32_t nsets, Fe* out, size_t out_stride, uint32_t n) {
+    if (!nsets) return ZG_OK;
+    ZG_REQUIRE(nsets <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "poly_combine_pairs: %u sets", nsets);
+    PairSets sets;
+    memset(&sets, 0, sizeof(sets));
+    double total = 0;
+    for (uint32_t s = 0; s < nsets; s++) {
+        sets.first[s] = firsts[s];
+        sets.count[s] = counts[s];
+        total += counts[s] + 1;
+    }
+    ZG_LAUNCH(ctx, "combine_pairs", total * n * 32, combine_pairs_kernel, dim3((n + 255) / 256, nsets), dim3(256), 0, polys, pc,
+              d_lists, sets, out, out_stride, n);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
 // kate_division: q_i = a_{i+1} + z q_{i+1} (i = n-2 .. 0, q_{n-1} = 0) -- upstream's one-core recurrence.  Strip form,
 // one workgroup per polynomial: lane l owns the strip [l S, (l + 1) S) of coefficients, S = n / lanes.
 //   pass A   the strip's own contribution at its first element, H_l = sum_{i in strip} a_{i+1} z^(i - l S) (Horner,

@@ -214,6 +214,13 @@ struct ProveBatch {
     zg_ctx* ctx;
     hipStream_t st;
     uint32_t nb, n, k, ek, bf, usable, A, I, P, NL, S, Q;
+    // A proof of SEVERAL circuit instances (create_proof's `circuits` slice, zg_prover_prove_multi): the nb slots are the
+    // circuits and there is ONE transcript, tr[0]; after every squeeze the same challenges go into every slot's scalars.
+    // The slots meet in three places: the transcript's order (the absorb halves), the quotient (fold_quotients: one h,
+    // one set of pieces) and the multiopen argument (lists over (circuit, polynomial) pairs, one W per point set).
+    // What the proof holds once -- h and its pieces, the openings -- is computed for `nq` = 1 slot, and `ntr` = 1.
+    bool multi = false;
+    uint32_t ntr, nq;
     bool hat;
     bool split;         // extended-domain parts of this proof: the split pair in the throughput configuration, the single coset otherwise
     bool phase_cosets;  // the coset forms of a phase's columns: on the side stream while that phase's commitments run (latency
@@ -236,7 +243,7 @@ struct ProveBatch {
     Cols base_cols;
     std::vector<Jac> random_commit;
     bool have_random = false;
-    struct Q1 { uint32_t poly, slot; };
+    struct Q1 { uint32_t poly, slot; bool shared; uint32_t at; };  // (multi: taken once, from slot 0; `at`: its place in a slot's row of evaluations)
     std::vector<int32_t> rots;  // distinct opening points, in any order (the powers table is indexed by slot)
     std::vector<Q1> evq;
     size_t e_fixed = 0, e_random = 0, e_sigma = 0, e_pz = 0, e_lk = 0, e_written = 0, e_h = 0;
@@ -246,8 +253,10 @@ struct ProveBatch {
     uint32_t* h_err = nullptr;  // the lookups' error words on the host
     uint32_t prod_per = 0;      // commitments per proof of the products phase (the random polynomial rides there without lookups)
     uint32_t nsets = 0;         // opening point sets: list of set s at lists[s * 512 ..], its evaluation indices in list order
-    std::vector<uint32_t> lists, counts, set_slot;
-    std::vector<std::vector<size_t>> set_evs;
+    std::vector<uint32_t> lists, counts, set_slot, firsts;  // (multi: the lists follow each other, set s from firsts[s])
+    struct EvRef { uint32_t circuit; size_t ev; };          // an evaluation of the proof: evq index `ev` of a circuit (multi)
+    std::vector<std::vector<EvRef>> set_evs;
+    uint32_t n_per = 0;  // multi: evaluations per circuit; the shared ones follow them in slot 0's row
     // ---- the gate (run())
     enum Wait { W_ADVICE, W_PERMUTED, W_PRODUCTS, W_QUOTIENT, W_EVALS, W_GWC };
     bool gated = false, armed = false;
@@ -262,10 +271,12 @@ struct ProveBatch {
 #endif
 
     ProveBatch(zg_prover* p_, size_t count, const zg_fr* const* advice_host_, void* const* advice_dev_, const zg_fr* const* instance_,
-               size_t instance_len_, const uint8_t* keys_, uint8_t* const* proofs_, size_t proof_cap_, size_t* proof_lens_, int* statuses_)
+               size_t instance_len_, const uint8_t* keys_, uint8_t* const* proofs_, size_t proof_cap_, size_t* proof_lens_, int* statuses_,
+               bool multi_ = false)
         : p(p_), advice_host(advice_host_), advice_dev(advice_dev_), instance(instance_), instance_len(instance_len_), keys(keys_),
           proofs(proofs_), proof_cap(proof_cap_), proof_lens(proof_lens_), statuses(statuses_), pk(*p_->pk), ctx(p_->ctx),
-          st(p_->ctx->stream), nb((uint32_t)count), tr(count), status(count, ZG_OK) {
+          st(p_->ctx->stream), nb((uint32_t)count), multi(multi_), ntr(multi_ ? 1u : (uint32_t)count), nq(ntr), tr(ntr),
+          status(count, ZG_OK) {
         n = pk.n; k = pk.k; ek = pk.ext_k; bf = pk.bf; usable = pk.usable;
         A = pk.A; I = pk.I; P = pk.P; NL = pk.NL; S = pk.sets; Q = pk.qpd;
         hat = pk.hat;
@@ -285,6 +296,11 @@ struct ProveBatch {
     }
 
     Fe* pp_at(uint32_t ix) const { return p->pp + (size_t)(ix - p->nsh) * n; }  // proof 0's polynomial ix (>= nsh)
+    EvmTranscript& T(uint32_t b) { return tr[multi ? 0 : b]; }                  // the transcript slot b writes into
+    // a challenge into every slot's scalars: each proof's own, or the one proof's for all its circuits
+    void squeeze_into(Fe ProofConst::*field) {
+        for (uint32_t b = 0; b < nb; b++) p->hpc[b].*field = b < ntr ? tr[b].squeeze() : p->hpc[0].*field;
+    }
     void lap(int slot) {
         auto now = clk::now();
         p->phase_ms[slot] = std::chrono::duration<double, std::milli>(now - t_prev).count();
@@ -304,11 +320,11 @@ struct ProveBatch {
     }
     // the commitments of a phase: `per` scalar vectors per proof (`stride` apart, proof b's `outer` after proof b-1's), all
     // against `bases` in their plain form unless the caller says otherwise
-    MsmJob phase_msm(const zg_bases* bases, const Fe* scalars, size_t stride, size_t per, size_t outer) const {
+    MsmJob phase_msm(const zg_bases* bases, const Fe* scalars, size_t stride, size_t per, size_t outer, uint32_t slots = 0) const {
         MsmJob m;
         m.bases = bases; m.split = per;
         m.scalars = scalars; m.stride = stride; m.per = per; m.outer = outer;
-        m.batch = (size_t)nb * per;
+        m.batch = (size_t)(slots ? slots : nb) * per;
         return m;
     }
     // two-level layouts of the transforms: `per` arrays per proof
@@ -477,7 +493,7 @@ struct ProveBatch {
         for (uint32_t b = 0; b < nb; b++) {
             memset(&p->hpc[b], 0, sizeof(ProofConst));
             memcpy(p->hpc[b].key, keys + 32 * (size_t)b, 32);
-            tr[b].common_scalar(pk.vk_repr);
+            if (b < ntr) tr[b].common_scalar(pk.vk_repr);
         }
         ZG_TRY(upload_consts(p, nb));
         // vanishing::Argument::commit's random polynomial depends on no challenge: generate it now and
@@ -494,7 +510,7 @@ struct ProveBatch {
                 p->inst_filled[b] = instance_len;
                 for (uint32_t c = 0; c < I; c++) {
                     const zg_fr* src = instance_len ? instance[b] + (size_t)c * instance_len : nullptr;
-                    for (size_t i = 0; i < instance_len; i++) tr[b].common_scalar(to_fe(&src[i]));
+                    for (size_t i = 0; i < instance_len; i++) T(b).common_scalar(to_fe(&src[i]));
                     if (instance_len) ZG_TRY(h2d(p, iv + (size_t)c * n, src, instance_len * 32));
                 }
             }
@@ -527,9 +543,9 @@ struct ProveBatch {
             ZG_TRY(wait_points(p, (size_t)nb * A, pts, W_ADVICE));
             ZG_TICK("advice: points on the host");
             for (uint32_t b = 0; b < nb; b++)
-                for (uint32_t c = 0; c < A; c++) tr[b].write_point(pts[(size_t)b * A + c]);
+                for (uint32_t c = 0; c < A; c++) T(b).write_point(pts[(size_t)b * A + c]);
         }
-        for (uint32_t b = 0; b < nb; b++) p->hpc[b].theta = tr[b].squeeze();
+        squeeze_into(&ProofConst::theta);
         ZG_TICK("theta");
         ZG_TRY(publish());
         ZG_TICK("theta uploaded");
@@ -586,16 +602,18 @@ struct ProveBatch {
             for (uint32_t b = 0; b < nb; b++) {
                 for (uint32_t l = 0; l < NL; l++)
                     if (h_err[b * NL + l] && status[b] == ZG_OK) {
-                        set_error("zg_prover_prove: lookup %u of proof %u has an input outside its table (ConstraintSystemFailure)", l, b);
+                        set_error("zg_prover_prove: lookup %u of %s %u has an input outside its table (ConstraintSystemFailure)", l,
+                                  multi ? "circuit" : "proof", b);
                         status[b] = ZG_ERR_CONSTRAINT;
+                        if (multi) status[0] = ZG_ERR_CONSTRAINT;  // (the one proof fails, as upstream's `?` does)
                     }
                 const Jac* q = &pts[(size_t)b * (2 * NL + 1)];
-                for (uint32_t i = 0; i < 2 * NL; i++) tr[b].write_point(q[i]);
+                for (uint32_t i = 0; i < 2 * NL; i++) T(b).write_point(q[i]);
                 random_commit[b] = q[2 * NL];
             }
             have_random = true;
-            if (nb == 1 && status[0] != ZG_OK && gate_failed()) return ZG_ERR_HIP;  // (error words from behind a failed gate: run() re-makes the proof)
-            if (nb == 1 && status[0] != ZG_OK) {  // a lone proof stops here, as upstream's `?` does
+            if (ntr == 1 && status[0] != ZG_OK && gate_failed()) return ZG_ERR_HIP;  // (error words from behind a failed gate: run() re-makes the proof)
+            if (ntr == 1 && status[0] != ZG_OK) {  // a lone proof stops here, as upstream's `?` does
                 open_gate();  // (whatever was queued ahead runs out on stale scalars: nobody reads its results)
                 (void)prover_drain(p);
                 if (statuses) statuses[0] = status[0];
@@ -604,10 +622,8 @@ struct ProveBatch {
                 return status[0];
             }
         }
-        for (uint32_t b = 0; b < nb; b++) {
-            p->hpc[b].beta = tr[b].squeeze();
-            p->hpc[b].gamma = tr[b].squeeze();
-        }
+        squeeze_into(&ProofConst::beta);
+        squeeze_into(&ProofConst::gamma);
         ZG_TICK("beta, gamma");
         ZG_TRY(publish());
         ZG_TICK("beta, gamma uploaded");
@@ -665,23 +681,45 @@ struct ProveBatch {
         if (mb) {
             ZG_TRY(wait_points(p, (size_t)nb * prod_per, pts, W_PRODUCTS));
             ZG_TICK("products: points on the host");
-            for (uint32_t b = 0; b < nb; b++) {
-                const Jac* q = &pts[(size_t)b * prod_per];
-                for (uint32_t i = 0; i < mb; i++) tr[b].write_point(q[i]);
-                if (!have_random) random_commit[b] = q[mb];
-            }
+            // (a slot's commitments are [S permutation z | NL lookup z]; the proof of several circuits writes the two families
+            //  as two passes over the circuits, as upstream commits them)
+            for (uint32_t pass = 0; pass < (multi ? 2u : 1u); pass++)
+                for (uint32_t b = 0; b < nb; b++) {
+                    const Jac* q = &pts[(size_t)b * prod_per];
+                    const uint32_t i0 = multi && pass ? S : 0, i1 = multi && !pass ? S : mb;
+                    for (uint32_t i = i0; i < i1; i++) T(b).write_point(q[i]);
+                    if (!have_random) random_commit[b] = q[mb];
+                }
         } else if (!have_random) {
             ZG_TRY(wait_points(p, nb, pts, W_PRODUCTS));
             for (uint32_t b = 0; b < nb; b++) random_commit[b] = pts[b];
         }
         have_random = true;
-        for (uint32_t b = 0; b < nb; b++) tr[b].write_point(random_commit[b]);
-        for (uint32_t b = 0; b < nb; b++) evalh_consts(p->hpc[b], tr[b].squeeze(), pk);
+        for (uint32_t b = 0; b < ntr; b++) tr[b].write_point(random_commit[b]);  // (multi: ONE random polynomial, slot 0's, from key 0)
+        Fe y{};
+        for (uint32_t b = 0; b < nb; b++) {
+            if (b < ntr) y = tr[b].squeeze();
+            evalh_consts(p->hpc[b], y, pk);
+        }
+        if (multi) fold_weights(y);
         ZG_TICK("y");
         ZG_TRY(publish());
         ZG_TICK("y uploaded");
         lap(2);
         return ZG_OK;
+    }
+
+    // multi: the weights of the slots' quotients in the proof's.  upstream's evaluate_h carries its Horner value in y from
+    // one circuit into the next, so with m terms per circuit (gates, permutation, 5 per lookup) and h_c the quotient of
+    // circuit c alone, h = sum_c y^(m (N - 1 - c)) h_c: Horner in Y = y^m over the circuits, circuit 0 first.
+    void fold_weights(const Fe& y) {
+        const uint32_t m = pk.dc.n_gates + (S ? 2 + (S - 1) + S : 0) + 5 * NL;
+        const Fe Y = Fr::pow_u64(y, m);
+        Fe w = Fr::one();
+        for (uint32_t c = nb; c-- > 0;) {
+            p->hpc[c].fold_w = w;
+            w = Fr::mul(w, Y);
+        }
     }
 
     int quotient_queue() {
@@ -694,13 +732,17 @@ struct ProveBatch {
             const EvalHArgs a = evalh_args(p, di);
             ZG_TRY(poly_evaluate_h(ctx, a, pk.dom[di].en, nb, A + I + pk.F, (double)((size_t)1 << ek) * ((double)pk.dom[di].en / parts_en)));
         }
+        // multi: the slots' quotients into slot 0's, on each part, BEFORE the transforms back: those, the pieces and their
+        // commitments then exist once (nq = 1)
+        if (multi)
+            for (uint32_t di = dlo; di < dhi; di++) ZG_TRY(poly_fold_slots(ctx, p->d_pc, nb, p->dbuf[di].h, pk.dom[di].en, pk.dom[di].en));
         p->have_last = true;
         p->last_split = split;
         p->last_nb = nb;
-        const double ext_inv_unit = (double)nb * 2.0 * (double)((size_t)1 << ek) * 32.0;  // (ext -> coeff, 2 * 8n * 32 B)
+        const double ext_inv_unit = (double)nq * 2.0 * (double)((size_t)1 << ek) * 32.0;  // (ext -> coeff, 2 * 8n * 32 B)
         if (!split) {
             ctx->unit_next = ext_inv_unit;
-            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[0].h, ek, (size_t)Q * n, pp_at(p->ix_hpiece), hat, pk.zeta, nb, pk.dom[0].en, pp_bs));
+            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[0].h, ek, (size_t)Q * n, pp_at(p->ix_hpiece), hat, pk.zeta, nq, pk.dom[0].en, pp_bs));
         } else {
             // h = A + (X^L1 - c1) B:  A (degree < L1) from the first coset, where X^L1 = c1 = shift1^L1;  B (degree < L2)
             // from the second, where X^L1 = c2 and X^L2 = e are constants too:  B = (h - A) / (c2 - c1) there, with A
@@ -713,18 +755,18 @@ struct ProveBatch {
             const size_t tb = (size_t)3 * L2;
             Fe *fold = p->split_tmp, *a2 = fold + L2, *bc = a2 + L2;
             ctx->unit_next = ext_inv_unit;  // (the three transforms of the split form stand for ONE extended_to_coeff)
-            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[1].h, d1.ek, L1, hp, hat, zeta, nb, L1, pp_bs));  // A, in place of the low pieces
-            ZG_TRY(poly_fold(ctx, nb, hp, pp_bs, L2, L1 / L2, e, fold, tb));                       // A mod (X^L2 - e)
+            ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[1].h, d1.ek, L1, hp, hat, zeta, nq, L1, pp_bs));  // A, in place of the low pieces
+            ZG_TRY(poly_fold(ctx, nq, hp, pp_bs, L2, L1 / L2, e, fold, tb));                       // A mod (X^L2 - e)
             ctx->unit_next = 0.0;
-            ZG_TRY(coeff_to_coset_dev(ctx, fold, tb, L2, a2, tb, nb, d2.ek, false, zeta2));            // A on the second coset
+            ZG_TRY(coeff_to_coset_dev(ctx, fold, tb, L2, a2, tb, nq, d2.ek, false, zeta2));            // A on the second coset
             const Fe unhat = hat ? Fr::inv(Fr::from_u64(32)) : Fr::one();
-            ZG_TRY(poly_diff_scale(ctx, nb, p->dbuf[2].h, L2, unhat, a2, tb, Fr::inv(Fr::sub(c2, c1)), a2, tb, L2));  // B on the second coset
+            ZG_TRY(poly_diff_scale(ctx, nq, p->dbuf[2].h, L2, unhat, a2, tb, Fr::inv(Fr::sub(c2, c1)), a2, tb, L2));  // B on the second coset
             ctx->unit_next = 0.0;
-            ZG_TRY(coset_to_coeff_dev(ctx, a2, d2.ek, L2, bc, false, zeta2, nb, tb, tb));              // B
-            ZG_TRY(poly_split_combine(ctx, nb, hp, pp_bs, bc, tb, L2, c1, L1));                    // h = A - c1 B + X^L1 B
+            ZG_TRY(coset_to_coeff_dev(ctx, a2, d2.ek, L2, bc, false, zeta2, nq, tb, tb));              // B
+            ZG_TRY(poly_split_combine(ctx, nq, hp, pp_bs, bc, tb, L2, c1, L1));                    // h = A - c1 B + X^L1 B
         }
         ctx->msm_dense_hint = true;  // (the quotient pieces are random vectors: every digit of every window is an addition)
-        const int st_h = commit(p, phase_msm(dense_g(p), pp_at(p->ix_hpiece), n, Q, pp_bs), W_QUOTIENT);
+        const int st_h = commit(p, phase_msm(dense_g(p), pp_at(p->ix_hpiece), n, Q, pp_bs, nq), W_QUOTIENT);
         ctx->msm_dense_hint = false;
         ZG_TRY(st_h);
         ZG_TICK("h: queued");
@@ -732,13 +774,14 @@ struct ProveBatch {
     }
     // (h's commitments, then x and the opening points: needs evaluation_lists())
     int quotient_absorb() {
-        ZG_TRY(wait_points(p, (size_t)nb * Q, pts, W_QUOTIENT));
+        ZG_TRY(wait_points(p, (size_t)nq * Q, pts, W_QUOTIENT));
         ZG_TICK("h: points on the host");
-        for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t b = 0; b < nq; b++)
             for (uint32_t i = 0; i < Q; i++) tr[b].write_point(pts[(size_t)b * Q + i]);
+        Fe x{};
         for (uint32_t b = 0; b < nb; b++) {
             ProofConst& c = p->hpc[b];
-            const Fe x = tr[b].squeeze();
+            if (b < ntr) x = tr[b].squeeze();
             c.xn = Fr::pow_u64(x, n);
             for (uint32_t i = 0; i < npoints; i++) c.points[i] = rotate_omega(pk, x, rots[i]);
         }
@@ -762,11 +805,11 @@ struct ProveBatch {
         evq.clear();  // evaluations in transcript order, then h_poly at x
         for (auto& q : pk.advice_queries) evq.push_back({p->ix_adv + q.column, rot_slot(q.rotation)});
         e_fixed = evq.size();
-        for (auto& q : pk.fixed_queries) evq.push_back({p->ix_fixed + q.column, rot_slot(q.rotation)});
+        for (auto& q : pk.fixed_queries) evq.push_back({p->ix_fixed + q.column, rot_slot(q.rotation), true});
         e_random = evq.size();
-        evq.push_back({p->ix_random, 0});
+        evq.push_back({p->ix_random, 0, true});
         e_sigma = evq.size();
-        for (uint32_t c = 0; c < P; c++) evq.push_back({p->ix_sigma + c, 0});
+        for (uint32_t c = 0; c < P; c++) evq.push_back({p->ix_sigma + c, 0, true});
         e_pz = evq.size();
         for (uint32_t s = 0; s < S; s++) {
             evq.push_back({p->ix_pz + s, 0});
@@ -782,8 +825,16 @@ struct ProveBatch {
             evq.push_back({p->ix_perm + 2 * l + 1, 0});  // s'(x)
         }
         e_written = evq.size();
-        evq.push_back({p->ix_hpoly, 0});
+        evq.push_back({p->ix_hpoly, 0, true});
         e_h = e_written;
+        // where an evaluation lands in a slot's row: in transcript order -- or, multi, the per-circuit ones first (every
+        // slot's row) and behind them, in slot 0's row only, what the proof holds once: fixed, random, sigma, h
+        n_per = 0;
+        for (Q1& q : evq) n_per += multi && q.shared ? 0 : 1;
+        {
+            uint32_t at_per = 0, at_once = n_per;
+            for (Q1& q : evq) q.at = multi && q.shared ? at_once++ : at_per++;
+        }
         npoints = (uint32_t)rots.size();
         ZG_REQUIRE(npoints <= p->max_points, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u distinct rotations are queried (max %u)", npoints,
                    p->max_points);
@@ -798,13 +849,13 @@ struct ProveBatch {
             std::vector<uint32_t> list(Q);
             for (uint32_t i = 0; i < Q; i++) list[i] = p->ix_hpiece + (Q - 1 - i);
             ZG_TRY(h2d_list(p, d_hlist, list));
-            ZG_TRY(poly_horner_combine_xn(ctx, polys, p->d_pc, nb, d_hlist, Q, pp_at(p->ix_hpoly), pp_bs, n));
+            ZG_TRY(poly_horner_combine_xn(ctx, polys, p->d_pc, nq, d_hlist, Q, pp_at(p->ix_hpoly), pp_bs, n));
         }
-        ZG_TRY(poly_powers(ctx, p->d_pc, nb, npoints, n, p->pw, pw_bs));
+        ZG_TRY(poly_powers(ctx, p->d_pc, nq, npoints, n, p->pw, pw_bs));  // (multi: one x, one table of powers)
         std::vector<uint32_t> idx(2 * evq.size());
-        for (size_t i = 0; i < evq.size(); i++) {
-            idx[i] = evq[i].poly;
-            idx[evq.size() + i] = evq[i].slot;
+        for (size_t i = 0; i < evq.size(); i++) {  // (by place in the row: polynomials [0, size), their points behind them)
+            idx[evq[i].at] = evq[i].poly;
+            idx[evq.size() + evq[i].at] = evq[i].slot;
         }
         ZG_TRY(h2d_list(p, p->d_idx, idx));
         // (the evaluations too are written where the host reads them: no copy command behind the kernel)
@@ -814,8 +865,17 @@ struct ProveBatch {
             std::sort(seen.begin(), seen.end());
             distinct_polys = (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
         }
-        ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + evq.size(), p->pw, pw_bs, (uint32_t)evq.size(),
-                        p->pin.dev_view(p->pin.evals()), p->max_evals, distinct_polys, npoints));
+        if (!multi) {
+            ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + evq.size(), p->pw, pw_bs, (uint32_t)evq.size(),
+                            p->pin.dev_view(p->pin.evals()), p->max_evals, distinct_polys, npoints));
+        } else {
+            // every circuit's own evaluations, then -- once, slot 0 -- the shared ones: all against the one table of powers
+            const uint32_t n_once = (uint32_t)evq.size() - n_per;
+            ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + evq.size(), p->pw, 0, n_per, p->pin.dev_view(p->pin.evals()),
+                            p->max_evals, 0, npoints));
+            ZG_TRY(poly_dot(ctx, polys, 1, n, p->d_idx + n_per, p->d_idx + evq.size() + n_per, p->pw, 0, n_once,
+                            p->pin.dev_view(p->pin.evals()) + n_per, p->max_evals, 0, npoints));
+        }
         ev_all = p->pin.evals();
         ZG_HIP(hipEventRecord(p->evs[W_EVALS], st));
         ZG_TICK("evals: queued");
@@ -825,14 +885,35 @@ struct ProveBatch {
     int evaluations_absorb() {
         ZG_HIP(hipEventSynchronize(p->evs[W_EVALS]));
         ZG_TICK("evals on the host");
-        for (uint32_t b = 0; b < nb; b++) {
+        // evaluation `e` (evq index) of circuit c of a multi proof: a shared one lives in slot 0's row
+        auto ev_of = [&](uint32_t c, size_t e) -> const Fe& { return ev_all[(size_t)(evq[e].shared ? 0 : c) * p->max_evals + evq[e].at]; };
+        if (multi) {
+            // every circuit's advice evaluations | fixed, random, sigma once | every circuit's permutation evaluations |
+            // every circuit's lookup evaluations
+            EvmTranscript& t = tr[0];
+            for (uint32_t c = 0; c < nb; c++)
+                for (size_t i = 0; i < e_fixed; i++) t.write_scalar(ev_of(c, i));
+            for (size_t i = e_fixed; i < e_pz; i++) t.write_scalar(ev_of(0, i));
+            for (uint32_t c = 0; c < nb; c++)
+                for (size_t i = e_pz; i < e_lk; i++) t.write_scalar(ev_of(c, i));
+            for (uint32_t c = 0; c < nb; c++)
+                for (size_t i = e_lk; i < e_written; i++) t.write_scalar(ev_of(c, i));
+            const Fe v = t.squeeze();
+            for (uint32_t b = 0; b < nb; b++) p->hpc[b].v = v;
+            for (uint32_t s = 0; s < nsets; s++) {  // eval_batch of a set: Horner in v over all circuits' evaluations, list order
+                Fe eval_batch = fe_zero();
+                for (const EvRef& r : set_evs[s]) eval_batch = Fr::add(Fr::mul(eval_batch, v), ev_of(r.circuit, r.ev));
+                p->hpc[0].subs[s] = eval_batch;
+            }
+        }
+        for (uint32_t b = 0; b < nb && !multi; b++) {
             const Fe* ev = ev_all + (size_t)b * p->max_evals;
             for (size_t i = 0; i < e_written; i++) tr[b].write_scalar(ev[i]);
             ProofConst& c = p->hpc[b];
             c.v = tr[b].squeeze();
             for (uint32_t s = 0; s < nsets; s++) {
                 Fe eval_batch = fe_zero();
-                for (size_t e : set_evs[s]) eval_batch = Fr::add(Fr::mul(eval_batch, c.v), ev[e]);
+                for (const EvRef& r : set_evs[s]) eval_batch = Fr::add(Fr::mul(eval_batch, c.v), ev[r.ev]);
                 c.subs[s] = eval_batch;
             }
         }
@@ -845,43 +926,67 @@ struct ProveBatch {
 
     int openings_lists() {
         // ---- opening queries in create_proof's order: (poly, point slot, index of the evaluation)
-        struct OQ { uint32_t poly, slot; size_t ev; };
+        // (multi: circuit after circuit its advice, permutation and lookup queries, then once what all circuits share)
+        struct OQ { uint32_t poly, slot; size_t ev; uint32_t circuit; };
         std::vector<OQ> oq;
-        for (size_t i = 0; i < e_fixed; i++) oq.push_back({evq[i].poly, evq[i].slot, i});
-        {
-            size_t e = e_pz;
-            std::vector<size_t> e_last(S, 0), e_cur(S, 0), e_next(S, 0);
-            for (uint32_t s = 0; s < S; s++) {
-                e_cur[s] = e++;
-                e_next[s] = e++;
-                if (s + 1 < S) e_last[s] = e++;
+        for (uint32_t circ = 0; circ < (multi ? nb : 1u); circ++) {
+            for (size_t i = 0; i < e_fixed; i++) oq.push_back({evq[i].poly, evq[i].slot, i, circ});
+            {
+                size_t e = e_pz;
+                std::vector<size_t> e_last(S, 0), e_cur(S, 0), e_next(S, 0);
+                for (uint32_t s = 0; s < S; s++) {
+                    e_cur[s] = e++;
+                    e_next[s] = e++;
+                    if (s + 1 < S) e_last[s] = e++;
+                }
+                for (uint32_t s = 0; s < S; s++) {
+                    oq.push_back({p->ix_pz + s, 0, e_cur[s], circ});
+                    oq.push_back({p->ix_pz + s, 1, e_next[s], circ});
+                }
+                for (uint32_t s = S; s-- > 0;) {
+                    if (s + 1 == S) continue;
+                    oq.push_back({p->ix_pz + s, 3, e_last[s], circ});
+                }
             }
-            for (uint32_t s = 0; s < S; s++) {
-                oq.push_back({p->ix_pz + s, 0, e_cur[s]});
-                oq.push_back({p->ix_pz + s, 1, e_next[s]});
-            }
-            for (uint32_t s = S; s-- > 0;) {
-                if (s + 1 == S) continue;
-                oq.push_back({p->ix_pz + s, 3, e_last[s]});
+            for (uint32_t l = 0; l < NL; l++) {
+                const size_t e5 = e_lk + 5 * l;
+                oq.push_back({p->ix_lz + l, 0, e5 + 0, circ});
+                oq.push_back({p->ix_perm + 2 * l, 0, e5 + 2, circ});
+                oq.push_back({p->ix_perm + 2 * l + 1, 0, e5 + 4, circ});
+                oq.push_back({p->ix_perm + 2 * l, 2, e5 + 3, circ});
+                oq.push_back({p->ix_lz + l, 1, e5 + 1, circ});
             }
         }
-        for (uint32_t l = 0; l < NL; l++) {
-            const size_t e5 = e_lk + 5 * l;
-            oq.push_back({p->ix_lz + l, 0, e5 + 0});
-            oq.push_back({p->ix_perm + 2 * l, 0, e5 + 2});
-            oq.push_back({p->ix_perm + 2 * l + 1, 0, e5 + 4});
-            oq.push_back({p->ix_perm + 2 * l, 2, e5 + 3});
-            oq.push_back({p->ix_lz + l, 1, e5 + 1});
-        }
-        for (size_t i = e_fixed; i < e_random; i++) oq.push_back({evq[i].poly, evq[i].slot, i});
-        for (uint32_t c = 0; c < P; c++) oq.push_back({p->ix_sigma + c, 0, e_sigma + c});
-        oq.push_back({p->ix_hpoly, 0, e_h});
-        oq.push_back({p->ix_random, 0, e_random});
+        for (size_t i = e_fixed; i < e_random; i++) oq.push_back({evq[i].poly, evq[i].slot, i, 0});
+        for (uint32_t c = 0; c < P; c++) oq.push_back({p->ix_sigma + c, 0, e_sigma + c, 0});
+        oq.push_back({p->ix_hpoly, 0, e_h, 0});
+        oq.push_back({p->ix_random, 0, e_random, 0});
 
         // ---- ProverGWC::create_proof: the point sets (circuit only), then per proof its v-weighted evaluation batches
         nsets = 0;
-        lists.clear(); counts.clear(); set_slot.clear(); set_evs.clear();
-        {
+        lists.clear(); counts.clear(); set_slot.clear(); set_evs.clear(); firsts.clear();
+        if (multi) {
+            // the same sets -- a point appears first in circuit 0's queries -- over (circuit, polynomial) pairs, each list as
+            // long as it has to be (N = 32 of the zero_g circuit puts about a thousand polynomials at x)
+            ZG_REQUIRE(oq.size() <= p->mlists_cap && p->nsh + p->npp <= 0x10000u, ZG_ERR_UNSUPPORTED,
+                       "zg_prover_prove_multi: %zu opening queries (room for %zu)", oq.size(), p->mlists_cap);
+            std::vector<char> done(oq.size(), 0);
+            for (size_t first = 0; first < oq.size(); first++) {
+                if (done[first]) continue;
+                const uint32_t slot = oq[first].slot;
+                firsts.push_back((uint32_t)lists.size());
+                set_evs.emplace_back();
+                for (size_t j = first; j < oq.size(); j++) {
+                    if (done[j] || oq[j].slot != slot) continue;
+                    done[j] = 1;
+                    lists.push_back(oq[j].circuit << 16 | oq[j].poly);
+                    set_evs.back().push_back({oq[j].circuit, oq[j].ev});
+                }
+                counts.push_back((uint32_t)lists.size() - firsts.back());
+                set_slot.push_back(slot);
+                nsets++;
+            }
+        } else {
             std::vector<char> done(oq.size(), 0);
             for (size_t first = 0; first < oq.size(); first++) {
                 if (done[first]) continue;
@@ -894,7 +999,7 @@ struct ProveBatch {
                     done[j] = 1;
                     ZG_REQUIRE(cnt < 512, ZG_ERR_UNSUPPORTED, "zg_prover_prove: more than 512 polynomials opened at one point");
                     lists[(size_t)nsets * 512 + cnt++] = oq[j].poly;
-                    set_evs.back().push_back(oq[j].ev);
+                    set_evs.back().push_back({0, oq[j].ev});
                 }
                 counts.push_back(cnt);
                 set_slot.push_back(slot);
@@ -908,24 +1013,27 @@ struct ProveBatch {
     int openings_queue() {
         // poly_batch of every point set in one launch: set s -> wpoly[2s]
         // (their own region of d_idx, behind the evaluation lists: nothing else writes there between proofs)
-        uint32_t* d_lists = d_hlist + 64;
+        uint32_t* d_lists = multi ? p->d_mlists : d_hlist + 64;
         ZG_TRY(h2d_list(p, d_lists, lists));
+        if (multi)
+            ZG_TRY(poly_combine_pairs(ctx, polys, p->d_pc, d_lists, firsts.data(), counts.data(), nsets, p->wpoly, (size_t)2 * n, n));
+        else
         ZG_TRY(poly_horner_combine_sets(ctx, polys, p->d_pc, nb, d_lists, 512, counts.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, n));
         // one batched kate_division: poly s at wpoly[2s], quotient at wpoly[2s+1]
-        ZG_TRY(poly_kate_division(ctx, p->d_pc, nb, set_slot.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n,
+        ZG_TRY(poly_kate_division(ctx, p->d_pc, nq, set_slot.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n,
                                   wp_bs, p->ktmp, n));
         // the witness polynomials sit at odd slots: stride 2n
         ctx->msm_dense_hint = true;  // (so are the opening quotients)
-        const int st_w = commit(p, phase_msm(dense_g(p), p->wpoly + n, (size_t)2 * n, nsets, wp_bs), W_GWC);
+        const int st_w = commit(p, phase_msm(dense_g(p), p->wpoly + n, (size_t)2 * n, nsets, wp_bs, nq), W_GWC);
         ctx->msm_dense_hint = false;
         ZG_TRY(st_w);
         ZG_TICK("gwc: queued");
         return ZG_OK;
     }
     int openings_absorb() {
-        ZG_TRY(wait_points(p, (size_t)nb * nsets, pts, W_GWC));
+        ZG_TRY(wait_points(p, (size_t)nq * nsets, pts, W_GWC));
         ZG_TICK("gwc: points on the host");
-        for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t b = 0; b < nq; b++)
             for (uint32_t s = 0; s < nsets; s++) tr[b].write_point(pts[(size_t)b * nsets + s]);
         return ZG_OK;
     }
@@ -939,7 +1047,7 @@ struct ProveBatch {
             p->in_flight = false;
             return ZG_ERR_HIP;
         }
-        for (uint32_t b = 0; b < nb; b++) {
+        for (uint32_t b = 0; b < ntr; b++) {
             if (status[b] == ZG_OK && tr[b].failed) {
                 set_error("zg_prover_prove: a commitment of proof %u is the identity point; EvmTranscript cannot absorb it", b);
                 status[b] = ZG_ERR_INVALID_ARG;
@@ -985,6 +1093,44 @@ static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
     ProveBatch again(p, count, advice_host, advice_dev, instance, instance_len, keys, proofs, proof_cap, proof_lens, statuses);
     again.no_gate = true;
     return again.run();
+}
+
+// create_proof for a `circuits` slice: ONE proof of `circuits` instances of the circuit (ProveBatch::multi).  One circuit is
+// the single-proof path, byte for byte.
+static int prove_multi_impl(zg_prover* p, size_t circuits, const zg_fr* const* advice_host, void* const* advice_dev,
+                            const zg_fr* const* instance, size_t instance_len, const uint8_t* keys /* [circuits][32] */, uint8_t* proof,
+                            size_t proof_cap, size_t* proof_len) {
+    ZG_REQUIRE(p && proof && proof_len && keys, ZG_ERR_INVALID_ARG, "zg_prover_prove_multi: null argument");
+    *proof_len = 0;
+    ZG_TRY(batch_args_ok("zg_prover_prove_multi", "circuits", p, circuits, instance, instance_len));
+    uint8_t* out[1] = {proof};
+    if (circuits == 1) return prove_batch_impl(p, 1, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr);
+    ZG_REQUIRE(p->world <= 1 && !p->rccl_comm, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not on a point-range shard of the SRS");
+    ZG_REQUIRE(circuits <= FOLD_MAX_SLOTS, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: %zu circuits in one proof (max %u)", circuits,
+               FOLD_MAX_SLOTS);
+    ZG_REQUIRE(p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG, "zg_prover_prove_multi: the base sets hold %u of %u points", p->shard_n, p->pk->n);
+    ZG_ENTER(p->ctx);
+    ProveBatch job(p, circuits, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr, true);
+    return job.run();  // (never gated: the gate is a lone proof's)
+}
+
+size_t zg_prover_proof_size_multi(const zg_prover* p, size_t circuits) {
+    if (!p || !circuits) return 0;
+    const PkDev& k = *p->pk;
+    const size_t per_points = k.A + 3 * k.NL + k.sets;
+    const size_t per_scalars = k.advice_queries.size() + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
+    const size_t max_open = 2 + k.advice_queries.size() + k.fixed_queries.size();
+    return 64 * (circuits * per_points + 1 + k.qpd + max_open) + 32 * (circuits * per_scalars + k.fixed_queries.size() + 1 + k.P);
+}
+
+int zg_prover_prove_multi(zg_prover* p, size_t circuits, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,
+                          const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    return prove_multi_impl(p, circuits, advice, nullptr, instance, instance_len, rng_keys, proof, proof_cap, proof_len);
+}
+
+int zg_prover_prove_multi_dev(zg_prover* p, size_t circuits, void* const* d_advice, const zg_fr* const* instance, size_t instance_len,
+                              const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    return prove_multi_impl(p, circuits, nullptr, d_advice, instance, instance_len, rng_keys, proof, proof_cap, proof_len);
 }
 
 int zg_prover_prove_batch(zg_prover* p, size_t count, const zg_fr* const* advice, const zg_fr* const* instance,

@@ -149,6 +149,9 @@ struct zg_prover {
     zg::ProofConst* d_pc = nullptr;
     std::vector<zg::ProofConst> hpc;
     uint32_t* d_idx = nullptr;  // index lists (circuit only: the same for every proof)
+    // a proof of several circuits: its opening lists over (slot, polynomial) pairs, sized for `cap` circuits
+    uint32_t* d_mlists = nullptr;
+    size_t mlists_cap = 0;
     std::map<uint32_t*, std::vector<uint32_t>> uploaded_lists;  // what h2d_list left at each destination
     std::vector<size_t> inst_filled;  // per slot: rows of inst_val that may be non-zero
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_err = nullptr;

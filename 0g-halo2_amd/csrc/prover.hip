@@ -225,6 +225,9 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
     p->maxv = std::max<uint32_t>(std::max<uint32_t>(A, 2 * NL + 1), std::max<uint32_t>(S + NL + 1, std::max<uint32_t>(Q, p->max_points)));
     ZG_TRY(dalloc_into(own, &p->xyzz, c * p->maxv));
     ZG_TRY(dalloc_into(own, &p->d_idx, (size_t)4 * p->max_evals + 64 + (size_t)p->max_points * 512));
+    // (per circuit: its advice queries, 3 per permutation set but 2 for the last, 5 per lookup; once: fixed, sigma, h, random)
+    p->mlists_cap = c * (k.advice_queries.size() + (S ? 3 * S - 1 : 0) + 5 * NL) + k.fixed_queries.size() + P + 2;
+    ZG_TRY(dalloc_into(own, &p->d_mlists, p->mlists_cap));
     ZG_TRY(dalloc_into(own, &p->ktmp, poly_kate_tmp_elems(n, cap * p->max_points)));
     ZG_TRY(dalloc_into(own, &p->d_pc, c));
     p->hpc.assign(cap, ProofConst{});

@@ -1,6 +1,9 @@
 // Batched GWC verification on the device -- replaces halo2_proofs::plonk::verify_proof::<KZGCommitmentScheme<Bn256>,
 // VerifierGWC, _, EvmTranscript, AccumulatorStrategy> + DualMSM::check (halo2_proofs v2023_04_20 src/plonk/verifier.rs,
-// src/poly/kzg/multiopen/gwc/verifier.rs, src/poly/kzg/strategy.rs) for many proofs of one circuit.
+// src/poly/kzg/multiopen/gwc/verifier.rs, src/poly/kzg/strategy.rs) for many proofs of one circuit, each of NC >= 1
+// instances of it (verify_proof's `instances: &[&[&[F]]]`; NC = 1: zg_verifier_verify_batch).  A proof of NC instances
+// holds the per-circuit commitments and evaluations NC times, circuit-major within each family, and once what the
+// circuits share: the random polynomial, h, the fixed and sigma evaluations, one W per point set.
 //
 // Per proof b the GWC equation is  e(L_b, [s]_2) = e(R_b, [1]_2)  with  L_b = sum_j u^j W_j  and
 // R_b = sum_j u^j (z_j W_j + sum_k v^(m_j-1-k) C_jk - e_j G),  j over the opening point sets in first-appearance order,
@@ -16,6 +19,7 @@
 //   host            e(L, [s]_2) e(-R, [1]_2) = 1 (pairing.hip), outside the context lock; if it fails, the batch is
 //                   bisected over the weighted pairs down to the proofs that fail alone.
 #include <cstring>
+#include <map>
 
 #include "keccak.h"
 #include "poly.h"
@@ -28,7 +32,8 @@ namespace {
 
 constexpr uint32_t SHARED = 0x80000000u;  // query table: commitment shared by all proofs (fixed, sigma)
 constexpr uint32_t HREF = 0x7fffffffu;    // query table: the h commitment sum_i xn^i H_i
-constexpr uint32_t IEVAL = 0x80000000u;   // evaluation source: an instance evaluation slot
+constexpr uint32_t IEVAL = 0x80000000u;   // evaluation source: an instance evaluation slot (of the circuit at hand)
+constexpr uint32_t FIXEV = 0x40000000u;   // evaluation source: a fixed-query evaluation (shared); else: an advice query's, per circuit
 
 struct alignas(16) VMono {
     Fe coeff;
@@ -63,19 +68,23 @@ struct VArgs {
     uint32_t n_gates, n_lookups, n_queries, n_iev, n_oq;
     uint32_t A, F, I, P, NL, sets, chunk, qpd, bf, nsets, nAQ, nFQ;
     uint32_t NE, NP, NT, ev_h;  // evaluations (with the expected h(x) last), per-proof points, terms
+    // proofs of NC circuit instances: where the families start among a proof's points (circuit c's share of a family
+    // follows circuit c-1's: A advice, 2 NL permuted, `sets` permutation z, NL lookup z) and among its evaluations (nAQ
+    // advice, npz permutation, 5 NL lookup evaluations per circuit)
+    uint32_t NC, PT_LK, PT_PZ, PT_LZ, PT_RAND, EV_FIX, EV_SIG, EV_PZ, EV_LK, npz;
     uint32_t log_n;
     Fe omega, ifft_div, delta, vk_repr;
     // batch
     const uint8_t* bytes;
     const uint64_t* off;
     const uint64_t* len;
-    const Fe* inst;  // [count][I][ilen]
+    const Fe* inst;  // [count][NC][I][ilen]
     uint32_t ilen, count;
     Affine* pts;     // [count][NP]
     Fe* ev;          // [count][NE]
     Fe* ch;          // [count][CH_N]
     int* status;     // [count]
-    Fe* qe;          // [count][n_queries + n_iev]
+    Fe* qe;          // [count][n_queries + n_iev]: the circuit at hand's
     Fe* tmp;         // [count][2 * ninv]
     uint32_t ninv;
     Fe* sc;          // [count][NT], canonical integers
@@ -163,7 +172,8 @@ __host__ __device__ bool read_scalar(Reader& r, Sponge& s, Fe& out) {
     return true;
 }
 
-// Read order: advice commitments | theta | per lookup (permuted input, permuted table) | beta, gamma | permutation z
+// Read order (NC = 1; with more circuits every per-circuit family is read for circuit 0, 1, ... in turn, and the
+// permutation z of all circuits come before the lookup z of all circuits): advice commitments | theta | per lookup (permuted input, permuted table) | beta, gamma | permutation z
 // per set | lookup z | random | y | h pieces | x | advice, fixed evals, random eval, sigma evals, permutation evals
 // (z, z(wx), and z(w^last x) except for the last set), lookup evals (z, z(wx), a', a'(w^-1 x), s') | v | one W per
 // point set | u.  Points land in pts in that order (W last), evaluations in ev.
@@ -175,18 +185,18 @@ __host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
     Fe* ev = a.ev + (size_t)b * a.NE;
     Fe* ch = a.ch + (size_t)b * CH_N;
     sp_int(s, Fr::to_raw(a.vk_repr));
-    const Fe* inst = a.inst + (size_t)b * a.I * a.ilen;
-    for (uint32_t i = 0; i < a.I * a.ilen; i++) sp_int(s, Fr::to_raw(inst[i]));
+    const Fe* inst = a.inst + (size_t)b * a.NC * a.I * a.ilen;
+    for (uint32_t i = 0; i < a.NC * a.I * a.ilen; i++) sp_int(s, Fr::to_raw(inst[i]));
     bool ok = true;
     uint32_t pi = 0, ei = 0;
-    for (uint32_t c = 0; c < a.A && ok; c++) ok = read_point(r, s, pts[pi++]);
+    for (uint32_t c = 0; c < a.NC * a.A && ok; c++) ok = read_point(r, s, pts[pi++]);
     if (ok) ch[CH_THETA] = sp_squeeze(s);
-    for (uint32_t l = 0; l < 2 * a.NL && ok; l++) ok = read_point(r, s, pts[pi++]);
+    for (uint32_t l = 0; l < a.NC * 2 * a.NL && ok; l++) ok = read_point(r, s, pts[pi++]);
     if (ok) {
         ch[CH_BETA] = sp_squeeze(s);
         ch[CH_GAMMA] = sp_squeeze(s);
     }
-    for (uint32_t c = 0; c < a.sets + a.NL + 1 && ok; c++) ok = read_point(r, s, pts[pi++]);
+    for (uint32_t c = 0; c < a.NC * (a.sets + a.NL) + 1 && ok; c++) ok = read_point(r, s, pts[pi++]);
     if (ok) ch[CH_Y] = sp_squeeze(s);
     for (uint32_t c = 0; c < a.qpd && ok; c++) ok = read_point(r, s, pts[pi++]);
     if (ok) ch[CH_X] = sp_squeeze(s);
@@ -237,8 +247,9 @@ __host__ __device__ Fe eval_poly(const VArgs& a, const zg_poly& p, const Fe* qe)
     return acc;
 }
 
-__host__ __device__ __forceinline__ Fe src_eval(uint32_t src, const Fe* ev, const Fe* iev) {
-    return (src & IEVAL) ? iev[src & ~IEVAL] : ev[src];
+// (ev: the proof's evaluations; adv: circuit c's advice evaluations among them; iev: its instance evaluations)
+__host__ __device__ __forceinline__ Fe src_eval(uint32_t src, const Fe* ev, const Fe* adv, const Fe* iev, uint32_t ev_fix) {
+    return (src & IEVAL) ? iev[src & ~IEVAL] : (src & FIXEV) ? ev[ev_fix + (src & ~FIXEV)] : adv[src];
 }
 
 __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
@@ -249,7 +260,7 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
     Fe* den = a.tmp + (size_t)b * 2 * a.ninv;
     Fe* pre = den + a.ninv;
     Fe* sc = a.sc + (size_t)b * a.NT;
-    const Fe* inst = a.inst + (size_t)b * a.I * a.ilen;
+    const Fe* inst_all = a.inst + (size_t)b * a.NC * a.I * a.ilen;
     const Fe x = ch[CH_X], y = ch[CH_Y], beta = ch[CH_BETA], gamma = ch[CH_GAMMA], theta = ch[CH_THETA];
     const Fe v = ch[CH_V], u = ch[CH_U], one = Fr::one();
     Fe xn = x;
@@ -267,7 +278,7 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
             wi = Fr::mul(wi, a.omega);
         }
     }
-    batch_inv(den, pre, 1 + nl + a.n_iev * a.ilen);
+    batch_inv(den, pre, 1 + nl + a.n_iev * a.ilen);  // (the same denominators serve every circuit of the proof)
     // l_i(x) = (x^n - 1)/n * omega^i / (x - omega^i)
     const Fe num = Fr::mul(Fr::sub(xn, one), a.ifft_div);
     Fe llast = fe_zero(), l0 = fe_zero(), lblind = fe_zero();
@@ -278,69 +289,72 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
         else lblind = Fr::add(lblind, li);
     }
     const Fe lactive = Fr::sub(one, Fr::add(llast, lblind));
-    // instance column c at x omega^rot: (x^n - 1)/n * sum_i inst_i omega^i / (x omega^rot - omega^i)
-    for (uint32_t e = 0; e < a.n_iev; e++) {
-        const Fe* col = inst + (size_t)a.iev_col[e] * a.ilen;
-        Fe acc = fe_zero(), wi = one;
-        for (uint32_t i = 0; i < a.ilen; i++) {
-            acc = Fr::add(acc, Fr::mul(Fr::mul(col[i], wi), den[1 + nl + e * a.ilen + i]));
-            wi = Fr::mul(wi, a.omega);
-        }
-        iev[e] = Fr::mul(acc, num);
-    }
-    for (uint32_t q = 0; q < a.n_queries; q++) qe[q] = src_eval(a.qsrc[q], ev, iev);
-
-    // expected h(x): gates, permutation, lookups folded with y (the prover's order), over x^n - 1
+    // expected h(x): gates, permutation, lookups folded with y (the prover's order) -- circuit 0's terms, then circuit
+    // 1's, and so on, ONE Horner value carried through all of them -- over x^n - 1
     Fe acc = fe_zero();
 #define FOLD(val) acc = Fr::add(Fr::mul(acc, y), (val))
-    for (uint32_t g = 0; g < a.n_gates; g++) FOLD(eval_poly(a, a.gates[g], qe));
-    const uint32_t EV_PZ = a.nAQ + a.nFQ + 1 + a.P;
-    if (a.sets > 0) {
-        const Fe* pz = ev + EV_PZ;  // set s: z at 3s, z(wx) at 3s + 1, z(w^last x) at 3s + 2
-        FOLD(Fr::mul(Fr::sub(one, pz[0]), l0));
-        const Fe zl = pz[3 * (a.sets - 1)];
-        FOLD(Fr::mul(Fr::sub(Fr::sqr(zl), zl), llast));
-        for (uint32_t s = 1; s < a.sets; s++) FOLD(Fr::mul(Fr::sub(pz[3 * s], pz[3 * (s - 1) + 2]), l0));
-        Fe cd0 = Fr::mul(beta, x);
-        for (uint32_t s = 0; s < a.sets; s++) {
-            Fe left = pz[3 * s + 1], right = pz[3 * s], cd = cd0;
-            const uint32_t c0 = s * a.chunk, c1 = c0 + a.chunk > a.P ? a.P : c0 + a.chunk;
-            for (uint32_t c = c0; c < c1; c++) {
-                const Fe ce = src_eval(a.psrc[c], ev, iev);
-                const Fe sig = ev[a.nAQ + a.nFQ + 1 + c];
-                left = Fr::mul(left, Fr::add(Fr::add(Fr::mul(beta, sig), ce), gamma));
-                right = Fr::mul(right, Fr::add(Fr::add(ce, cd), gamma));
-                cd = Fr::mul(cd, a.delta);
+    for (uint32_t circ = 0; circ < a.NC; circ++) {
+        const Fe* inst = inst_all + (size_t)circ * a.I * a.ilen;
+        const Fe* adv = ev + circ * a.nAQ;
+        // instance column c at x omega^rot: (x^n - 1)/n * sum_i inst_i omega^i / (x omega^rot - omega^i)
+        for (uint32_t e = 0; e < a.n_iev; e++) {
+            const Fe* col = inst + (size_t)a.iev_col[e] * a.ilen;
+            Fe sum = fe_zero(), wi = one;
+            for (uint32_t i = 0; i < a.ilen; i++) {
+                sum = Fr::add(sum, Fr::mul(Fr::mul(col[i], wi), den[1 + nl + e * a.ilen + i]));
+                wi = Fr::mul(wi, a.omega);
             }
-            cd0 = cd;
-            FOLD(Fr::mul(Fr::sub(left, right), lactive));
+            iev[e] = Fr::mul(sum, num);
         }
-    }
-    const Fe* lk = ev + EV_PZ + (a.sets ? 3 * a.sets - 1 : 0);
-    for (uint32_t l = 0; l < a.NL; l++) {
-        const zg_lookup L = a.lookups[l];
-        Fe ai = fe_zero(), ti = fe_zero();
-        for (uint32_t e = 0; e < ZG_MAX_LOOKUP_WIDTH; e++) {
-            if (e >= L.width) break;
-            ai = Fr::add(Fr::mul(ai, theta), eval_poly(a, L.inputs[e], qe));
-            ti = Fr::add(Fr::mul(ti, theta), eval_poly(a, L.tables[e], qe));
+        for (uint32_t q = 0; q < a.n_queries; q++) qe[q] = src_eval(a.qsrc[q], ev, adv, iev, a.EV_FIX);
+        for (uint32_t g = 0; g < a.n_gates; g++) FOLD(eval_poly(a, a.gates[g], qe));
+        if (a.sets > 0) {
+            const Fe* pz = ev + a.EV_PZ + circ * a.npz;  // set s: z at 3s, z(wx) at 3s + 1, z(w^last x) at 3s + 2
+            FOLD(Fr::mul(Fr::sub(one, pz[0]), l0));
+            const Fe zl = pz[3 * (a.sets - 1)];
+            FOLD(Fr::mul(Fr::sub(Fr::sqr(zl), zl), llast));
+            for (uint32_t s = 1; s < a.sets; s++) FOLD(Fr::mul(Fr::sub(pz[3 * s], pz[3 * (s - 1) + 2]), l0));
+            Fe cd0 = Fr::mul(beta, x);
+            for (uint32_t s = 0; s < a.sets; s++) {
+                Fe left = pz[3 * s + 1], right = pz[3 * s], cd = cd0;
+                const uint32_t c0 = s * a.chunk, c1 = c0 + a.chunk > a.P ? a.P : c0 + a.chunk;
+                for (uint32_t c = c0; c < c1; c++) {
+                    const Fe ce = src_eval(a.psrc[c], ev, adv, iev, a.EV_FIX);
+                    const Fe sig = ev[a.EV_SIG + c];
+                    left = Fr::mul(left, Fr::add(Fr::add(Fr::mul(beta, sig), ce), gamma));
+                    right = Fr::mul(right, Fr::add(Fr::add(ce, cd), gamma));
+                    cd = Fr::mul(cd, a.delta);
+                }
+                cd0 = cd;
+                FOLD(Fr::mul(Fr::sub(left, right), lactive));
+            }
         }
-        const Fe* e5 = lk + 5 * l;  // z, z(wx), a', a'(w^-1 x), s'
-        FOLD(Fr::mul(Fr::sub(one, e5[0]), l0));
-        FOLD(Fr::mul(Fr::sub(Fr::sqr(e5[0]), e5[0]), llast));
-        const Fe lft = Fr::mul(Fr::mul(Fr::add(e5[2], beta), Fr::add(e5[4], gamma)), e5[1]);
-        const Fe rgt = Fr::mul(Fr::mul(Fr::add(ai, beta), Fr::add(ti, gamma)), e5[0]);
-        FOLD(Fr::mul(Fr::sub(lft, rgt), lactive));
-        const Fe ams = Fr::sub(e5[2], e5[4]);
-        FOLD(Fr::mul(ams, l0));
-        FOLD(Fr::mul(Fr::mul(Fr::sub(e5[2], e5[3]), ams), lactive));
+        const Fe* lk = ev + a.EV_LK + circ * 5 * a.NL;
+        for (uint32_t l = 0; l < a.NL; l++) {
+            const zg_lookup L = a.lookups[l];
+            Fe ai = fe_zero(), ti = fe_zero();
+            for (uint32_t e = 0; e < ZG_MAX_LOOKUP_WIDTH; e++) {
+                if (e >= L.width) break;
+                ai = Fr::add(Fr::mul(ai, theta), eval_poly(a, L.inputs[e], qe));
+                ti = Fr::add(Fr::mul(ti, theta), eval_poly(a, L.tables[e], qe));
+            }
+            const Fe* e5 = lk + 5 * l;  // z, z(wx), a', a'(w^-1 x), s'
+            FOLD(Fr::mul(Fr::sub(one, e5[0]), l0));
+            FOLD(Fr::mul(Fr::sub(Fr::sqr(e5[0]), e5[0]), llast));
+            const Fe lft = Fr::mul(Fr::mul(Fr::add(e5[2], beta), Fr::add(e5[4], gamma)), e5[1]);
+            const Fe rgt = Fr::mul(Fr::mul(Fr::add(ai, beta), Fr::add(ti, gamma)), e5[0]);
+            FOLD(Fr::mul(Fr::sub(lft, rgt), lactive));
+            const Fe ams = Fr::sub(e5[2], e5[4]);
+            FOLD(Fr::mul(ams, l0));
+            FOLD(Fr::mul(Fr::mul(Fr::sub(e5[2], e5[3]), ams), lactive));
+        }
     }
 #undef FOLD
     ev[a.ev_h] = Fr::mul(acc, den[0]);
 
     // term scalars: u^j v^k on each commitment (x_n^i more on the h pieces), -sum u^j e_j on g0, u^j and u^j z_j on W_j
     for (uint32_t t = 0; t < a.NT; t++) sc[t] = fe_zero();
-    const uint32_t T_SHARED = a.NP + a.nsets, T_G0 = a.NT - 1, PT_H = a.A + 3 * a.NL + a.sets + 1, PT_W = PT_H + a.qpd;
+    const uint32_t T_SHARED = a.NP + a.nsets, T_G0 = a.NT - 1, PT_H = a.PT_RAND + 1, PT_W = PT_H + a.qpd;
     Fe g0 = fe_zero();
     for (uint32_t q = 0; q < a.n_oq; q++) {
         const VQuery oq = a.oq[q];
@@ -444,8 +458,15 @@ struct zg_verifier {
     VArgs a{};
     zg_g2_affine g2{}, s_g2{};
     std::vector<void*> owned;  // circuit arrays
-    // batch buffers, grown on demand
-    size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0;
+    // what the query table of a proof of NC circuits is built from, and the tables made so far (by NC)
+    std::vector<zg_query> advice_queries, fixed_queries;
+    struct Table {
+        const VQuery* oq = nullptr;
+        uint32_t n_oq = 0;
+    };
+    std::map<uint32_t, Table> tables;
+    // batch buffers, grown on demand (cap: proofs; pts / ev / sc: elements, their size per proof follows NC)
+    size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0, pts_cap = 0, ev_cap = 0, sc_cap = 0;
     std::vector<void*> batch;
 };
 
@@ -473,13 +494,15 @@ int grow(zg_verifier* v, T** dst, size_t elems) {
 void free_batch(zg_verifier* v) {
     for (void* p : v->batch) (void)hipFree(p);
     v->batch.clear();
-    v->cap = v->bytes_cap = v->inst_cap = v->tmp_cap = 0;
+    v->cap = v->bytes_cap = v->inst_cap = v->tmp_cap = v->pts_cap = v->ev_cap = v->sc_cap = 0;
 }
 
 // batch buffers for `count` proofs of `bytes` bytes in all, `inst` instance values and `tmp` inversion scratch elements
 int ensure(zg_verifier* v, size_t count, size_t bytes, size_t inst, size_t tmp) {
     VArgs& a = v->a;
-    if (count <= v->cap && bytes <= v->bytes_cap && inst <= v->inst_cap && tmp <= v->tmp_cap) return ZG_OK;
+    if (count <= v->cap && bytes <= v->bytes_cap && inst <= v->inst_cap && tmp <= v->tmp_cap && count * a.NP <= v->pts_cap &&
+        count * a.NE <= v->ev_cap && count * a.NT <= v->sc_cap)
+        return ZG_OK;
     free_batch(v);
     count = std::max(count, (size_t)1);
     bytes = std::max(bytes, (size_t)1);
@@ -503,11 +526,88 @@ int ensure(zg_verifier* v, size_t count, size_t bytes, size_t inst, size_t tmp) 
     v->bytes_cap = bytes;
     v->inst_cap = inst;
     v->tmp_cap = tmp;
+    v->pts_cap = count * a.NP;
+    v->ev_cap = count * a.NE;
+    v->sc_cap = count * a.NT;
     return ZG_OK;
 }
 
 Fe omega_pow(const Fe& omega, const Fe& omega_inv, int64_t r) {
     return Fr::pow_u64(r >= 0 ? omega : omega_inv, (uint64_t)(r >= 0 ? r : -r));
+}
+
+// The layout of a proof of NC circuit instances and its table of opening queries into v->a; tables are built once per NC.
+// Points in read order: every circuit's advice | every circuit's (permuted input, permuted table) per lookup | every
+// circuit's permutation z | every circuit's lookup z | random | h pieces | W per point set.  Evaluations in read order:
+// every circuit's advice | fixed, random, sigma | every circuit's permutation (3 per set, 2 for the last) | every circuit's
+// lookups (5 each) | (the expected h(x)).
+int set_circuits(zg_verifier* v, uint32_t NC) {
+    VArgs& a = v->a;
+    a.NC = NC;
+    a.PT_LK = NC * a.A; a.PT_PZ = a.PT_LK + NC * 2 * a.NL; a.PT_LZ = a.PT_PZ + NC * a.sets; a.PT_RAND = a.PT_LZ + NC * a.NL;
+    a.EV_FIX = NC * a.nAQ;
+    const uint32_t EV_RAND = a.EV_FIX + a.nFQ;
+    a.EV_SIG = EV_RAND + 1; a.EV_PZ = a.EV_SIG + a.P; a.EV_LK = a.EV_PZ + NC * a.npz;
+    a.ev_h = a.EV_LK + NC * 5 * a.NL;
+    a.NE = a.ev_h + 1;
+    // opening queries in the prover's order -- circuit after circuit its advice, permutation and lookup queries, then what
+    // the circuits share; point sets by first appearance of their rotation (circuit 0's order: the same sets for every NC)
+    std::vector<VQuery> oq;
+    std::vector<int64_t> set_rot;
+    std::vector<uint32_t> set_size;
+    const int64_t nn = (int64_t)1 << a.log_n, last = -(int64_t)(a.bf + 1);
+    auto add = [&](int64_t rot, uint32_t term, uint32_t eval) {
+        const int64_t key = ((rot % nn) + nn) % nn;
+        uint32_t j = 0;
+        while (j < set_rot.size() && set_rot[j] != key) j++;
+        if (j == set_rot.size()) {
+            set_rot.push_back(key);
+            set_size.push_back(0);
+        }
+        oq.push_back({term, eval, j, set_size[j]++});
+    };
+    for (uint32_t c = 0; c < NC; c++) {
+        const uint32_t pt_adv = c * a.A, pt_lk = a.PT_LK + c * 2 * a.NL, pt_pz = a.PT_PZ + c * a.sets, pt_lz = a.PT_LZ + c * a.NL;
+        const uint32_t ev_adv = c * a.nAQ, ev_pz = a.EV_PZ + c * a.npz, ev_lk = a.EV_LK + c * 5 * a.NL;
+        for (uint32_t i = 0; i < a.nAQ; i++) add(v->advice_queries[i].rotation, pt_adv + v->advice_queries[i].column, ev_adv + i);
+        for (uint32_t s = 0; s < a.sets; s++) {
+            add(0, pt_pz + s, ev_pz + 3 * s);
+            add(1, pt_pz + s, ev_pz + 3 * s + 1);
+        }
+        for (uint32_t s = a.sets; s-- > 0;)
+            if (s + 1 != a.sets) add(last, pt_pz + s, ev_pz + 3 * s + 2);
+        for (uint32_t l = 0; l < a.NL; l++) {
+            add(0, pt_lz + l, ev_lk + 5 * l);
+            add(0, pt_lk + 2 * l, ev_lk + 5 * l + 2);
+            add(0, pt_lk + 2 * l + 1, ev_lk + 5 * l + 4);
+            add(-1, pt_lk + 2 * l, ev_lk + 5 * l + 3);
+            add(1, pt_lz + l, ev_lk + 5 * l + 1);
+        }
+    }
+    for (uint32_t i = 0; i < a.nFQ; i++) add(v->fixed_queries[i].rotation, SHARED | v->fixed_queries[i].column, a.EV_FIX + i);
+    for (uint32_t c = 0; c < a.P; c++) add(0, SHARED | (a.F + c), a.EV_SIG + c);
+    add(0, HREF, a.ev_h);
+    add(0, a.PT_RAND, EV_RAND);
+    // v-powers run down within a set: the first query of a set of m gets v^(m-1)
+    for (VQuery& q : oq) q.vpow = set_size[q.set] - 1 - q.vpow;
+    a.nsets = (uint32_t)set_rot.size();
+    a.n_oq = (uint32_t)oq.size();
+    a.NP = a.PT_RAND + 1 + a.qpd + a.nsets;
+    a.NT = a.NP + a.nsets + a.F + a.P + 1;
+    auto it = v->tables.find(NC);
+    if (it == v->tables.end()) {
+        zg_verifier::Table t;
+        ZG_TRY(upload(v, &t.oq, oq));
+        t.n_oq = a.n_oq;
+        if (!a.set_wr) {  // (the point sets do not depend on NC)
+            std::vector<Fe> set_wr;
+            for (int64_t r : set_rot) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
+            ZG_TRY(upload(v, &a.set_wr, set_wr));
+        }
+        it = v->tables.emplace(NC, t).first;
+    }
+    a.oq = it->second.oq;
+    return ZG_OK;
 }
 
 int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fixed_c, const zg_g1_affine* sigma_c,
@@ -528,11 +628,9 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
     a.ifft_div = Fr::inv(Fr::from_u64(n));
     a.delta = fr_delta();
     a.vk_repr = fe_of(*vk_repr);
-    // evaluations in read order: advice, fixed, random, sigma, permutation (3 per set, 2 for the last), lookups (5 each)
-    const uint32_t EV_FIX = a.nAQ, EV_RAND = a.nAQ + a.nFQ, EV_SIG = EV_RAND + 1, EV_PZ = EV_SIG + a.P;
-    const uint32_t EV_LK = EV_PZ + (a.sets ? 3 * a.sets - 1 : 0);
-    a.ev_h = EV_LK + 5 * a.NL;
-    a.NE = a.ev_h + 1;
+    a.npz = a.sets ? 3 * a.sets - 1 : 0;
+    v->advice_queries.assign(cs->advice_queries, cs->advice_queries + a.nAQ);
+    v->fixed_queries.assign(cs->fixed_queries, cs->fixed_queries + a.nFQ);
 
     // where each circuit query's evaluation comes from
     std::vector<uint32_t> iev_col;
@@ -552,7 +650,7 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
             return true;
         }
         const zg_query* list = kind == ZG_ADVICE ? cs->advice_queries : cs->fixed_queries;
-        const uint32_t cnt = kind == ZG_ADVICE ? a.nAQ : a.nFQ, base = kind == ZG_ADVICE ? 0 : EV_FIX;
+        const uint32_t cnt = kind == ZG_ADVICE ? a.nAQ : a.nFQ, base = kind == ZG_ADVICE ? 0 : FIXEV;
         bool found = false;
         for (uint32_t i = 0; i < cnt; i++)
             if (list[i].column == col && list[i].rotation == rot) {
@@ -570,52 +668,8 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
                    "zg_verifier_create: permutation column %u has no query at the current row", c);
     a.n_iev = (uint32_t)iev_col.size();
 
-    // per-proof points in read order: advice | (permuted input, permuted table) per lookup | permutation z | lookup z |
-    // random | h pieces | W per point set
-    const uint32_t PT_LK = a.A, PT_PZ = PT_LK + 2 * a.NL, PT_LZ = PT_PZ + a.sets, PT_RAND = PT_LZ + a.NL;
-    // opening queries in the prover's order; point sets by first appearance of their rotation
-    std::vector<VQuery> oq;
-    std::vector<int64_t> set_rot;
-    std::vector<uint32_t> set_size;
-    const int64_t nn = (int64_t)n, last = -(int64_t)(a.bf + 1);
-    auto add = [&](int64_t rot, uint32_t term, uint32_t eval) {
-        const int64_t key = ((rot % nn) + nn) % nn;
-        uint32_t j = 0;
-        while (j < set_rot.size() && set_rot[j] != key) j++;
-        if (j == set_rot.size()) {
-            set_rot.push_back(key);
-            set_size.push_back(0);
-        }
-        oq.push_back({term, eval, j, set_size[j]++});
-    };
-    for (uint32_t i = 0; i < a.nAQ; i++) add(cs->advice_queries[i].rotation, cs->advice_queries[i].column, i);
-    for (uint32_t s = 0; s < a.sets; s++) {
-        add(0, PT_PZ + s, EV_PZ + 3 * s);
-        add(1, PT_PZ + s, EV_PZ + 3 * s + 1);
-    }
-    for (uint32_t s = a.sets; s-- > 0;)
-        if (s + 1 != a.sets) add(last, PT_PZ + s, EV_PZ + 3 * s + 2);
-    for (uint32_t l = 0; l < a.NL; l++) {
-        add(0, PT_LZ + l, EV_LK + 5 * l);
-        add(0, PT_LK + 2 * l, EV_LK + 5 * l + 2);
-        add(0, PT_LK + 2 * l + 1, EV_LK + 5 * l + 4);
-        add(-1, PT_LK + 2 * l, EV_LK + 5 * l + 3);
-        add(1, PT_LZ + l, EV_LK + 5 * l + 1);
-    }
-    for (uint32_t i = 0; i < a.nFQ; i++)
-        add(cs->fixed_queries[i].rotation, SHARED | cs->fixed_queries[i].column, EV_FIX + i);
-    for (uint32_t c = 0; c < a.P; c++) add(0, SHARED | (a.F + c), EV_SIG + c);
-    add(0, HREF, a.ev_h);
-    add(0, PT_RAND, EV_RAND);
-    // v-powers run down within a set: the first query of a set of m gets v^(m-1)
-    for (VQuery& q : oq) q.vpow = set_size[q.set] - 1 - q.vpow;
-    a.nsets = (uint32_t)set_rot.size();
-    a.n_oq = (uint32_t)oq.size();
-    a.NP = PT_RAND + 1 + a.qpd + a.nsets;
-    a.NT = a.NP + a.nsets + a.F + a.P + 1;
-    std::vector<Fe> set_wr, lag_w;
-    for (int64_t r : set_rot) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
-    for (int64_t r = last; r <= 0; r++) lag_w.push_back(omega_pow(a.omega, omega_inv, r));
+    std::vector<Fe> lag_w;
+    for (int64_t r = -(int64_t)(a.bf + 1); r <= 0; r++) lag_w.push_back(omega_pow(a.omega, omega_inv, r));
 
     std::vector<VMono> monos(cs->n_monomials);
     for (uint32_t m = 0; m < cs->n_monomials; m++) {
@@ -656,11 +710,9 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
     ZG_TRY(upload(v, &a.psrc, psrc));
     ZG_TRY(upload(v, &a.iev_col, iev_col));
     ZG_TRY(upload(v, &a.iev_wr, iev_wr));
-    ZG_TRY(upload(v, &a.oq, oq));
-    ZG_TRY(upload(v, &a.set_wr, set_wr));
     ZG_TRY(upload(v, &a.lag_w, lag_w));
     ZG_TRY(upload(v, &a.shared, shared));
-    return ZG_OK;
+    return set_circuits(v, 1);
 }
 
 }  // namespace
@@ -703,8 +755,14 @@ void zg_verifier_destroy(zg_verifier* v) {
 
 int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const* proofs, const size_t* proof_lens,
                              const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
+    return zg_verifier_verify_multi(v, count, 1, proofs, proof_lens, instance, instance_len, key, verdicts);
+}
+
+int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, const uint8_t* const* proofs, const size_t* proof_lens,
+                             const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
     ZG_REQUIRE(v && key && (count == 0 || (proofs && proof_lens && verdicts && (instance || v->a.I == 0))),
                ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: null argument");
+    ZG_REQUIRE(circuits >= 1 && circuits <= 1024, ZG_ERR_INVALID_ARG, "zg_verifier_verify_multi: proofs of %zu circuits", circuits);
     ZG_REQUIRE(count < (1u << 24) && instance_len < (1u << 24), ZG_ERR_UNSUPPORTED,
                "zg_verifier_verify_batch: %zu proofs of %zu instance rows", count, instance_len);
     if (count == 0) return ZG_OK;
@@ -716,12 +774,15 @@ int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const*
         // the device part holds the context (and this verifier's buffers); the host pairings below do not
         ZG_ENTER(ctx);
         VArgs& a = v->a;
-        const size_t per_inst = (size_t)a.I * instance_len;
+        ZG_TRY(set_circuits(v, (uint32_t)circuits));
+        const size_t one_inst = (size_t)a.I * instance_len, per_inst = circuits * one_inst;
         std::vector<uint64_t> off(count), len(count);
         size_t total = 0;
         for (size_t b = 0; b < count; b++) {
             ZG_REQUIRE(proofs[b] || proof_lens[b] == 0, ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: proof %zu is null", b);
-            ZG_REQUIRE(per_inst == 0 || instance[b], ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: instance %zu is null", b);
+            for (size_t c = 0; c < circuits; c++)
+                ZG_REQUIRE(per_inst == 0 || instance[b * circuits + c], ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: instance %zu is null",
+                           b * circuits + c);
             off[b] = total;
             len[b] = proof_lens[b];
             total += proof_lens[b];
@@ -733,7 +794,8 @@ int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const*
         std::memcpy(kw, key, 32);
         for (size_t b = 0; b < count; b++) {
             if (proof_lens[b]) std::memcpy(bytes.data() + off[b], proofs[b], proof_lens[b]);
-            if (per_inst) std::memcpy(inst.data() + b * per_inst, instance[b], per_inst * sizeof(Fe));
+            for (size_t c = 0; c < circuits && per_inst; c++)
+                std::memcpy(inst.data() + b * per_inst + c * one_inst, instance[b * circuits + c], one_inst * sizeof(Fe));
             rb[b] = Fr::to_raw(rand_fr_host(kw, TAG_VERIFY_BATCH, b));
             if (fe_is_zero(rb[b])) rb[b].l[0] = 1;  // (a zero weight would hide the proof; probability 2^-254)
         }

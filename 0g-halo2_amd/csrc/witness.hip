@@ -921,6 +921,16 @@ int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* i
     return zg_prover_prove_batch_dev(p, count, nullptr, inst, plan->n_instance, rng_keys, proofs, proof_cap, proof_lens, statuses);
 }
 
+int zg_prover_prove_images_multi(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t circuits, const uint8_t* rng_keys,
+                                 uint8_t* proof, size_t proof_cap, size_t* proof_len, zg_fr* outputs) {
+    ZG_REQUIRE(p && plan && images && rng_keys && proof && proof_len && (outputs || !plan->n_instance), ZG_ERR_INVALID_ARG,
+               "zg_prover_prove_images_multi: null argument");
+    void* slots[64];
+    const zg_fr* inst[64];
+    ZG_TRY(images_into_slots("zg_prover_prove_images_multi", p, plan, images, circuits, outputs, slots, inst));
+    return zg_prover_prove_multi_dev(p, circuits, nullptr, inst, plan->n_instance, rng_keys, proof, proof_cap, proof_len);
+}
+
 int zg_prover_check_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, zg_fr* outputs,
                            zg_failure* failures, size_t cap, uint32_t* totals) {
     ZG_REQUIRE(p && plan && images && totals && (outputs || !plan->n_instance) && (failures || cap == 0), ZG_ERR_INVALID_ARG,

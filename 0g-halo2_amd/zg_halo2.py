@@ -78,6 +78,8 @@ ABI_SYMBOLS = [
     "zg_prover_check_batch", "zg_prover_check_batch_dev", "zg_prover_check_images", "zg_permutation_mapping",
     "zg_fr_cube_root", "zg_ctx_set_coset_generator", "zg_ctx_coset_generator", "zg_prover_coset_generator",
     "zg_permutation_sigma", "zg_prover_export_key", "zg_params_lagrange", "zg_params_lagrange_dev", "zg_params_check",
+    "zg_prover_proof_size_multi", "zg_prover_prove_multi", "zg_prover_prove_multi_dev", "zg_prover_prove_images_multi",
+    "zg_verifier_verify_multi",
 ]
 
 # zg_params_check: bits of `failed`
@@ -731,6 +733,58 @@ class Prover:
             _check(st)
         return [bytes(bufs[b][: lens[b]]) for b in range(count)], outputs, list(sts)
 
+    # ---- one proof of several circuit instances (create_proof's `circuits` slice)
+    def proof_size_multi(self, circuits: int) -> int:
+        """zg_prover_proof_size_multi: upper bound of the size of a proof of `circuits` instances, bytes."""
+        fn = self.ctx.lib.zg_prover_proof_size_multi
+        fn.restype = c_size_t
+        fn.argtypes = [c_void_p, c_size_t]
+        return int(fn(self.h, circuits))
+
+    def prove_multi(self, advice, instances, seeds, device=False) -> bytes:
+        """ONE proof of len(seeds) circuit instances (<= the prover's batch): one transcript, one h, one GWC opening.
+        advice / instances / seeds per circuit, as prove_batch takes them (device=True: zg_prover_prove_multi_dev).
+        A lookup failure in any circuit raises ZgError(ZG_ERR_CONSTRAINT)."""
+        count = len(seeds)
+        lib = self.ctx.lib
+        keep = []
+        if advice is None:
+            adv_ptrs = None
+        elif device:
+            adv_ptrs = (c_void_p * count)(*[c_void_p(a) if a else None for a in advice])
+        else:
+            keep = [np.ascontiguousarray(a, dtype=np.uint64) if a is not None else None for a in advice]
+            adv_ptrs = (c_void_p * count)(*[c_void_p(a.ctypes.data) if a is not None else None for a in keep])
+        insts, inst_len = [], 0
+        for b in range(count):
+            i, inst_len = self._inst(instances[b])
+            insts.append(i)
+        inst_ptrs = (c_void_p * max(count, 1))(*[c_void_p(i.ctypes.data) for i in insts])
+        keys = b"".join(rng_key(s) for s in seeds)
+        cap = max(self.proof_size_multi(count), 1)
+        buf = (ctypes.c_uint8 * cap)()
+        plen = c_size_t(0)
+        fn = lib.zg_prover_prove_multi_dev if device else lib.zg_prover_prove_multi
+        _check(fn(self.h, c_size_t(count), adv_ptrs, inst_ptrs, c_size_t(inst_len), keys, buf, c_size_t(cap), ctypes.byref(plen)))
+        return bytes(buf[: plen.value])
+
+    def prove_multi_dev(self, d_advice, instances, seeds) -> bytes:
+        """prove_multi with the advice columns in HBM (device addresses, or None = the slots as they stand)."""
+        return self.prove_multi(d_advice, instances, seeds, device=True)
+
+    def prove_images_multi(self, plan: "WitnessPlan", images: np.ndarray, seeds):
+        """Wnn::proof for len(seeds) images in ONE proof: image bytes -> (proof, outputs uint64[circuits, n_instance, 4])."""
+        count = len(seeds)
+        images = np.ascontiguousarray(images, dtype=np.uint8).reshape(max(count, 1), -1)
+        keys = b"".join(rng_key(s) for s in seeds)
+        cap = max(self.proof_size_multi(count), 1)
+        buf = (ctypes.c_uint8 * cap)()
+        plen = c_size_t(0)
+        outputs = np.zeros((max(count, 1), plan.n_instance, 4), np.uint64)
+        _check(self.ctx.lib.zg_prover_prove_images_multi(self.h, plan.h, _ptr(images), c_size_t(count), keys, buf, c_size_t(cap),
+                                                         ctypes.byref(plen), _ptr(outputs)))
+        return bytes(buf[: plen.value]), outputs
+
     # ---- witness check (Wnn::mock_proof)
     @staticmethod
     def _reports(count, cap, recs, totals):
@@ -901,6 +955,25 @@ class Verifier:
         verdicts = (c_int * count)()
         _check(self.ctx.lib.zg_verifier_verify_batch(self.h, c_size_t(count), pptrs, lens, iptrs, c_size_t(inst_len),
                                                      rng_key(key), verdicts))
+        return list(verdicts)
+
+    def verify_multi(self, proofs, instances, key, circuits: int) -> list:
+        """verify for proofs of `circuits` instances each (Prover.prove_multi): instances[b] = the list of proof b's
+        per-circuit instance arrays.  Verdicts as verify."""
+        count = len(proofs)
+        bufs = [bytes(p) for p in proofs]
+        pptrs = (ctypes.c_char_p * count)(*bufs)
+        lens = (c_size_t * count)(*[len(p) for p in bufs])
+        insts, inst_len = [], 0
+        for b in range(count):
+            assert len(instances[b]) == circuits, "one instance array per circuit of every proof"
+            for c in range(circuits):
+                i, inst_len = Prover._inst(instances[b][c])
+                insts.append(i)
+        iptrs = (c_void_p * max(len(insts), 1))(*[c_void_p(i.ctypes.data) for i in insts])
+        verdicts = (c_int * count)()
+        _check(self.ctx.lib.zg_verifier_verify_multi(self.h, c_size_t(count), c_size_t(circuits), pptrs, lens, iptrs,
+                                                     c_size_t(inst_len), rng_key(key), verdicts))
         return list(verdicts)
 
     def close(self):

@@ -436,6 +436,24 @@ int zg_prover_prove_batch(zg_prover *p, size_t count, const zg_fr *const *advice
 int zg_prover_prove_batch_dev(zg_prover *p, size_t count, void *const *d_advice, const zg_fr *const *instance,
                               size_t instance_len, const uint8_t *rng_keys, uint8_t *const *proofs,
                               size_t proof_cap, size_t *proof_lens, int *statuses);
+/* ONE proof of several instances of the circuit: halo2_proofs::plonk::create_proof's `circuits: &[C]` /
+ * `instances: &[&[&[F]]]` slice (v2023_04_20 src/plonk/prover.rs) -- every instance behind one transcript, one set of
+ * challenges, one quotient h, one random polynomial, one GWC opening.  The `circuits` slots of the prover are the
+ * circuits (1 <= circuits <= zg_prover_batch(p), else ZG_ERR_INVALID_ARG; more than 64, or a point-range shard:
+ * ZG_ERR_UNSUPPORTED).  advice[c], instance[c]: as zg_prover_prove_batch takes them.  rng_keys: circuits x 32 bytes --
+ * circuit c draws its blinding rows from key c (tags and indices of the one-circuit proof), the random polynomial comes
+ * from key 0.  Transcript order, the fold of the quotients and the limits: DESIGN.md section 11.  A lookup failure in ANY
+ * circuit fails the call (ZG_ERR_CONSTRAINT, *proof_len = 0; the message names the circuit).  circuits = 1 gives
+ * zg_prover_prove's bytes.  After such a proof zg_prover_fetch_slot(p, 0, 0, ...) returns the FOLDED h (the proof's
+ * quotient), other slots' item 0 their own circuit's. */
+size_t zg_prover_proof_size_multi(const zg_prover *p, size_t circuits); /* upper bound, bytes */
+int zg_prover_prove_multi(zg_prover *p, size_t circuits, const zg_fr *const *advice, const zg_fr *const *instance,
+                          size_t instance_len, const uint8_t *rng_keys, uint8_t *proof, size_t proof_cap,
+                          size_t *proof_len);
+/* Same with the advice columns in HBM, as zg_prover_prove_batch_dev takes them. */
+int zg_prover_prove_multi_dev(zg_prover *p, size_t circuits, void *const *d_advice, const zg_fr *const *instance,
+                              size_t instance_len, const uint8_t *rng_keys, uint8_t *proof, size_t proof_cap,
+                              size_t *proof_len);
 /* One proof (the batch of one).  advice: [n_advice][2^k] column values (host).  instance: [n_instance][instance_len]
  * public inputs.  proof: receives the transcript bytes (EvmTranscript layout). */
 int zg_prover_prove(zg_prover *p, const zg_fr *advice, const zg_fr *instance, size_t instance_len,
@@ -574,6 +592,9 @@ int zg_witness_run_dev(zg_witness_plan* plan, const uint8_t* images, size_t coun
  * field elements); everything else as zg_prover_prove_batch.  plan and prover must live on the same device. */
 int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, const uint8_t* rng_keys,
                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses);
+/* ... into ONE proof of `circuits` images (zg_prover_prove_multi: create_proof's `circuits` slice); outputs as above. */
+int zg_prover_prove_images_multi(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t circuits,
+                                 const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len, zg_fr* outputs);
 
 /* ------------------------------------------------------------------ witness check
  * Replaces halo2_proofs::dev::MockProver::run followed by MockProver::verify / assert_satisfied (halo2_proofs
@@ -658,6 +679,12 @@ void zg_verifier_destroy(zg_verifier *v);
  * bad proofs whose errors cancel in the weighted sum.  Returns the zg_status of the call itself. */
 int zg_verifier_verify_batch(zg_verifier *v, size_t count, const uint8_t *const *proofs, const size_t *proof_lens,
                              const zg_fr *const *instance, size_t instance_len, const uint8_t key[32], int *verdicts);
+/* The same for proofs of `circuits` instances each (zg_prover_prove_multi; verify_proof's `instances: &[&[&[F]]]`):
+ * instance[b * circuits + c] = the instance columns of circuit c of proof b.  Verdict classes, weights and bisection are
+ * zg_verifier_verify_batch's; circuits = 1 IS that call.  The query tables are built per `circuits` at first use and kept. */
+int zg_verifier_verify_multi(zg_verifier *v, size_t count, size_t circuits, const uint8_t *const *proofs,
+                             const size_t *proof_lens, const zg_fr *const *instance, size_t instance_len,
+                             const uint8_t key[32], int *verdicts);
 /* Host helper (no device): *result = 1 iff prod_i e(p[i], q[i]) = 1 in GT (BN254 optimal ate pairing); identity
  * points contribute 1.  The points are taken to be in G1 and G2.  bn256::multi_miller_loop + final_exponentiation. */
 int zg_pairing_check(const zg_g1_affine *p, const zg_g2_affine *q, size_t n, int *result);

@@ -353,15 +353,17 @@ fn from_be32<F: PrimeField>(b: &[u8]) -> Option<F> {
 
 /// Proof bytes in EvmTranscript layout (points as x || y, scalars, 32-byte big-endian each) ->
 /// the caller's transcript object, in proof order.  Generic: C is G1Affine whenever this runs.
-fn replay<C: CurveAffine, E: EncodedChallenge<C>, T: TranscriptWrite<C, E>>(cs: &ConstraintSystem<C::Scalar>, proof: &[u8],
-                                                                            transcript: &mut T) -> std::io::Result<()> {
+// (`circuits`: the instances of the circuit behind this one proof -- the per-circuit commitments and evaluations are there
+//  that many times, what the circuits share once: DESIGN.md section 11)
+fn replay<C: CurveAffine, E: EncodedChallenge<C>, T: TranscriptWrite<C, E>>(cs: &ConstraintSystem<C::Scalar>, circuits: usize,
+                                                                            proof: &[u8], transcript: &mut T) -> std::io::Result<()> {
     let bad = |what: &'static str| std::io::Error::new(std::io::ErrorKind::InvalidData, what);
     let nl = cs.lookups().len();
     let chunk = cs.degree() - 2;
     let sets = (cs.permutation().get_columns().len() + chunk - 1) / chunk;
-    let points_before_evals = cs.num_advice_columns() + 2 * nl + sets + nl + 1 + (cs.degree() - 1);
-    let scalars = cs.advice_queries().len() + cs.fixed_queries().len() + 1 + cs.permutation().get_columns().len()
-        + if sets > 0 { 3 * sets - 1 } else { 0 } + 5 * nl;
+    let points_before_evals = circuits * (cs.num_advice_columns() + 2 * nl + sets + nl) + 1 + (cs.degree() - 1);
+    let scalars = circuits * (cs.advice_queries().len() + if sets > 0 { 3 * sets - 1 } else { 0 } + 5 * nl)
+        + cs.fixed_queries().len() + 1 + cs.permutation().get_columns().len();
     if proof.len() < 64 * points_before_evals + 32 * scalars || (proof.len() - 64 * points_before_evals - 32 * scalars) % 64 != 0 {
         return Err(bad("zg proof: unexpected length"));
     }
@@ -401,8 +403,12 @@ where
     T: TranscriptWrite<Scheme::Curve, E>,
     ConcreteCircuit: Circuit<Scheme::Scalar>,
 {
-    if std::env::var_os("ZG_HALO2_DISABLE").is_some() || circuits.len() != 1 || instances.len() != 1 {
+    if std::env::var_os("ZG_HALO2_DISABLE").is_some() || circuits.is_empty() || instances.len() != circuits.len() {
         return None;
+    }
+    if circuits.len() > 1 {
+        // several circuits behind one transcript: zg_prover_prove_multi (UNVERIFIED source like the rest of this file)
+        return try_create_proof_multi::<Scheme, E, R, T, ConcreteCircuit>(params, pk, circuits, instances, rng, transcript);
     }
     if TypeId::of::<Scheme>() != TypeId::of::<KZGCommitmentScheme<Bn256>>() {
         return None;
@@ -460,7 +466,78 @@ where
             zg_prover_prove(h.prover, advice.as_ptr() as *const Fr, inst.as_ptr() as *const Fr, inst_len, key32.as_ptr(),
                             buf.as_mut_ptr(), buf.len(), &mut len)
         })?;
-        replay::<Scheme::Curve, E, T>(cs, &buf[..len], transcript).map_err(Error::from)
+        replay::<Scheme::Curve, E, T>(cs, 1, &buf[..len], transcript).map_err(Error::from)
+    })())
+}
+
+/// `create_proof` for `circuits.len() > 1`: one proof of all the instances (`zg_prover_prove_multi`).  A handle of its own
+/// (slot count, throughput form), one 32-byte blinding key per circuit from the caller's RNG.
+fn try_create_proof_multi<'params, Scheme, E, R, T, ConcreteCircuit>(
+    params: &'params Scheme::ParamsProver,
+    pk: &ProvingKey<Scheme::Curve>,
+    circuits: &[ConcreteCircuit],
+    instances: &[&[&[Scheme::Scalar]]],
+    rng: &mut R,
+    transcript: &mut T,
+) -> Option<Result<(), Error>>
+where
+    Scheme: CommitmentScheme + 'static,
+    E: EncodedChallenge<Scheme::Curve>,
+    R: RngCore,
+    T: TranscriptWrite<Scheme::Curve, E>,
+    ConcreteCircuit: Circuit<Scheme::Scalar>,
+{
+    if TypeId::of::<Scheme>() != TypeId::of::<KZGCommitmentScheme<Bn256>>() || std::env::var("ZG_HALO2_TRANSCRIPT").as_deref() != Ok("evm") {
+        return None;
+    }
+    let params_kzg: &ParamsKZG<Bn256> = unsafe { &*(params as *const Scheme::ParamsProver as *const ParamsKZG<Bn256>) };
+    let pk_g1: &ProvingKey<G1Affine> = unsafe { &*(pk as *const ProvingKey<Scheme::Curve> as *const ProvingKey<G1Affine>) };
+    let key = fingerprint(params_kzg, pk_g1, true);
+    let mut cache = PROVERS.lock().unwrap();
+    if !cache.contains_key(&key) {
+        let h = build_handle(params_kzg, pk_g1)?;
+        if unsafe { zg_prover_set_overlap(h.prover, 0) } != 0 {
+            return None;
+        }
+        cache.insert(key, h);
+    }
+    let h = cache.get(&key)?;
+    let count = circuits.len();
+    if count > 64 {
+        return None; // (the library's limit for one proof: the stock prover runs)
+    }
+    if unsafe { zg_prover_batch(h.prover) } < count && unsafe { zg_prover_set_batch(h.prover, count) } != 0 {
+        return None;
+    }
+    let cs = pk.get_vk().cs();
+    Some((|| {
+        let inst_len = instances.iter().flat_map(|i| i.iter()).map(|c| c.len()).max().unwrap_or(0);
+        if inst_len > h.n - (cs.blinding_factors() + 1) {
+            return Err(Error::InstanceTooLarge);
+        }
+        let mut adv = Vec::with_capacity(count);
+        let mut inst = Vec::with_capacity(count);
+        for (c, i) in circuits.iter().zip(instances.iter()) {
+            if i.len() != cs.num_instance_columns() {
+                return Err(Error::InvalidInstances);
+            }
+            adv.push(synthesize(cs, params_kzg.k(), c, i)?);
+            let mut flat = vec![Scheme::Scalar::ZERO; i.len() * inst_len];
+            for (col, v) in i.iter().enumerate() { flat[col * inst_len..col * inst_len + v.len()].copy_from_slice(v); }
+            inst.push(flat);
+        }
+        let adv_ptrs: Vec<*const Fr> = adv.iter().map(|a| a.as_ptr() as *const Fr).collect();
+        let inst_ptrs: Vec<*const Fr> = inst.iter().map(|a| a.as_ptr() as *const Fr).collect();
+        let mut keys = vec![0u8; 32 * count];
+        for c in 0..count { rng.fill_bytes(&mut keys[32 * c..32 * c + 32]); } // one blinding key per circuit
+        let cap = unsafe { zg_prover_proof_size_multi(h.prover, count) };
+        let mut buf = vec![0u8; cap];
+        let mut len = 0usize;
+        check(unsafe {
+            zg_prover_prove_multi(h.prover, count, adv_ptrs.as_ptr(), inst_ptrs.as_ptr(), inst_len, keys.as_ptr(), buf.as_mut_ptr(),
+                                  buf.len(), &mut len)
+        })?;
+        replay::<Scheme::Curve, E, T>(cs, count, &buf[..len], transcript).map_err(Error::from)
     })())
 }
 
