@@ -68,16 +68,18 @@ struct WsBlock {
 struct TwiddleKey {
     uint32_t log_n;
     std::array<uint64_t, 4> omega;
+    std::array<uint64_t, 4> scale;  // the constant every entry carries (one: the plain table)
     bool operator<(const TwiddleKey& o) const {
         if (log_n != o.log_n) return log_n < o.log_n;
-        return omega < o.omega;
+        if (omega != o.omega) return omega < o.omega;
+        return scale < o.scale;
     }
 };
 
 }  // namespace zg
 
 namespace zg {
-// What the contexts of one device share: NTT twiddle tables (omega^i, i < 2^log_n, per (log_n, omega); they live in
+// What the contexts of one device share: NTT twiddle tables (omega^i * s, i < 2^log_n, per (log_n, omega, s); they live in
 // HBM until the last context of the device is destroyed) and the once-per-device kernel attributes.
 struct DeviceState {
     std::mutex mu;
@@ -215,7 +217,7 @@ zg_ctx::ProfRec* prof_slot(zg_ctx* ctx, const char* name, double algo_bytes, dou
     ZG_LAUNCH_U(ctx, name, bytes, 0.0, kernel, grid, block, lds, __VA_ARGS__)
 
 // twiddle table for (log_n, omega), created on first use
-int get_twiddles(zg_ctx* ctx, uint32_t log_n, const Fe& omega, Fe** out);
+int get_twiddles(zg_ctx* ctx, uint32_t log_n, const Fe& omega, Fe** out, const Fe* scale = nullptr);
 
 // host-side constants
 Fe host_domain_omega(uint32_t log_n);

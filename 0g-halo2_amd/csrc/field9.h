@@ -471,6 +471,45 @@ __device__ __forceinline__ void xyzz9_madd(XYZZ9& a, bool& inf, const F9& qx, co
     a.zzz = Fq9::mul(a.zzz, ppp);
 }
 
+// (x1, y1) + (x2, y2), both affine in the nine-limb 2^261 form, into XYZZ (mmadd-2008-s): xyzz9_madd on an accumulator
+// with zz = zzz = 1 spends four of its ten products on multiplications by one; here 2 S + 2 M and the fused pair for Y3.
+// (x1, y1) and x2 are normalised, y2 may arrive with negative limbs (a negated y).  Same case analysis as xyzz9_madd:
+// `inf` is set where the two cancel (out is then not written).  Output normalised.
+__device__ __forceinline__ void xyzz9_from_pair(const F9& x1, const F9& y1, const F9& x2, const F9& y2, XYZZ9& out, bool& inf) {
+    const F9 p = f9_sub(x2, x1);           // limb magnitudes < 2^29: both operands normalised
+    const F9 r = f9_sub(f9_norm(y2), y1);  // (normalised first: the difference of a negated y and y1 could reach 2^30)
+    const F9 pp = Fq9::sqr(p);
+    if (__builtin_expect(pp.l[8] >= 0 && Fq9::is_zero_mod_p(pp), 0)) {
+        const F9 rr = Fq9::sqr(r);
+        if (!Fq9::is_zero_mod_p(rr)) {  // (x2, y2) = -(x1, y1)
+            inf = true;
+            return;
+        }
+        // the same point twice: dbl-2008-s-1 on the affine point, as in xyzz9_madd
+        const F9 u = f9_norm(f9_add(y1, y1));
+        const F9 v = Fq9::sqr(u);
+        const F9 w = Fq9::mul(u, v);
+        const F9 s = Fq9::mul(x1, v);
+        const F9 xx = Fq9::sqr(x1);
+        const F9 m = f9_norm(f9_add(f9_add(xx, xx), xx));
+        const F9 x3 = f9_norm(f9_sub(f9_sub(Fq9::sqr(m), s), s));
+        out.y = f9_norm(f9_sub(Fq9::mul(m, f9_norm(f9_sub(s, x3))), Fq9::mul(w, y1)));
+        out.x = x3;
+        out.zz = v;
+        out.zzz = w;
+        inf = false;
+        return;
+    }
+    const F9 ppp = Fq9::mul(p, pp);
+    const F9 qq = Fq9::mul(x1, pp);
+    const F9 x3 = f9_norm(f9_sub(f9_sub(f9_sub(Fq9::sqr(r), ppp), qq), qq));
+    out.y = Fq9::mul2<true>(r, f9_sub(qq, x3), y1, ppp);  // R (Q - X3) - y1 PPP, one reduction
+    out.x = x3;
+    out.zz = pp;
+    out.zzz = ppp;
+    inf = false;
+}
+
 // dbl-2008-s-1 in the nine-limb form (only reached when an addition meets two equal points)
 __device__ __noinline__ XYZZ9 xyzz9_dbl(const XYZZ9& a) {
     if (xyzz9_is_identity(a)) return a;

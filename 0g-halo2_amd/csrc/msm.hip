@@ -744,6 +744,27 @@ __global__ __launch_bounds__(AFF_TOP) void aff_inv_top_kernel(int32_t* __restric
     }
 }
 
+// One summand into the running sum of a throughput chain.  The first point of a task is kept affine (`aff`: acc.x, acc.y
+// hold it, zz = zzz = 1 unwritten), the second joins it through xyzz9_from_pair -- 6 products, where xyzz9_madd on a copied
+// point spends 4 of its 10 multiplying by one --, the rest are mixed additions.  A pair that cancels leaves the sum empty.
+__device__ __forceinline__ void chain_madd(XYZZ9& acc, bool& inf, bool& aff, const F9& qx, const F9& qy) {
+    if (inf) {
+        acc.x = qx;
+        acc.y = f9_norm(qy);  // (a negated y arrives with negative limbs)
+        inf = false;
+        aff = true;
+    } else if (aff) {
+        aff = false;
+        xyzz9_from_pair(acc.x, acc.y, qx, qy, acc, inf);
+    } else {
+        xyzz9_madd(acc, inf, qx, qy);
+    }
+}
+__device__ __forceinline__ void chain_store(XYZZ9* dst, XYZZ9& acc, bool inf, bool aff) {
+    if (aff) acc.zz = acc.zzz = Fq9Params::one();
+    st_xyzz9(dst, inf ? xyzz9_identity() : acc);
+}
+
 // One lane per task: at most K points of one bucket, mixed adds in XYZZ on nine 29-bit limbs (field9.h:
 // no carry word per partial product, no per-operation modular correction); the partial sum leaves in
 // the library's packed form.
@@ -795,7 +816,7 @@ __global__ __launch_bounds__(256) void msm_accumulate_kernel(
     const uint32_t len = share + (j < extra ? 1u : 0u);
     const uint32_t* so = sorted + (size_t)b * cap + start;
     XYZZ9* dst = partial + (size_t)b * max_tasks + to[k] + j;  // (the bucket-order slot the reduction reads)
-    bool inf = true;
+    bool inf = true, aff = false;
     if constexpr (PAIR) {
         PairAcc acc;
         for (uint32_t e = 0; e < len; e++) {  // (both lanes of a pair see the same entries)
@@ -824,9 +845,9 @@ __global__ __launch_bounds__(256) void msm_accumulate_kernel(
             const F9 qx = f9_unpack(ld_fe_g(&src[e].x));
             const F9 qy = f9_unpack(ld_fe_g(&src[e].y));
             if (f9_limbs_zero(qx) && f9_limbs_zero(qy)) continue;  // (a pad pair, or a pair that cancelled)
-            xyzz9_madd(acc, inf, qx, qy);
+            chain_madd(acc, inf, aff, qx, qy);
         }
-        st_xyzz9(dst, inf ? xyzz9_identity() : acc);
+        chain_store(dst, acc, inf, aff);
     } else {
         XYZZ9 acc;
         for (uint32_t e = 0; e < len; e++) {
@@ -837,9 +858,9 @@ __global__ __launch_bounds__(256) void msm_accumulate_kernel(
             F9 qy = f9_unpack(ld_fe_g(&src->y));
             if (f9_limbs_zero(qx) && f9_limbs_zero(qy)) continue;  // identity base point
             if (ent >> 31) qy = f9_neg(qy);
-            xyzz9_madd(acc, inf, qx, qy);
+            chain_madd(acc, inf, aff, qx, qy);
         }
-        st_xyzz9(dst, inf ? xyzz9_identity() : acc);
+        chain_store(dst, acc, inf, aff);
     }
 }
 

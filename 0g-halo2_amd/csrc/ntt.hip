@@ -6,7 +6,8 @@
 // Structure (MI355X-first, not halo2's recursive butterfly):
 //   N = N1 * N2.  Pass 1 ("cols"): each workgroup stages an [N1][C] tile of C adjacent columns in
 //   LDS, runs the size-N1 DIF butterflies there, multiplies by the inter-pass twiddle
-//   omega^(j2*k1) and writes rows of C contiguous elements.  Pass 2 ("rows"): each workgroup stages
+//   omega^(j2*k1) -- from a table that also carries the transform's constant factor (the ifft
+//   divisor, the 2^5 of the `hat` form: ntt_run) -- and writes rows of C contiguous elements.  Pass 2 ("rows"): each workgroup stages
 //   R contiguous rows of N2, runs the size-N2 butterflies in LDS and writes X[k1 + N1*k2] so that R
 //   neighbouring k1 form one contiguous segment.  Natural order in, natural order out, the
 //   bit-reversal is absorbed into the LDS read index of the store loop.  Twiddles omega^i come
@@ -30,6 +31,8 @@ struct NttArgs {
     const Fe* in;
     Fe* out;
     const Fe* tw;       // omega^i, i < N; entries [N, 2N) hold omega^i * 2^5 (the 2^261 Montgomery form)
+    const Fe* tw_x;     // COLS: what the store loop multiplies entry (j2, k1) by, at [j2 * k1]: omega^i * s in the form the
+                        // pass's arithmetic takes (s: the constant the transform owes every output; ntt_run)
     const Fe* tw_m;     // (nine-limb pass) the same table for the pass's sub-transform: omega_M^t, t < M, then omega_M^t * 2^5
     uint32_t tw_shift;  // (nine-limb pass) LDS holds the sub-transform twiddles whose index is a multiple of 2^tw_shift; the
                         // stages before that read theirs from tw_m (contiguous, L1-resident)
@@ -43,9 +46,9 @@ struct NttArgs {
     uint32_t in_len;    // FIRST pass: input entries beyond in_len read as zero
     uint32_t out_len;   // LAST pass: entries >= out_len are not written
     uint32_t coset_in;  // FIRST pass: 1 = multiply entry j by zin[j % 3] for j % 3 != 0; 2 = all three (zin0 too)
-    uint32_t coset_out; // LAST pass: multiply entry k by zout[k % 3]
+    uint32_t coset_out; // LAST pass: 1 = multiply entry k by zout[k % 3] for k % 3 != 0; 2 = all three (zout0 too)
     uint32_t scale_out; // LAST pass: multiply by `scale`
-    Fe zin0, zin1, zin2, zout1, zout2, scale;
+    Fe zin0, zin1, zin2, zout0, zout1, zout2, scale;
 };
 
 __device__ __forceinline__ uint32_t bitrev(uint32_t v, uint32_t bits) {
@@ -149,10 +152,10 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt_pass_kernel(NttArgs a) {
             if (g < a.in_len) {
                 v = ld_fe(in + g);
                 if (a.coset_in) {
-                    uint32_t m3 = g % 3u;
-                    if (m3 == 1) v = Fr::mul(v, a.zin1);
-                    else if (m3 == 2) v = Fr::mul(v, a.zin2);
-                    else if (a.coset_in == 2) v = Fr::mul(v, a.zin0);
+                    // (the constant is selected, the product written once: a wave holds all three residues and would
+                    // walk one product per branch)
+                    const uint32_t m3 = g % 3u;
+                    if (m3 != 0 || a.coset_in == 2) v = Fr::mul(v, m3 == 1 ? a.zin1 : m3 == 2 ? a.zin2 : a.zin0);
                 }
             } else {
                 v = fe_zero();
@@ -267,8 +270,8 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt_pass_kernel(NttArgs a) {
             uint32_t k1 = bitrev(pos, log_m);
             uint32_t j2 = base + c;
             Fe v = ldx(e);
-            uint32_t ti = j2 * k1;  // < N
-            if (ti != 0) v = Fr::mul(v, ld_fe(a.tw + ti));
+            // (j2 * k1 < N.  Entry 0 too: it is the table's constant, and skipping omega^0 saved a wave nothing)
+            v = Fr::mul(v, ld_fe(a.tw_x + j2 * k1));
             st_fe(out + (size_t)k1 * N2 + j2, v);
         }
     } else {
@@ -280,9 +283,8 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt_pass_kernel(NttArgs a) {
             Fe v = ldx((r << log_m) + pos);
             if (a.scale_out) v = Fr::mul(v, a.scale);
             if (a.coset_out) {
-                uint32_t m3 = k % 3u;
-                if (m3 == 1) v = Fr::mul(v, a.zout1);
-                else if (m3 == 2) v = Fr::mul(v, a.zout2);
+                const uint32_t m3 = k % 3u;
+                if (m3 != 0 || a.coset_out == 2) v = Fr::mul(v, m3 == 1 ? a.zout1 : m3 == 2 ? a.zout2 : a.zout0);
             }
             st_fe(out + k, v);
         }
@@ -357,7 +359,6 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt9_pass_kernel(NttArgs a) 
 
     const Fe* in = a.in + (size_t)(blockIdx.y / a.in_per) * a.in_outer + (size_t)(blockIdx.y % a.in_per) * a.in_stride;
     Fe* out = a.out + (size_t)(blockIdx.y / a.out_per) * a.out_outer + (size_t)(blockIdx.y % a.out_per) * a.out_stride;
-    const Fe* tw9 = a.tw + ((size_t)1 << a.log_n);  // omega^i * 2^5
 
     for (uint32_t t = tid; t < (M / 2) >> S; t += NT) st3(TL, TH, T8, t, f9_unpack(ld_fe(twm9 + (t << S))));
     for (uint32_t e = tid; e < tile; e += NT) {
@@ -374,10 +375,8 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt9_pass_kernel(NttArgs a) 
             if (g < a.in_len) {
                 v = f9_unpack(ld_fe(in + g));
                 if (a.coset_in) {  // (zin*, zout*, scale arrive in the 2^261 form on this path: launch_passes)
-                    uint32_t m3 = g % 3u;
-                    if (m3 == 1) v = Fr9::mul(v, f9_unpack(a.zin1));
-                    else if (m3 == 2) v = Fr9::mul(v, f9_unpack(a.zin2));
-                    else if (a.coset_in == 2) v = Fr9::mul(v, f9_unpack(a.zin0));
+                    const uint32_t m3 = g % 3u;
+                    if (m3 != 0 || a.coset_in == 2) v = Fr9::mul(v, f9_unpack(m3 == 1 ? a.zin1 : m3 == 2 ? a.zin2 : a.zin0));
                 }
             } else {
 #pragma unroll
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt9_pass_kernel(NttArgs a) 
             uint32_t c = e & (cnt - 1), pos = e >> log_cnt;
             uint32_t k1 = bitrev(pos, log_m);
             uint32_t j2 = base + c;
-            const F9 v = Fr9::mul(ldx(e), f9_unpack(ld_fe(tw9 + j2 * k1)));  // (j2 * k1 < N)
+            const F9 v = Fr9::mul(ldx(e), f9_unpack(ld_fe(a.tw_x + j2 * k1)));  // (j2 * k1 < N)
             st_fe(out + (size_t)k1 * N2 + j2, f9_reduce_pack<Fr9Params>(v));
         }
     } else {
@@ -487,22 +486,21 @@ __global__ __launch_bounds__(1 << (LOG_T - 2)) void ntt9_pass_kernel(NttArgs a) 
             F9 v = ldx((r << log_m) + pos);
             if (a.scale_out) v = Fr9::mul(v, f9_unpack(a.scale));
             if (a.coset_out) {
-                uint32_t m3 = k % 3u;
-                if (m3 == 1) v = Fr9::mul(v, f9_unpack(a.zout1));
-                else if (m3 == 2) v = Fr9::mul(v, f9_unpack(a.zout2));
+                const uint32_t m3 = k % 3u;
+                if (m3 != 0 || a.coset_out == 2) v = Fr9::mul(v, f9_unpack(m3 == 1 ? a.zout1 : m3 == 2 ? a.zout2 : a.zout0));
             }
             st_fe(out + k, f9_reduce_pack<Fr9Params>(v));
         }
     }
 }
 
-// tw[i] = omega^i, tw[n + i] = omega^i in the 2^261 Montgomery form (nine-limb butterflies), i < n
-__global__ void twiddle_kernel(Fe* tw, Fe omega, uint32_t n) {
+// tw[i] = omega^i * s, tw[n + i] = the same in the 2^261 Montgomery form (nine-limb butterflies), i < n
+__global__ void twiddle_kernel(Fe* tw, Fe omega, Fe s, uint32_t n) {
     constexpr uint32_t CH = 16;
     uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * CH;
     if (i0 >= n) return;
     const Fe c261 = Fr9Params::c261_fe();
-    Fe cur = Fr::pow_u64(omega, i0);
+    Fe cur = Fr::mul(Fr::pow_u64(omega, i0), s);
     for (uint32_t j = 0; j < CH && i0 + j < n; j++) {
         st_fe(tw + i0 + j, cur);
         st_fe(tw + n + i0 + j, Fr::mul(cur, c261));
@@ -510,12 +508,19 @@ __global__ void twiddle_kernel(Fe* tw, Fe omega, uint32_t n) {
     }
 }
 
-// One table per (device, log_n, omega), shared by every context of the device.  The table is complete (the
+// One table per (device, log_n, omega, scale), shared by every context of the device.  The table is complete (the
 // creating stream is drained) before its pointer is published, so that another context's stream may read it.
-int get_twiddles(zg_ctx* ctx, uint32_t log_n, const Fe& omega, Fe** out) {
+// scale (null: one) multiplies every entry: the table of a two-pass transform's inter-pass product, which then
+// carries the transform's constant factor (ntt_run).  A prover knows a handful of such constants per size; a caller of
+// the stand-alone entries may pass any divisor, so a size keeps at most MAX_SCALED_TABLES scaled tables: beyond that
+// *out is null and the caller applies the constant itself.
+constexpr uint32_t MAX_SCALED_TABLES = 8;
+int get_twiddles(zg_ctx* ctx, uint32_t log_n, const Fe& omega, Fe** out, const Fe* scale) {
+    const Fe s = scale ? *scale : Fr::one();
     TwiddleKey key;
     key.log_n = log_n;
     memcpy(key.omega.data(), &omega, 32);
+    memcpy(key.scale.data(), &s, 32);
     DeviceState& ds = device_state(ctx->device);
     std::lock_guard<std::mutex> lock(ds.mu);
     auto it = ds.twiddles.find(key);
@@ -523,13 +528,22 @@ int get_twiddles(zg_ctx* ctx, uint32_t log_n, const Fe& omega, Fe** out) {
         *out = it->second;
         return ZG_OK;
     }
+    if (scale) {
+        const Fe one = Fr::one();
+        uint32_t scaled = 0;
+        for (const auto& kv : ds.twiddles) scaled += kv.first.log_n == log_n && memcmp(kv.first.scale.data(), &one, 32) != 0;
+        if (scaled >= MAX_SCALED_TABLES) {
+            *out = nullptr;
+            return ZG_OK;
+        }
+    }
     uint32_t n = 1u << log_n;
     Fe* tw = nullptr;
     gate_yield(ctx);  // (a new table: an allocation and a stream synchronisation)
     ZG_HIP(hipMalloc(&tw, (size_t)2 * n * sizeof(Fe)));
     uint32_t threads = 256, per = 16;
     uint32_t blocks = (n + threads * per - 1) / (threads * per);
-    hipLaunchKernelGGL(twiddle_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, tw, omega, n);
+    hipLaunchKernelGGL(twiddle_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, tw, omega, s, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
@@ -552,9 +566,11 @@ struct NttPlan {
     Fe omega;
     uint32_t in_len, out_len;
     Grouping grp;           // how the caller's arrays are laid out (the workspace between the passes is flat)
-    uint32_t coset_in = 0;  // 0 none, 1 zeta^(j%3) on j%3 != 0, 2 all entries (zin0 too)
-    bool coset_out = false, scale_out = false;
-    Fe zin0, zin1, zin2, zout1, zout2, scale;
+    uint32_t coset_in = 0;   // 0 none, 1 zeta^(j%3) on j%3 != 0, 2 all entries (zin0 too)
+    uint32_t coset_out = 0;  // the same for the outputs (zout*)
+    bool scale_out = false;  // every output times `scale`
+    bool hat = false;        // every output times 2^5 (the 2^261 form evaluate_h works in)
+    Fe zin0, zin1, zin2, zout0, zout1, zout2, scale;
 };
 
 // (nine-limb pass) the sub-transform's own twiddle table -- omega_M = omega^(N / M), contiguous -- and how much of it the pass
@@ -578,22 +594,23 @@ static size_t nine_lds_bytes(uint32_t T, uint32_t log_m, uint32_t shift) {
 }
 
 template <int LOG_T, bool NINE>
-static int launch_passes(zg_ctx* ctx, const NttPlan& p, const Fe* tw, Fe* tmp, size_t tmp_stride) {
+static int launch_passes(zg_ctx* ctx, const NttPlan& p, const Fe* tw, const Fe* tw_x, Fe* tmp, size_t tmp_stride) {
     constexpr uint32_t T = 1u << LOG_T;
     constexpr size_t ELEM = NINE ? 36 : sizeof(Fe);
     NttArgs a;
     memset(&a, 0, sizeof(a));
     a.tw = tw;
+    a.tw_x = tw_x;
     a.log_n = p.log_n;
     a.in_len = p.in_len;
     a.out_len = p.out_len;
     a.coset_in = p.coset_in;
     a.coset_out = p.coset_out;
     a.scale_out = p.scale_out;
-    a.zin0 = p.zin0; a.zin1 = p.zin1; a.zin2 = p.zin2; a.zout1 = p.zout1; a.zout2 = p.zout2; a.scale = p.scale;
+    a.zin0 = p.zin0; a.zin1 = p.zin1; a.zin2 = p.zin2; a.zout0 = p.zout0; a.zout1 = p.zout1; a.zout2 = p.zout2; a.scale = p.scale;
     if (NINE) {  // the nine-limb pass multiplies x * 2^256 by constants in the 2^261 form (c * 2^5 here)
         const Fe c261 = Fr9Params::c261_fe();
-        for (Fe* c : {&a.zin0, &a.zin1, &a.zin2, &a.zout1, &a.zout2, &a.scale}) *c = Fr::mul(*c, c261);
+        for (Fe* c : {&a.zin0, &a.zin1, &a.zin2, &a.zout0, &a.zout1, &a.zout2, &a.scale}) *c = Fr::mul(*c, c261);
     }
     const uint32_t N = 1u << p.log_n;
     const uint32_t gper = p.grp.per ? p.grp.per : 0xffffffffu;
@@ -676,9 +693,10 @@ static int launch_passes(zg_ctx* ctx, const NttPlan& p, const Fe* tw, Fe* tmp, s
 static uint32_t ntt_log_t(uint32_t log_n) { return log_n <= 16 ? 10u : 11u; }
 bool ntt_needs_tmp(uint32_t log_n) { return log_n > ntt_log_t(log_n); }
 
-int ntt_run(zg_ctx* ctx, const NttPlan& p, Fe* tmp, size_t tmp_stride) {
-    ZG_REQUIRE(p.log_n <= 22, ZG_ERR_UNSUPPORTED, "ntt: log_n %u > 22 not built", p.log_n);
-    if (p.batch == 0) return ZG_OK;
+int ntt_run(zg_ctx* ctx, const NttPlan& plan, Fe* tmp, size_t tmp_stride) {
+    ZG_REQUIRE(plan.log_n <= 22, ZG_ERR_UNSUPPORTED, "ntt: log_n %u > 22 not built", plan.log_n);
+    if (plan.batch == 0) return ZG_OK;
+    NttPlan p = plan;
     Fe* tw = nullptr;
     ZG_TRY(get_twiddles(ctx, p.log_n, p.omega, &tw));
     // nine-limb butterflies in the latency form (a lone proof: its transforms finish 7-15 % sooner), 8 x 32-bit ones in the
@@ -686,8 +704,56 @@ int ntt_run(zg_ctx* ctx, const NttPlan& p, Fe* tmp, size_t tmp_stride) {
     // LDS full at four workgroups, 27 % more multiply-adds and a 0.7 % lower clock -- DESIGN.md section 5); ZG_NTT9 = 0 / 1 forces one
     const int k9 = knob(K_NTT9);
     const bool nine = k9 < 0 ? ctx->msm_pair : k9 != 0;
-    if (ntt_log_t(p.log_n) == 10) return nine ? launch_passes<10, true>(ctx, p, tw, tmp, tmp_stride) : launch_passes<10, false>(ctx, p, tw, tmp, tmp_stride);
-    return nine ? launch_passes<11, true>(ctx, p, tw, tmp, tmp_stride) : launch_passes<11, false>(ctx, p, tw, tmp, tmp_stride);
+    // The constant a transform owes every output -- `scale` (the ifft divisor), the 2^5 of `hat` -- costs a product per
+    // element at the edge it is applied at.  A two-pass transform already has one table-driven product per element, between
+    // its passes, and the transform is linear: there the constant rides on that table (omega^i * s, get_twiddles) and the
+    // edges keep only the coset factors of the entries with index % 3 != 0.  A single pass has no such product (nor has a
+    // transform whose size already holds MAX_SCALED_TABLES other constants): `scale` joins the three output coset constants
+    // where there are any (else it stays at the store), 2^5 the three input ones.
+    const Fe c32 = Fr::from_u64(32);
+    const size_t half = (size_t)1 << p.log_n;
+    // A table's second half is its first times 2^5 -- 2^261 mod r (c261_fe) is the field element 32 --: what the nine-limb
+    // pass multiplies by (its operands are in the 2^261 form), and the 8 x 32-bit pass's table for s = 2^5.
+    const Fe c261 = Fr9Params::c261_fe();
+    ZG_REQUIRE(memcmp(&c261, &c32, sizeof(Fe)) == 0, ZG_ERR_UNSUPPORTED, "ntt: 2^261 mod r is not the field element 32");
+    const Fe* tw_x = tw + (nine ? half : 0);
+    bool rides = false;  // the constant is on the inter-pass table
+    if (ntt_needs_tmp(p.log_n) && (p.scale_out || p.hat)) {
+        if (!nine && !p.scale_out) {
+            tw_x = tw + half;
+            rides = true;
+        } else {
+            Fe s = p.scale_out ? p.scale : Fr::one();
+            if (p.hat) s = Fr::mul(s, c32);
+            Fe* tws = nullptr;
+            ZG_TRY(get_twiddles(ctx, p.log_n, p.omega, &tws, &s));
+            if (tws) {
+                tw_x = tws + (nine ? half : 0);
+                rides = true;
+            }
+        }
+    }
+    if (rides) {
+        p.scale_out = false;
+    } else {
+        if (p.hat) {
+            ZG_REQUIRE(p.coset_in == 1, ZG_ERR_UNSUPPORTED, "ntt: a hat transform without coset constants");
+            p.coset_in = 2;
+            p.zin0 = c32;
+            p.zin1 = Fr::mul(p.zin1, c32);
+            p.zin2 = Fr::mul(p.zin2, c32);
+        }
+        if (p.scale_out && p.coset_out == 1) {
+            p.coset_out = 2;
+            p.zout0 = p.scale;
+            p.zout1 = Fr::mul(p.zout1, p.scale);
+            p.zout2 = Fr::mul(p.zout2, p.scale);
+            p.scale_out = false;
+        }
+    }
+    if (ntt_log_t(p.log_n) == 10)
+        return nine ? launch_passes<10, true>(ctx, p, tw, tw_x, tmp, tmp_stride) : launch_passes<10, false>(ctx, p, tw, tw_x, tmp, tmp_stride);
+    return nine ? launch_passes<11, true>(ctx, p, tw, tw_x, tmp, tmp_stride) : launch_passes<11, false>(ctx, p, tw, tw_x, tmp, tmp_stride);
 }
 
 static int ensure_lds_attr(zg_ctx* ctx) {
@@ -754,8 +820,8 @@ int ntt_batch_dev(zg_ctx* ctx, Fe* d_a, size_t stride, size_t batch, uint32_t lo
 
 
 // hat: the evaluations come out multiplied by 2^5, i.e. in the 2^261 Montgomery form evaluate_h's
-// nine-limb arithmetic works in (the factor rides on the coset constants: one extra product for the
-// entries with j % 3 == 0, n of the 8n loaded)
+// nine-limb arithmetic works in (the factor rides on the inter-pass table of a two-pass transform, on the
+// coset constants of a single pass: ntt_run)
 int coeff_to_extended_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, Fe* d_out, size_t out_stride,
                           size_t batch, uint32_t k, uint32_t ext_k, bool hat) {
     return coeff_to_coset_dev(ctx, d_in, in_stride, 1u << k, d_out, out_stride, batch, ext_k, hat, ctx->coset_gen, nullptr);
@@ -782,13 +848,7 @@ int coeff_to_coset_dev(zg_ctx* ctx, const Fe* d_in, size_t in_stride, uint32_t i
     p.zin0 = Fr::one();
     p.zin1 = shift;
     p.zin2 = Fr::sqr(shift);
-    if (hat) {
-        const Fe c32 = Fr::from_u64(32);
-        p.coset_in = 2;
-        p.zin0 = c32;
-        p.zin1 = Fr::mul(p.zin1, c32);
-        p.zin2 = Fr::mul(p.zin2, c32);
-    }
+    p.hat = hat;  // (ntt_run: on the inter-pass table, or on the three coset constants of a single pass)
     size_t n = (size_t)1 << ext_k;
     Fe* tmp = nullptr;
     if (ntt_needs_tmp(ext_k)) {
@@ -824,7 +884,7 @@ int coset_to_coeff_dev(zg_ctx* ctx, Fe* d_evals, uint32_t ext_k, size_t out_len,
     p.out_len = (uint32_t)out_len;
     p.scale_out = true;
     p.scale = Fr::inv(Fr::from_u64((uint64_t)n * (unhat ? 32u : 1u)));
-    p.coset_out = true;
+    p.coset_out = 1;
     p.zout1 = Fr::sqr(shift);  // shift^-1 (shift^3 = 1)
     p.zout2 = shift;           // shift^-2
     Fe* tmp = nullptr;

@@ -149,9 +149,10 @@ __global__ __launch_bounds__(256) void lookup_compress_kernel(DevCircuit c, Cols
     const DLookup* lk = c.lookups + l;
     l += b * c.n_lookups;  // (outputs: lookup l of proof b)
     Fe ai = fe_zero(), ti = fe_zero();
-    for (uint32_t e = 0; e < lk->width; e++) {
-        ai = Fr::add(Fr::mul(ai, theta), eval_poly(c, cols, lk->inputs[e], row));
-        ti = Fr::add(Fr::mul(ti, theta), eval_poly(c, cols, lk->tables[e], row));
+    for (uint32_t e = 0; e < lk->width; e++) {  // (the first expression enters as it is: evaluate_h9_kernel's `compress`)
+        const Fe in = eval_poly(c, cols, lk->inputs[e], row), tb = eval_poly(c, cols, lk->tables[e], row);
+        ai = e ? Fr::add(Fr::mul(ai, theta), in) : in;
+        ti = e ? Fr::add(Fr::mul(ti, theta), tb) : tb;
     }
     stg(cin + (size_t)l * n + row, ai);
     stg(ctab + (size_t)l * n + row, ti);
@@ -756,9 +757,10 @@ __global__ __launch_bounds__(256) void evaluate_h_kernel(EvalHArgs a, uint32_t e
     for (uint32_t l = 0; l < c.n_lookups; l++) {
         const DLookup* lk = c.lookups + l;
         Fe ai = fe_zero(), ti = fe_zero();
-        for (uint32_t e = 0; e < lk->width; e++) {
-            ai = Fr::add(Fr::mul(ai, theta), eval_poly(c, pr.cols, lk->inputs[e], idx));
-            ti = Fr::add(Fr::mul(ti, theta), eval_poly(c, pr.cols, lk->tables[e], idx));
+        for (uint32_t e = 0; e < lk->width; e++) {  // (the first expression enters as it is)
+            const Fe in = eval_poly(c, pr.cols, lk->inputs[e], idx), tb = eval_poly(c, pr.cols, lk->tables[e], idx);
+            ai = e ? Fr::add(Fr::mul(ai, theta), in) : in;
+            ti = e ? Fr::add(Fr::mul(ti, theta), tb) : tb;
         }
         const Fe* zc = pr.lz_cos + (size_t)l * en;
         const Fe* ap = pr.pin_cos + (size_t)l * a.perm_stride;
