@@ -80,6 +80,7 @@ ABI_SYMBOLS = [
     "zg_permutation_sigma", "zg_prover_export_key", "zg_params_lagrange", "zg_params_lagrange_dev", "zg_params_check",
     "zg_prover_proof_size_multi", "zg_prover_prove_multi", "zg_prover_prove_multi_dev", "zg_prover_prove_images_multi",
     "zg_verifier_verify_multi",
+    "zg_wnn_create", "zg_wnn_destroy", "zg_wnn_predict", "zg_wnn_predict_dev", "zg_wnn_accuracy",
 ]
 
 # zg_params_check: bits of `failed`
@@ -979,6 +980,81 @@ class Verifier:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.zg_verifier_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+class Wnn:
+    """zg_wnn: the cleartext model (Wnn::predict and the compute-accuracy loop) on one GPU.  `model` is an object with the
+    fields of harness/wnn_model.Wnn (num_classes, num_filter_entries, num_filter_hashes, num_filter_inputs, p, bloom_filters
+    (classes, filters, entries), input_permutation, binarization_thresholds (w, h, bits_per_input)), or a dict of those."""
+
+    FIELDS = ("num_classes", "num_filter_entries", "num_filter_hashes", "num_filter_inputs", "p", "bloom_filters",
+              "input_permutation", "binarization_thresholds")
+
+    def __init__(self, ctx: Ctx, model=None, **arrays):
+        self.ctx = ctx
+        lib = ctx.lib
+        lib.zg_wnn_destroy.argtypes = [c_void_p]
+        lib.zg_wnn_destroy.restype = None
+        get = (lambda f: model[f]) if isinstance(model, dict) else (lambda f: getattr(model, f))
+        v = {f: arrays[f] if f in arrays else get(f) for f in self.FIELDS}
+        bloom = np.ascontiguousarray(v["bloom_filters"], dtype=np.uint8)
+        perm = np.ascontiguousarray(v["input_permutation"], dtype=np.uint64)
+        thr = np.ascontiguousarray(v["binarization_thresholds"], dtype=np.uint16)
+        assert thr.ndim == 3 and bloom.ndim == 3 and perm.ndim == 1, "thresholds (w, h, bpi), bloom (classes, filters, entries)"
+        self.num_classes = int(v["num_classes"])
+        self.width, self.height, self.bits_per_input = (int(x) for x in thr.shape)
+        n, entries = int(v["num_filter_inputs"]), int(v["num_filter_entries"])
+        bits = self.width * self.height * self.bits_per_input
+        # the C entry takes pointers: the arrays must have the sizes it will read
+        assert perm.shape[0] == bits, "input_permutation has one entry per thermometer bit"
+        assert n < 1 or bloom.shape == (self.num_classes, bits // n, entries), "bloom_filters is (classes, filters, entries)"
+        h = c_void_p()
+        _check(lib.zg_wnn_create(ctx.h, c_uint32(self.num_classes), c_uint32(self.width), c_uint32(self.height),
+                                 c_uint32(self.bits_per_input), c_uint32(n), c_uint32(entries),
+                                 c_uint32(int(v["num_filter_hashes"])), ctypes.c_uint64(int(v["p"])), _ptr(bloom), _ptr(perm),
+                                 _ptr(thr), ctypes.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def _images(self, images) -> np.ndarray:
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        images = images.reshape(-1, self.width * self.height) if images.size else images.reshape(0, self.width * self.height)
+        return images
+
+    def predict(self, images) -> np.ndarray:
+        """images: uint8[count, w, h] (or [count, w*h]); returns the class scores, uint64[count, num_classes]."""
+        images = self._images(images)
+        scores = np.zeros((images.shape[0], self.num_classes), np.uint64)
+        _check(self.ctx.lib.zg_wnn_predict(self.h, _ptr(images), c_size_t(images.shape[0]), _ptr(scores)))
+        return scores
+
+    def predict_dev(self, d_images: int, count: int, d_scores: int):
+        """Device addresses (count * w * h bytes in, count * num_classes uint64 out); asynchronous: Ctx.sync() before reading."""
+        _check(self.ctx.lib.zg_wnn_predict_dev(self.h, c_void_p(d_images), c_size_t(count), c_void_p(d_scores)))
+
+    def accuracy(self, images, labels, predictions: bool = True, confusion: bool = True):
+        """(correct, predictions uint32[count] or None, confusion uint64[classes, classes] (label, prediction) or None)."""
+        images = self._images(images)
+        labels = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        assert labels.shape[0] == images.shape[0], "one label per image"
+        pred = np.zeros(images.shape[0], np.uint32) if predictions else None
+        conf = np.zeros((self.num_classes, self.num_classes), np.uint64) if confusion else None
+        correct = ctypes.c_uint64(0)
+        _check(self.ctx.lib.zg_wnn_accuracy(self.h, _ptr(images), _ptr(labels), c_size_t(images.shape[0]),
+                                            _ptr(pred) if predictions else None, ctypes.byref(correct),
+                                            _ptr(conf) if confusion else None))
+        return int(correct.value), pred, conf
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.zg_wnn_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -689,6 +689,45 @@ int zg_verifier_verify_multi(zg_verifier *v, size_t count, size_t circuits, cons
  * points contribute 1.  The points are taken to be in G1 and G2.  bn256::multi_miller_loop + final_exponentiation. */
 int zg_pairing_check(const zg_g1_affine *p, const zg_g2_affine *q, size_t n, int *result);
 
+/* ------------------------------------------------------------------ WNN model (cleartext inference)
+ * Replaces Wnn::predict (/root/reference/src/wnn.rs:78-173: thermometer_encoding, mish_mash_hash, encode_image,
+ * bloom_filter_lookup, predict) for a batch of images, and the loop of the CLI's compute-accuracy
+ * (/root/reference/src/main.rs:186-213) with its argmax (/root/reference/src/utils.rs:35-45): the cleartext model whose
+ * inference every proof is about.  The object is built from the fields of `Wnn` (wnn.rs:52-76) as io.rs's load_wnn leaves
+ * them; no recorded program is involved.  Integer arithmetic: every output is the reference's, bit for bit.
+ *   filters       = (width * height * bits_per_input) / num_filter_inputs, floor (chunks_exact drops a partial chunk)
+ *   bit[b*W*H + i*H + j] = image[i*H + j] >= thresholds[(i*H + j) * bits_per_input + b]   (16-bit comparison: a threshold of
+ *                   0 is always met, one of 256 never)
+ *   filter f's index x = permuted bits f*n .. f*n + n - 1, the first one bit 0, where permuted bit t = bit[input_permutation[t]]
+ *                   (any in-range map, not only permutations)
+ *   h             = (x * x * x mod p) mod entries^hashes as exact integers; index i = (h / entries^i) mod entries
+ *   score[c]      = the number of filters f with bloom_filters[c][f][index i] non-zero for every i < hashes
+ * zg_wnn_create checks everything on the host before anything is uploaded: a null pointer, a zero dimension / entries /
+ * hashes / p, num_filter_inputs outside 1..64, filters = 0, a permutation entry >= the bit count or a threshold > 256 are
+ * ZG_ERR_INVALID_ARG; num_classes > 64, images of more than 16384 pixels, 2^31 input bits or a table of 2^32 (filter, entry) pairs and beyond
+ * are ZG_ERR_UNSUPPORTED.
+ * Resident size: filters * entries words of 4 bytes (8 beyond 32 classes) + filters * num_filter_inputs * 4 bytes
+ * (DESIGN.md section 12).  The model lives on its context and must be destroyed before it. */
+typedef struct zg_wnn zg_wnn;
+int zg_wnn_create(zg_ctx *ctx, uint32_t num_classes, uint32_t width, uint32_t height, uint32_t bits_per_input,
+                  uint32_t num_filter_inputs, uint32_t num_filter_entries, uint32_t num_filter_hashes, uint64_t p,
+                  const uint8_t *bloom_filters,        /* [classes][filters][entries], 0 / non-zero (Array3<bool>) */
+                  const uint64_t *input_permutation,   /* [width*height*bits_per_input]                              */
+                  const uint16_t *thresholds,          /* [width][height][bits_per_input], 0..256                    */
+                  zg_wnn **out);
+void zg_wnn_destroy(zg_wnn *m);
+/* images: [count][width*height] bytes; scores: [count][num_classes].  count = 0 is ZG_OK and launches nothing.  The host
+ * form returns when the scores are written; the _dev form takes device pointers and is asynchronous on the context stream. */
+int zg_wnn_predict(zg_wnn *m, const uint8_t *images, size_t count, uint64_t *scores);
+int zg_wnn_predict_dev(zg_wnn *m, const void *d_images, size_t count, void *d_scores);
+/* compute-accuracy: prediction = argmax of utils.rs (the first index of the strict maximum; class 0 when every score is
+ * 0), *correct = how many predictions equal their label, confusion[label * num_classes + prediction] counts the pairs.
+ * predictions ([count]) and confusion ([classes][classes]) may be NULL.  A label >= num_classes is ZG_ERR_INVALID_ARG
+ * (checked before any launch).  Host pointers, blocking. */
+int zg_wnn_accuracy(zg_wnn *m, const uint8_t *images, const uint32_t *labels, size_t count,
+                    uint32_t *predictions /* [count] or NULL */, uint64_t *correct,
+                    uint64_t *confusion   /* [classes][classes] (label, prediction) or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
