@@ -1,4 +1,5 @@
-// Nine 29-bit limbs: the register form of Fq used inside the MSM bucket accumulation (device only).
+// Nine 29-bit limbs: the register form of Fq used inside the MSM bucket accumulation.  Kernels only; everything up to
+// xyzz9_add / xyzz9_to_xyzz is plain C++ and also compiles for the host, where tests/abi/field9_probe.hip runs it.
 //
 // Why: with 32-bit limbs a column of partial products overflows a 64-bit accumulator after one
 // product, so every v_mad_u64_u32 drags a v_addc_co_u32 behind it (128 + 128 per Montgomery product).
@@ -29,16 +30,16 @@ struct F9 {
 constexpr int32_t MASK29 = (1 << 29) - 1;
 
 struct Fq9Params {
-    static __device__ __forceinline__ int32_t p(int i) {
+    static ZG_HD int32_t p(int i) {
         constexpr int32_t P[9] = {0x187cfd47, 0x010460b6, 0x1c72a34f, 0x02d522d0, 0x1585d978,
                                   0x02db40c0, 0x00a6e141, 0x0e5c2634, 0x0030644e};
         return P[i];
     }
     static constexpr uint32_t INV29 = 0x04866389u;  // -p^-1 mod 2^29
-    static __device__ __forceinline__ F9 one() {    // 2^261 mod p
+    static ZG_HD F9 one() {    // 2^261 mod p
         return F9{{0x157ccc21, 0x141c2758, 0x185230d3, 0x014c0419, 0x0aa36fb9, 0x1d4240ce, 0x11d54c07, 0x052ac7a8, 0x000dc836}};
     }
-    static __device__ __forceinline__ F9 k256() {   // 2^256 mod p: mul9(x * 2^261, k256) = x * 2^256
+    static ZG_HD F9 k256() {   // 2^256 mod p: mul9(x * 2^261, k256) = x * 2^256
         return F9{{0x058f0d9d, 0x1aea1c6e, 0x11c2cf74, 0x11d651eb, 0x1462c0a7, 0x11b7bc3c, 0x1cbd99ba, 0x183340fb, 0x000e0a77}};
     }
     // 2^261 mod p as an 8 x 32-bit integer: Fq::mul(X, c261) = X * 2^5, i.e. x*2^256 -> x*2^261
@@ -46,19 +47,19 @@ struct Fq9Params {
         return Fe{{0x157ccc21u, 0x4e8384ebu, 0x0ce148c3u, 0xfb90a602u, 0x819caa36u, 0x5301fa84u, 0x563d4475u, 0x0dc83629u}};
     }
     // 2^271 mod p: Fq::inv of the packed form of x * 2^261 returns x^-1 * 2^251; mul9(that, k271) = x^-1 * 2^261
-    static __device__ __forceinline__ F9 k271() {
+    static ZG_HD F9 k271() {
         return F9{{0x1d1c9c4b, 0x08a372ee, 0x1273abad, 0x17c9d397, 0x1698b0a7, 0x09c89e50, 0x177e12ab, 0x185f3518, 0x001ed378}};
     }
 };
 
 struct Fr9Params {
-    static __device__ __forceinline__ int32_t p(int i) {
+    static ZG_HD int32_t p(int i) {
         constexpr int32_t P[9] = {0x10000001, 0x1f0fac9f, 0x0e5c2450, 0x07d090f3, 0x1585d283,
                                   0x02db40c0, 0x00a6e141, 0x0e5c2634, 0x0030644e};
         return P[i];
     }
     static constexpr uint32_t INV29 = 0x0fffffffu;
-    static __device__ __forceinline__ F9 one() {  // 2^261 mod r
+    static ZG_HD F9 one() {  // 2^261 mod r
         return F9{{0x0fffff57, 0x1ea70ab4, 0x052c068b, 0x17504f49, 0x0aa8075b, 0x1d4240ce, 0x11d54c07, 0x052ac7a8, 0x000dc836}};
     }
     // 2^261 mod r as an 8 x 32-bit integer: Fr::mul(X, c261) = X * 2^5, i.e. x*2^256 -> x*2^261
@@ -68,7 +69,7 @@ struct Fr9Params {
 };
 
 // 8 x 32-bit packed (canonical, < 2^256) -> normalised limbs
-__device__ __forceinline__ F9 f9_unpack(const Fe& a) {
+ZG_HD F9 f9_unpack(const Fe& a) {
     F9 o;
     o.l[0] = (int32_t)(a.l[0] & (uint32_t)MASK29);
 #pragma unroll
@@ -82,7 +83,7 @@ __device__ __forceinline__ F9 f9_unpack(const Fe& a) {
 }
 
 // canonical normalised limbs (all in [0, 2^29), value < 2^256) -> packed
-__device__ __forceinline__ Fe f9_pack(const F9& a) {
+ZG_HD Fe f9_pack(const F9& a) {
     Fe o;
 #pragma unroll
     for (int w = 0; w < 8; w++) {
@@ -96,7 +97,7 @@ __device__ __forceinline__ Fe f9_pack(const F9& a) {
 }
 
 // carry propagation: l[0..7] into [0, 2^29), l[8] takes the signed remainder (value unchanged)
-__device__ __forceinline__ F9 f9_norm(const F9& a) {
+ZG_HD F9 f9_norm(const F9& a) {
     F9 o;
     int32_t c = 0;
 #pragma unroll
@@ -109,25 +110,25 @@ __device__ __forceinline__ F9 f9_norm(const F9& a) {
     return o;
 }
 
-__device__ __forceinline__ F9 f9_add(const F9& a, const F9& b) {
+ZG_HD F9 f9_add(const F9& a, const F9& b) {
     F9 o;
 #pragma unroll
     for (int i = 0; i < 9; i++) o.l[i] = a.l[i] + b.l[i];
     return o;
 }
-__device__ __forceinline__ F9 f9_sub(const F9& a, const F9& b) {
+ZG_HD F9 f9_sub(const F9& a, const F9& b) {
     F9 o;
 #pragma unroll
     for (int i = 0; i < 9; i++) o.l[i] = a.l[i] - b.l[i];
     return o;
 }
-__device__ __forceinline__ F9 f9_neg(const F9& a) {
+ZG_HD F9 f9_neg(const F9& a) {
     F9 o;
 #pragma unroll
     for (int i = 0; i < 9; i++) o.l[i] = -a.l[i];
     return o;
 }
-__device__ __forceinline__ bool f9_limbs_zero(const F9& a) {
+ZG_HD bool f9_limbs_zero(const F9& a) {
     int32_t o = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++) o |= a.l[i];
@@ -138,7 +139,7 @@ template <class P>
 struct Field9 {
     // a * b * 2^-261 mod p.  Operand limb magnitudes < 2^29 (one of them may reach 2^30); operand
     // values of magnitude < 2^258.  Result normalised, value in (-2^256, 2^256 + p).
-    static __device__ __forceinline__ F9 mul(const F9& a, const F9& b) {
+    static ZG_HD F9 mul(const F9& a, const F9& b) {
         int64_t acc = 0;
         int32_t m[9];
         F9 r;
@@ -166,10 +167,52 @@ struct Field9 {
         r.l[8] = (int32_t)acc;
         return r;
     }
+    // mul that also hands out the quotient of its reduction, q (limbs in [0, 2^29)): result * 2^261 = a b + q p.
+    // Two products that different lanes reduce apart can then be subtracted as ONE reduction would (sub_fused).
+    static ZG_HD F9 mulq(const F9& a, const F9& b, F9& q) {
+        int64_t acc = 0;
+        F9 r;
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) {
+                const int j = k - i;
+                if (j >= 0 && j < 9) acc += (int64_t)a.l[i] * (int64_t)b.l[j];
+            }
+#pragma unroll
+            for (int i = 0; i < 9; i++) {
+                const int j = k - i;
+                if (i < k && j >= 0 && j < 9) acc += (int64_t)q.l[i] * (int64_t)P::p(j);
+            }
+            if (k < 9) {
+                q.l[k] = (int32_t)(((uint32_t)acc * P::INV29) & (uint32_t)MASK29);
+                acc += (int64_t)q.l[k] * (int64_t)P::p(0);
+                acc >>= 29;
+            } else {
+                r.l[k - 9] = (int32_t)((uint32_t)acc & (uint32_t)MASK29);
+                acc >>= 29;
+            }
+        }
+        r.l[8] = (int32_t)acc;
+        return r;
+    }
+    // h - k for h = mulq(a, b, qh) and k = mulq(c, d, qk): limb for limb what mul2<true>(a, b, c, d) returns.
+    // h - k = (a b - c d + (qh - qk) p) / 2^261, and the one reduction's quotient is (qh - qk) mod 2^261: one p
+    // more where qh < qk, which the borrow of the limb-wise difference tells.  Result normalised.
+    static ZG_HD F9 sub_fused(const F9& h, const F9& qh, const F9& k, const F9& qk) {
+        int32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < 9; i++) c = (qh.l[i] - qk.l[i] + c) >> 29;  // -1 where qh < qk, else 0
+        F9 o;
+#pragma unroll
+        for (int i = 0; i < 9; i++) o.l[i] = h.l[i] - k.l[i] + (P::p(i) & c);
+        return f9_norm(o);
+    }
+
     // (a*b + c*d) * 2^-261 (SUB: a*b - c*d) with ONE Montgomery reduction: 81 + 81 + 81 mads instead of
     // 2 * 162.  All four operands need limb magnitudes < 2^29 (a column then holds 27 * 2^58 < 2^63).
     template <bool SUB>
-    static __device__ __forceinline__ F9 mul2(const F9& a, const F9& b, const F9& c, const F9& d) {
+    static ZG_HD F9 mul2(const F9& a, const F9& b, const F9& c, const F9& d) {
         int64_t acc = 0;
         int32_t m[9];
         F9 r;
@@ -203,8 +246,9 @@ struct Field9 {
     }
 
     // a * a * 2^-261: the 36 cross products are taken once against the doubled operand (limbs < 2^30,
-    // which the accumulator bound allows on one side) -- 45 + 81 mads instead of 81 + 81.
-    static __device__ __forceinline__ F9 sqr(const F9& a) {
+    // which the accumulator bound allows on one side) -- 45 + 81 mads instead of 81 + 81.  The doubled copy IS that
+    // one side: a itself needs limb magnitudes < 2^29 and |a| < 2^258 (at 2^30 column 7 alone is 8 * 2^60 = 2^63).
+    static ZG_HD F9 sqr(const F9& a) {
         int64_t acc = 0;
         int32_t m[9], d[9];
         F9 r;
@@ -237,7 +281,7 @@ struct Field9 {
     }
 
     // value in (-2p, 3p), any limbs -> the canonical representative in [0, p), normalised
-    static __device__ F9 canon(const F9& x) {
+    static __host__ __device__ F9 canon(const F9& x) {
         F9 a = f9_norm(x);
         F9 pp;
 #pragma unroll
@@ -255,7 +299,7 @@ struct Field9 {
 
     // exact test x == 0 (mod p) for a NORMALISED value in [0, 8p): the low limb filters, the rare hit is
     // settled by subtraction
-    static __device__ bool is_zero_mod_p(const F9& a) {
+    static __host__ __device__ bool is_zero_mod_p(const F9& a) {
         bool cand = false;
         uint32_t lo = 0;  // low limb of j*p
 #pragma unroll
@@ -288,11 +332,11 @@ using Fr9 = Field9<Fr9Params>;
 template <class P>
 struct Dot9 {
     int64_t c[17];
-    __device__ __forceinline__ void zero() {
+    ZG_HD void zero() {
 #pragma unroll
         for (int k = 0; k < 17; k++) c[k] = 0;
     }
-    __device__ __forceinline__ void mac(const F9& a, const F9& b) {
+    ZG_HD void mac(const F9& a, const F9& b) {
 #pragma unroll
         for (int k = 0; k < 17; k++) {
 #pragma unroll
@@ -303,7 +347,7 @@ struct Dot9 {
         }
     }
     // columns 0..15 back into [0, 2^29); the top column takes what is left (value unchanged)
-    __device__ __forceinline__ void carry() {
+    ZG_HD void carry() {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             c[k + 1] += c[k] >> 29;
@@ -312,7 +356,7 @@ struct Dot9 {
     }
     // (sum) * 2^-261 mod p, normalised, value in [0, sum / 2^261 + p).  Call after carry(); the sum must stay below
     // 2^521 (2^13 terms of canonical operands of a 254-bit field), which keeps the result under f9_reduce_pack's 2^263.
-    __device__ __forceinline__ F9 reduce() const {
+    ZG_HD F9 reduce() const {
         int64_t acc = 0;
         int32_t m[9];
         F9 r;
@@ -343,7 +387,7 @@ struct Dot9 {
 // 8e-5 of v/p and the dropped low limbs add less than 4e-7, so floor(estimate - 1e-4) is floor(v/p) or
 // one less -- the remainder lies in [0, 2p) and one conditional subtraction finishes.
 template <class P>
-__device__ __forceinline__ Fe f9_reduce_pack(const F9& v) {
+ZG_HD Fe f9_reduce_pack(const F9& v) {
     const int32_t q = (int32_t)floorf((float)v.l[8] * 3.153175148504101e-07f - 1.0e-4f);
     F9 a, t;
     int64_t c = 0;
@@ -381,7 +425,7 @@ __device__ __forceinline__ Fe f9_reduce_pack(const F9& v) {
 // value below 2p is below 2^23.
 constexpr int32_t F9_SMALL_MAX = 1 << 12;
 template <class P>
-__device__ __forceinline__ F9 f9_mul_small(const F9& x, int32_t c) {
+ZG_HD F9 f9_mul_small(const F9& x, int32_t c) {
     const float top = (float)x.l[8] + (float)x.l[7] * 1.862645149230957e-09f;  // x / 2^232
     const int32_t q = (int32_t)floorf(top * (float)c * 3.153175148504101e-07f - 0.05f);
     F9 a;
@@ -402,15 +446,15 @@ struct alignas(16) XYZZ9 {
 };
 static_assert(sizeof(XYZZ9) == 144, "XYZZ9 layout");
 
-__device__ __forceinline__ XYZZ9 xyzz9_identity() {
+ZG_HD XYZZ9 xyzz9_identity() {
     XYZZ9 r;
 #pragma unroll
     for (int i = 0; i < 9; i++) r.x.l[i] = r.y.l[i] = r.zz.l[i] = r.zzz.l[i] = 0;
     return r;
 }
-__device__ __forceinline__ bool xyzz9_is_identity(const XYZZ9& a) { return f9_limbs_zero(a.zz); }
+ZG_HD bool xyzz9_is_identity(const XYZZ9& a) { return f9_limbs_zero(a.zz); }
 
-__device__ __forceinline__ XYZZ9 ld_xyzz9(const XYZZ9* p) {
+ZG_HD XYZZ9 ld_xyzz9(const XYZZ9* p) {
     XYZZ9 r;
     const uint4* q = reinterpret_cast<const uint4*>(p);
     uint4* d = reinterpret_cast<uint4*>(&r);
@@ -418,7 +462,7 @@ __device__ __forceinline__ XYZZ9 ld_xyzz9(const XYZZ9* p) {
     for (int i = 0; i < 9; i++) d[i] = q[i];
     return r;
 }
-__device__ __forceinline__ void st_xyzz9(XYZZ9* p, const XYZZ9& v) {
+ZG_HD void st_xyzz9(XYZZ9* p, const XYZZ9& v) {
     uint4* q = reinterpret_cast<uint4*>(p);
     const uint4* s = reinterpret_cast<const uint4*>(&v);
 #pragma unroll
@@ -427,7 +471,7 @@ __device__ __forceinline__ void st_xyzz9(XYZZ9* p, const XYZZ9& v) {
 
 // acc + q, q affine in the nine-limb 2^261 form (madd-2008-s, same case analysis as xyzz_madd).
 // `inf` is the accumulator's identity flag.  All coordinates in and out are normalised.
-__device__ __forceinline__ void xyzz9_madd(XYZZ9& a, bool& inf, const F9& qx, const F9& qy) {
+ZG_HD void xyzz9_madd(XYZZ9& a, bool& inf, const F9& qx, const F9& qy) {
     if (inf) {
         a.x = qx;
         a.y = f9_norm(qy);  // (a negated y arrives with negative limbs)
@@ -475,7 +519,7 @@ __device__ __forceinline__ void xyzz9_madd(XYZZ9& a, bool& inf, const F9& qx, co
 // with zz = zzz = 1 spends four of its ten products on multiplications by one; here 2 S + 2 M and the fused pair for Y3.
 // (x1, y1) and x2 are normalised, y2 may arrive with negative limbs (a negated y).  Same case analysis as xyzz9_madd:
 // `inf` is set where the two cancel (out is then not written).  Output normalised.
-__device__ __forceinline__ void xyzz9_from_pair(const F9& x1, const F9& y1, const F9& x2, const F9& y2, XYZZ9& out, bool& inf) {
+ZG_HD void xyzz9_from_pair(const F9& x1, const F9& y1, const F9& x2, const F9& y2, XYZZ9& out, bool& inf) {
     const F9 p = f9_sub(x2, x1);           // limb magnitudes < 2^29: both operands normalised
     const F9 r = f9_sub(f9_norm(y2), y1);  // (normalised first: the difference of a negated y and y1 could reach 2^30)
     const F9 pp = Fq9::sqr(p);
@@ -511,7 +555,7 @@ __device__ __forceinline__ void xyzz9_from_pair(const F9& x1, const F9& y1, cons
 }
 
 // dbl-2008-s-1 in the nine-limb form (only reached when an addition meets two equal points)
-__device__ __noinline__ XYZZ9 xyzz9_dbl(const XYZZ9& a) {
+__host__ __device__ __noinline__ inline XYZZ9 xyzz9_dbl(const XYZZ9& a) {
     if (xyzz9_is_identity(a)) return a;
     XYZZ9 o;
     const F9 u = f9_norm(f9_add(a.y, a.y));
@@ -528,7 +572,7 @@ __device__ __noinline__ XYZZ9 xyzz9_dbl(const XYZZ9& a) {
 }
 
 // add-2008-s in the nine-limb form, same case analysis as xyzz_add.  Inputs and output normalised.
-__device__ __forceinline__ XYZZ9 xyzz9_add(const XYZZ9& a, const XYZZ9& b) {
+ZG_HD XYZZ9 xyzz9_add(const XYZZ9& a, const XYZZ9& b) {
     if (xyzz9_is_identity(a)) return b;
     if (xyzz9_is_identity(b)) return a;
     const F9 u1 = Fq9::mul(a.x, b.zz);
@@ -559,7 +603,9 @@ __device__ __forceinline__ XYZZ9 xyzz9_add(const XYZZ9& a, const XYZZ9& b) {
 // share one addition: seven of the fourteen products each, intermediate values swapped with DPP
 // quad_perm [1,0,3,2] moves (45 moves per addition), results written per coordinate by the lane that
 // holds them (A: zz; B: x, y, zzz).  Same case analysis as xyzz9_add; the equal-x case falls back to
-// lane A doing the generic addition alone.
+// lane A doing the generic addition alone.  All four coordinates come out limb for limb as from xyzz9_add, whatever
+// the number of lanes: R (Q - X3) and S1 PPP are reduced apart here, where xyzz9_add reduces their difference once,
+// and Fq9::sub_fused settles the q between the two from the quotients (the same holds for xadd4 and xmadd_pair below).
 __device__ __forceinline__ int32_t dpp_swap1(int32_t v) {
     int32_t r = __builtin_amdgcn_update_dpp(0, v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
     // keep the move a move: folded into a following subtraction (GCN DPP combine) the operands came out
@@ -665,11 +711,12 @@ __device__ __forceinline__ XSum xadd(const XYZZ9* pa, const XYZZ9* pb, uint32_t 
     const F9 og = f9_swap(g);
     const F9 ppp = f9_sel(A, g, og), qq = f9_sel(A, og, g);
     const F9 x3 = f9_norm(f9_sub(f9_sub(f9_sub(rr, ppp), qq), qq));
-    const F9 h = Fq9::mul(f9_sel(A, e, r), f9_sel(A, pp, f9_sub(qq, x3)));  // A: ZZ3 = ZZ12 PP   B: R (Q - X3)
-    const F9 k = Fq9::mul(f9_sel(A, sv, e), ppp);                            // A: S1 PPP          B: ZZZ3 = ZZZ12 PPP
-    const F9 ok = f9_swap(k);
+    F9 mh, mk;  // the quotients of the two reductions
+    const F9 h = Fq9::mulq(f9_sel(A, e, r), f9_sel(A, pp, f9_sub(qq, x3)), mh);  // A: ZZ3 = ZZ12 PP   B: R (Q - X3)
+    const F9 k = Fq9::mulq(f9_sel(A, sv, e), ppp, mk);                            // A: S1 PPP          B: ZZZ3 = ZZZ12 PPP
+    const F9 ok = f9_swap(k), omk = f9_swap(mk);
     s.r.x = x3;
-    s.r.y = f9_norm(f9_sub(h, ok));  // (meaningful on B)
+    s.r.y = Fq9::sub_fused(h, mh, ok, omk);  // (meaningful on B)
     s.r.zz = h;                      // (meaningful on A)
     s.r.zzz = k;                     // (meaningful on B)
     s.wm = A ? 4u : 11u;
@@ -741,10 +788,11 @@ __device__ __forceinline__ XSum xadd4(const XYZZ9* pa, const XYZZ9* pb, uint32_t
     const F9 x3 = f9_norm(f9_sub(f9_sub(f9_sub(t2, ppp), qq), qq));   // lane 3: RR - PPP - 2Q
     const F9 tt = f9_sub(qq, x3);
     const F9 s1 = f9_quad<QUAD_B2>(t1);
-    const F9 t4 = Fq9::mul(role == 3 ? d : role == 2 ? t2 : s1, role == 3 ? tt : ppp);  // . | S1 PPP | ZZZ3 | R (Q - X3)
-    const F9 o4 = f9_quad<QUAD_B1>(t4);
+    F9 m4;  // the quotient of the reduction
+    const F9 t4 = Fq9::mulq(role == 3 ? d : role == 2 ? t2 : s1, role == 3 ? tt : ppp, m4);  // . | S1 PPP | ZZZ3 | R (Q - X3)
+    const F9 o4 = f9_quad<QUAD_B1>(t4), om4 = f9_quad<QUAD_B1>(m4);
     s.r.x = x3;
-    s.r.y = f9_norm(f9_sub(t4, o4));  // (meaningful on lane 3)
+    s.r.y = Fq9::sub_fused(t4, m4, o4, om4);  // (meaningful on lane 3)
     s.r.zz = t3;                       // (meaningful on lane 2)
     s.r.zzz = t4;
     s.wm = role == 3 ? 3u : role == 2 ? 12u : 0u;
@@ -798,16 +846,17 @@ __device__ __forceinline__ void xmadd_pair(PairAcc& a, bool& inf, const F9& qx, 
     const F9 og = f9_swap(g);                                     // A: PPP            B: Q
     const F9 x3 = f9_norm(f9_sub(f9_sub(f9_sub(of, og), g), g));  // A: RR - PPP - 2Q
     const F9 ot = f9_swap(f9_sub(g, x3));                         //                   B: T = Q - X3
-    const F9 h = Fq9::mul(f9_sel(A, a.z, a.m), f9_sel(A, f, g));  // A: ZZ3 = ZZ1 PP   B: Y1 PPP
-    const F9 k = Fq9::mul(f9_sel(A, a.w, d), f9_sel(A, og, ot));  // A: ZZZ3 = ZZZ1 PPP   B: R T
-    const F9 ok = f9_swap(k);                                     //                   B: ZZZ3
-    a.m = f9_sel(A, x3, f9_norm(f9_sub(k, h)));
+    F9 mh, mk;  // the quotients of the two reductions
+    const F9 h = Fq9::mulq(f9_sel(A, a.z, a.m), f9_sel(A, f, g), mh);  // A: ZZ3 = ZZ1 PP   B: Y1 PPP
+    const F9 k = Fq9::mulq(f9_sel(A, a.w, d), f9_sel(A, og, ot), mk);  // A: ZZZ3 = ZZZ1 PPP   B: R T
+    const F9 ok = f9_swap(k);                                          //                   B: ZZZ3
+    a.m = f9_sel(A, x3, Fq9::sub_fused(k, mk, h, mh));                 //                   B: R T - Y1 PPP as xyzz9_madd
     a.z = f9_sel(A, h, ok);
     a.w = k;
 }
 
 // nine-limb 2^261 form -> the library's packed XYZZ (coordinates x * 2^256, canonical)
-__device__ __forceinline__ XYZZ xyzz9_to_xyzz(const XYZZ9& a, bool inf) {
+ZG_HD XYZZ xyzz9_to_xyzz(const XYZZ9& a, bool inf) {
     if (inf || xyzz9_is_identity(a)) return xyzz_identity();
     XYZZ o;
     const F9 k = Fq9Params::k256();
