@@ -85,7 +85,7 @@ struct DeviceState {
     std::mutex mu;
     std::map<TwiddleKey, Fe*> twiddles;
     int refs = 0;
-    bool msm_attrs = false, ntt_attrs = false;  // hipFuncSetAttribute is per device; set under `mu`
+    bool msm_attrs = false, ntt_attrs = false, msm_var_attrs = false;  // hipFuncSetAttribute is per device; set under `mu`
 };
 DeviceState& device_state(int device);
 }  // namespace zg

@@ -53,6 +53,9 @@ def load() -> ctypes.CDLL:
     lib.zg_ctx_destroy.restype = None
     lib.zg_bases_free.argtypes = [c_void_p]
     lib.zg_bases_free.restype = None
+    lib.zg_msm_var.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]
+    lib.zg_msm_var_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint32, c_void_p]
+    lib.zg_msm_var_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]
     _lib = lib
     return lib
 
@@ -62,6 +65,7 @@ ABI_SYMBOLS = [
     "zg_last_error", "zg_version", "zg_ctx_create", "zg_ctx_destroy", "zg_ctx_sync", "zg_ctx_stream",
     "zg_bases_register", "zg_bases_register_dev", "zg_bases_free", "zg_bases_len",
     "zg_bases_window_bits", "zg_msm", "zg_msm_batch", "zg_msm_batch_dev", "zg_msm_finish", "zg_g1_sum",
+    "zg_msm_var", "zg_msm_var_batch", "zg_msm_var_dev",
     "zg_ntt", "zg_intt", "zg_ntt_batch", "zg_intt_batch", "zg_ntt_batch_dev", "zg_coeff_to_extended",
     "zg_coeff_to_extended_batch_dev", "zg_extended_to_coeff", "zg_extended_to_coeff_dev",
     "zg_domain_omega", "zg_ctx_profile_enable", "zg_ctx_profile_collect", "zg_params_new",
@@ -428,6 +432,32 @@ class Ctx:
         out = np.zeros((batch, 12), np.uint64)
         _check(self.lib.zg_msm_finish(self.h, c_void_p(d_xyzz), c_size_t(batch), _ptr(out)))
         return out
+
+    # ---- MSM over points that are not registered (zg_msm_var*) ----
+    def msm_var(self, bases: np.ndarray, scalars: np.ndarray, window_bits: int = 0) -> np.ndarray:
+        """best_multiexp(scalars, bases): bases uint64[n, 8] (any points, used once), scalars uint64[n, 4] -> normalised point."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+        scalars = _fr(scalars).reshape(-1, 4)
+        assert bases.shape[0] == scalars.shape[0], f"{scalars.shape[0]} scalars for {bases.shape[0]} points"
+        out = np.zeros(12, np.uint64)
+        _check(self.lib.zg_msm_var(self.h, _ptr(bases), _ptr(scalars), c_size_t(scalars.shape[0]), c_uint32(window_bits), _ptr(out)))
+        return out
+
+    def msm_var_batch(self, bases: np.ndarray, scalars: np.ndarray, window_bits: int = 0) -> np.ndarray:
+        """scalars uint64[batch, n, 4] against the same n points, one launch sequence -> uint64[batch, 12]."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+        scalars = _fr(scalars)
+        assert scalars.ndim == 3 and scalars.shape[1] == bases.shape[0]
+        batch, n = scalars.shape[0], scalars.shape[1]
+        ptrs = (c_void_p * batch)(*[scalars[b].ctypes.data for b in range(batch)])
+        out = np.zeros((batch, 12), np.uint64)
+        _check(self.lib.zg_msm_var_batch(self.h, _ptr(bases), ptrs, c_size_t(batch), c_size_t(n), c_uint32(window_bits), _ptr(out)))
+        return out
+
+    def msm_var_dev(self, d_bases: int, d_scalars: int, stride: int, batch: int, n: int, d_out: int, window_bits: int = 0):
+        """Device addresses, asynchronous on the context stream; d_out: batch x 128 B, finished by msm_finish."""
+        _check(self.lib.zg_msm_var_dev(self.h, c_void_p(d_bases), c_void_p(d_scalars), c_size_t(stride), c_size_t(batch),
+                                       c_size_t(n), c_uint32(window_bits), c_void_p(d_out)))
 
     # ---- NTT ----
     def ntt(self, a: np.ndarray, omega: np.ndarray, divisor: np.ndarray | None = None) -> np.ndarray:

@@ -215,6 +215,40 @@ int zg_msm_finish(zg_ctx *ctx, const void *d_xyzz, size_t batch, zg_g1 *out);
  * partials (the EC add that follows the RCCL all-gather; EC add is not an ncclRedOp). */
 int zg_g1_sum(const zg_g1 *parts, size_t count, zg_g1 *out);
 
+/* Multiexp over points that are NOT registered: the bases are an argument, as in upstream's best_multiexp(coeffs, bases)
+ * (MSMKZG::eval in the verifier, a downsized or imported ParamsKZG, a gadget's own points).  No table is built and nothing
+ * stays resident: every window has a bucket set of its own and the windows meet in a ladder of 254 dependent doublings per
+ * vector (1.3 - 1.65 ms measured, whatever n is: DESIGN.md 13) -- the trade for points used once; points used many times belong
+ * in a zg_bases.
+ *   result        the host forms return NORMALISED zg_g1 as zg_msm does, the identity as (0, 1, 0); for the same points and
+ *                 scalars the bytes are those of zg_msm on a registered set.
+ *   window_bits   the Pippenger window width c: 0 = chosen by the library, 2..16 taken as given, anything else
+ *                 ZG_ERR_INVALID_ARG.  No width changes a byte.  At 0 the width is the c in 2..16 with the least
+ *                 ceil(255 / c) * (n + 4 * 2^(c-1)) -- a window adds n points into buckets and reduces 2^(c-1) buckets at
+ *                 about four accumulated points each -- which is 2 or 3 below n = 32, 10 at n = 2^14 and 13 at 2^17; it is
+ *                 lowered while batch * ceil(255 / c) * 2^(c-1) exceeds 2^24 bucket sums.
+ *   sizes         n = 0 or batch = 0 is ZG_OK, launches nothing, and every out is the identity.  A null pointer where a
+ *                 size is non-zero is ZG_ERR_INVALID_ARG.  n >= 2^23 is ZG_ERR_UNSUPPORTED (an entry names its point in 23
+ *                 bits, as in a base set), and so is batch > ZG_MSM_VAR_MAX_BATCH: at c = 2 a batch of 256 is 256 * 128
+ *                 bucket sets, half of what one launch grid's second dimension holds, and at c = 16 its bucket sums
+ *                 (256 * 16 * 2^15 * 144 B) are 19 GB.  These are checked before anything is read or allocated.
+ *   points        any points of the curve in any arrangement: (0,0) is the identity and contributes nothing, the same
+ *                 point may occur any number of times, a point and its negative may both occur.  Points are NOT validated;
+ *                 points off the curve give garbage, as upstream (zg_params_check is the validation).
+ *   lifetime      nothing survives the call: every buffer comes from the context's workspace pool and goes back to it; no
+ *                 zg_bases is created.  The context lock is held for the call. */
+#define ZG_MSM_VAR_MAX_BATCH 256
+/* best_multiexp(scalars, bases) with the bases as an ARGUMENT: out = sum_i scalars[i] * bases[i], i < n. */
+int zg_msm_var(zg_ctx *ctx, const zg_g1_affine *bases, const zg_fr *scalars, size_t n,
+               uint32_t window_bits, zg_g1 *out);
+/* `batch` scalar vectors against the same n points, one launch sequence; out[batch]. */
+int zg_msm_var_batch(zg_ctx *ctx, const zg_g1_affine *bases, const zg_fr *const *scalars, size_t batch,
+                     size_t n, uint32_t window_bits, zg_g1 *out);
+/* Device pointers, asynchronous on the context stream: d_bases n * 64 B; vector b at d_scalars + b*stride_elems*32 B
+ * (stride_elems >= n); d_out_xyzz[batch] in the 128-byte form zg_msm_batch_dev leaves, finished by zg_msm_finish. */
+int zg_msm_var_dev(zg_ctx *ctx, const void *d_bases, const void *d_scalars, size_t stride_elems,
+                   size_t batch, size_t n, uint32_t window_bits, void *d_out_xyzz);
+
 /* ------------------------------------------------------------------ SRS
  * Replaces ParamsKZG::<Bn256>::new(k) (reference call sites benches/bench.rs:19, src/main.rs:232):
  * g[i] = s^i * G and g_lagrange[i] = L_i(s) * G, 2^k affine points each.  Upstream draws s from

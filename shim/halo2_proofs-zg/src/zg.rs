@@ -15,6 +15,9 @@
 //!     `transcript.finalize()` in `Wnn::proof` returns them.
 //!
 //! Everything that does not fit returns `None` and the stock prover runs.
+//!
+//! (Arithmetic-level forks that route `arithmetic::best_multiexp(coeffs, bases)` itself: a `bases` slice that is not a
+//! registered SRS goes to `zg_msm_var`, which takes the points with the call.  Unverified like the rest of this file.)
 use std::any::TypeId;
 use std::collections::{BTreeMap, HashMap};
 use std::ffi::CStr;
