@@ -47,6 +47,19 @@ def n_point_sets(cs) -> int:
     return len(set(r % (1 << cs.k) for r in rots))
 
 
+def point_set_lengths(cs, N: int) -> dict:
+    """{rotation mod n: how many (circuit, polynomial) pairs a proof of N circuits opens at x * omega^rotation}: the lists
+    that step 8 of verify walks -- every circuit's own queries, then the fixed columns, the sigmas, h and the random
+    polynomial at rotation 0."""
+    n, out = 1 << cs.k, {}
+    for r, *_ in circuit_queries(cs):
+        out[r % n] = out.get(r % n, 0) + N
+    for _, r in cs.fixed_queries:
+        out[r % n] = out.get(r % n, 0) + 1
+    out[0] = out.get(0, 0) + len(cs.perm_columns) + 2
+    return out
+
+
 def proof_len(cs, N: int) -> int:
     """64 (N (A + 3 NL + S) + 1 + (d - 1) + nsets) + 32 (N (AQ + (S ? 3 S - 1 : 0) + 5 NL) + FQ + 1 + P)"""
     A, NL, S, P, d = cs.n_advice, len(cs.lookups), n_sets(cs), len(cs.perm_columns), cs.degree()

@@ -109,6 +109,50 @@ def test_n_circuits_verify(ctx, zg, orc, N):
     s.close()
 
 
+CHUNK = 128  # combine_pairs_kernel takes a point set's list in chunks of HC9_MAX = 128 terms, the short chunk first
+
+
+def short_first_chunk_N(cs) -> tuple:
+    """(N, length): the N in 1..64 whose longest point-set list is nearest above a multiple of 128 (the smallest such N)"""
+    longest = {N: max(multi_ref.point_set_lengths(cs, N).values()) for N in range(1, 65)}
+    N = min((L % CHUNK, N) for N, L in longest.items() if L > CHUNK and L % CHUNK)[1]
+    return N, longest[N]
+
+
+@pytest.mark.parametrize("N", [4, 7, 15, 64])
+def test_lazy_sum_kernels_at_their_edges(ctx, zg, orc, N):
+    """fold_slots_kernel sums the circuits' quotients three terms at a time: N = 4 leaves its loop a tail of one, N = 7 two
+    rounds and a tail of one, N = 64 is FOLD_MAX_SLOTS (21 rounds and a tail of one, every weight slot in use).
+    combine_pairs_kernel: the toy circuit's longest list (rotation 0) holds 8 N + 10 pairs; N = 15 gives 130 = 2 + 128, the
+    N in 1..64 nearest above a multiple of 128 -- a first chunk of two terms, then a whole chunk chained by v^128; N = 64
+    gives 522 = 10 + 4 * 128."""
+    s = Setup(orc, zg, ctx, toy_family(N))
+    assert short_first_chunk_N(s.cs) == (15, 130)
+    assert max(multi_ref.point_set_lengths(s.cs, N).values()) == 8 * N + 10
+    proof = s.both_forms(list(range(N)), [71 + c for c in range(N)])
+    assert len(proof) == multi_ref.proof_len(s.cs, N)
+    assert s.verdicts(proof, s.inst) == (1, 1)
+    if N > 4:  # the last circuit's quotient is in the sum: its instance exchanged with another's is rejected by both
+        assert s.inst[N - 1].tobytes() != s.inst[0].tobytes()
+        assert s.verdicts(proof, [s.inst[N - 1]] + s.inst[1:N - 1] + [s.inst[0]]) == (0, 0)
+    s.close()
+
+
+def test_sixty_five_circuits_are_refused(ctx, zg, orc):
+    """FOLD_MAX_SLOTS + 1: zg_prover_set_batch allows 65 slots (they serve batches of proofs), one proof of 65 circuits is
+    ZG_ERR_UNSUPPORTED -- the status poly_fold_slots has for it, raised by zg_prover_prove_multi before anything is launched --
+    and the prover goes on to prove 64."""
+    s = Setup(orc, zg, ctx, toy_family(65))
+    assert s.prover.batch == 65
+    s.prover.set_overlap(True)
+    with pytest.raises(zg.ZgError) as e:
+        s.prover.prove_multi(s.adv, s.inst, list(range(65)))
+    assert e.value.status == -4 and "65 circuits" in str(e.value)  # ZG_ERR_UNSUPPORTED
+    proof = s.prover.prove_multi(s.adv[:64], s.inst[:64], list(range(64)))
+    assert s.verifier.verify_multi([proof], [s.inst[:64]], 5, 64) == [1]
+    s.close()
+
+
 def test_structure_of_a_three_circuit_proof(ctx, zg, orc):
     """Circuit-major order and per-circuit keys, without any verifier: circuit c's advice commitments are those of its own
     single proof under key c; the random polynomial's commitment is the single proof's under key 0."""

@@ -307,20 +307,27 @@ def test_unsatisfied_witness_still_proves_but_does_not_verify(ctx, zg, orc):
 @pytest.mark.parametrize("latency_form", [True, False])
 @pytest.mark.parametrize("n", [1, 2, 5, 1000, 1024, 1025, 1 << 14, (1 << 17) + 3])
 def test_grand_product(ctx, zg, orc, n, latency_form):
-    """Both forms of the scan: block-local Hillis-Steele (latency) and one strip per lane (throughput)."""
+    """Both forms of the scan: block-local Hillis-Steele (latency) and one strip per lane (throughput).  A zero denominator
+    zeroes every row after it, so the first pass compares products on four rows only; the second pass, without zeros,
+    compares one on every row (tests/test_gpu_poly_scans.py has the edge sizes and the zero places)."""
     num, den = orc.fill_fr(1, n), orc.fill_fr(2, n)
-    if n > 4:
-        den[3] = 0  # BatchInvert leaves zeros alone -> that ratio is zero
-    if n > 2000:
-        den[1500] = 0
     z0 = orc.fill_fr(3, 1)[0]
-    dn, dd = dev(num), dev(den)
-    dz = torch.empty_like(dn)
+    free = orc.grand_product(num, den, z0)
+    assert free.any(axis=1).all()  # no zero row: every row of the second pass is a product
+    with_zeros = den.copy()
+    if n > 4:
+        with_zeros[3] = 0  # BatchInvert leaves zeros alone -> that ratio is zero
+    if n > 2000:
+        with_zeros[1500] = 0
+    dn = dev(num)
     ctx.set_msm_latency(latency_form)
     try:
-        ctx.grand_product_dev(dn.data_ptr(), dd.data_ptr(), z0, n, dz.data_ptr())
-        assert np.array_equal(host(dz), orc.grand_product(num, den, z0))
-        assert np.array_equal(ctx.grand_product(num, den, z0), orc.grand_product(num, den, z0))  # host-pointer entry
+        for d, want in ((with_zeros, orc.grand_product(num, with_zeros, z0)), (den, free)):
+            dd = dev(d)
+            dz = torch.empty_like(dn)
+            ctx.grand_product_dev(dn.data_ptr(), dd.data_ptr(), z0, n, dz.data_ptr())
+            assert np.array_equal(host(dz), want)
+            assert np.array_equal(ctx.grand_product(num, d, z0), want)  # host-pointer entry
     finally:
         ctx.set_msm_latency(True)
 
@@ -332,15 +339,15 @@ def test_eval_polys_and_kate_division(ctx, zg, orc, n, latency_form):
     pts = orc.fill_fr(99, 4)
     d = dev(polys)
     idx = [0, 2, 1, 2]
-    got = ctx.eval_polys_dev(d.data_ptr(), n, n, idx, pts)
-    for j, pi in enumerate(idx):
-        assert np.array_equal(got[j], orc.eval_poly(polys[pi], pts[j]))
     dq = torch.empty((n, 4), dtype=torch.int64, device="cuda")
     ctx.set_msm_latency(latency_form)
     try:
+        got = ctx.eval_polys_dev(d.data_ptr(), n, n, idx, pts)
         ctx.kate_division_dev(d.data_ptr(), n, pts[0], dq.data_ptr())
     finally:
         ctx.set_msm_latency(True)
+    for j, pi in enumerate(idx):
+        assert np.array_equal(got[j], orc.eval_poly(polys[pi], pts[j]))
     assert np.array_equal(host(dq), orc.kate_division(polys[0], pts[0]))
 
 

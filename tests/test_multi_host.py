@@ -93,3 +93,14 @@ def test_verdict_classes_on_tampered_proofs(orc):
     # a proof checked against another circuit's key
     alt = HostSetup(orc, *toy_circuit(5, force_degree=6))
     assert multi_ref.verify(alt.vk, [s.inst], good) == cls(orc.verify_proof_pairing(alt.pk, s.inst, good)) != 1
+
+
+@pytest.mark.parametrize("N", [1, 3, 15, 64])
+def test_point_set_lengths_count_the_evaluations(N):
+    """Every evaluation of the proof is opened once, and h(x), which the proof does not carry, beside them."""
+    for cs in (toy_circuit(5)[0], toy_circuit(6, force_degree=6)[0], variant_circuit("wide_lookup", k=5, seed=3)[0]):
+        lengths = multi_ref.point_set_lengths(cs, N)
+        A, NL, S, d = cs.n_advice, len(cs.lookups), multi_ref.n_sets(cs), cs.degree()
+        points = 64 * (N * (A + 3 * NL + S) + 1 + (d - 1) + multi_ref.n_point_sets(cs))
+        assert len(lengths) == multi_ref.n_point_sets(cs)
+        assert 32 * (sum(lengths.values()) - 1) == multi_ref.proof_len(cs, N) - points
