@@ -2134,12 +2134,15 @@ extern "C" {
 
 int zg_bases_register_dev(zg_ctx* ctx, const void* d_bases, size_t n, uint32_t window_bits, zg_bases** out) {
     ZG_REQUIRE(ctx && d_bases && out, ZG_ERR_INVALID_ARG, "zg_bases_register_dev: null argument");
+    // (one row per bit position, window_bits = 1, is bases_enable_naf's own table: not a window size a caller may ask for)
+    ZG_REQUIRE(window_bits != 1, ZG_ERR_INVALID_ARG, "zg_bases_register_dev: window_bits 1 not in [2,16]");
     ZG_ENTER(ctx);
     return bases_register_dev(ctx, (const Affine*)d_bases, n, window_bits, out);
 }
 
 int zg_bases_register(zg_ctx* ctx, const zg_g1_affine* bases, size_t n, uint32_t window_bits, zg_bases** out) {
     ZG_REQUIRE(ctx && bases && out, ZG_ERR_INVALID_ARG, "zg_bases_register: null argument");
+    ZG_REQUIRE(window_bits != 1, ZG_ERR_INVALID_ARG, "zg_bases_register: window_bits 1 not in [2,16]");
     ZG_ENTER(ctx);
     WsScope ws(ctx);
     Affine* d = ws.get<Affine>(n ? n : 1);

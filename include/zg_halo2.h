@@ -167,7 +167,7 @@ int zg_ctx_profile_collect(zg_ctx *ctx, zg_kernel_stat *out, size_t cap, size_t 
 
 /* Uploads a fixed base set once (ParamsKZG::g or ::g_lagrange) and precomputes the
  * window-shifted copies 2^(c*w) * P_i that let all Pippenger windows share one bucket set.
- * window_bits = 0 picks c from n.  Host pointer. */
+ * window_bits = 0 picks c from n; otherwise 2..16 (anything else: ZG_ERR_INVALID_ARG).  Host pointer. */
 int zg_bases_register(zg_ctx *ctx, const zg_g1_affine *bases, size_t n, uint32_t window_bits,
                       zg_bases **out);
 /* Same, from a device pointer (n * 64 B, HBM resident). */
