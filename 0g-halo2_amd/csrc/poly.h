@@ -167,8 +167,12 @@ int poly_from_raw_rows(zg_ctx* ctx, const Fe* src, size_t src_stride, Fe* dst, s
 int poly_lookup_terms(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const Fe* cin, const Fe* ctab, const Fe* pin,
                       const Fe* ptab, size_t perm_stride, size_t perm_bs, Fe* num, Fe* den, uint32_t per, uint32_t first,
                       uint32_t n, uint32_t n_lookups);
+// (only_set >= 0: that column set alone, written as product 0 of each proof)
 int poly_perm_terms(zg_ctx* ctx, const DevCircuit& c, const Cols& cols, const ProofConst* pc, uint32_t nb,
-                    const Fe* sigma_val, const Fe* omega_tw, Fe* num, Fe* den, uint32_t per, uint32_t n);
+                    const Fe* sigma_val, const Fe* omega_tw, Fe* num, Fe* den, uint32_t per, uint32_t n, int only_set = -1);
+// A one-entry ProofConst in workspace memory for the stand-alone entries that borrow a prover kernel: *hc is copied to a
+// block of `ws` and the stream is drained (hc is the caller's stack memory), *out = the device copy
+int poly_one_const(zg_ctx* ctx, WsScope& ws, const ProofConst& hc, ProofConst** out);
 // z[q][0] = z0[q] (device array, or all ones if null), z[q][i+1] = z[q][i]*num[q][i]/den[q][i] for the `batch`
 // products q = g * per + j (per = 0: one group); within a group the first `chain` products are chained: product j
 // starts from product j-1's value at row `last`.  num / den / tmp are flat ([q][n]); z of product q goes to
@@ -219,6 +223,9 @@ int poly_fold_slots(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, Fe* h, size_
 // length), minus pc[0].subs[s] at X^0; out + s * out_stride
 int poly_combine_pairs(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, const uint32_t* d_lists, const uint32_t* firsts,
                        const uint32_t* counts, uint32_t nsets, Fe* out, size_t out_stride, uint32_t n);
+// out[i] = sum_j coeffs[j] * polys[j][i], i < n, minus *sub0 (may be null) at i = 0; polys and coeffs are HOST arrays of
+// `count` entries (device pointers / library-form scalars) that travel in the kernel arguments, 64 terms per launch
+int poly_lincomb(zg_ctx* ctx, const Fe* const* polys, const Fe* coeffs, size_t count, uint32_t n, const Fe* sub0, Fe* out);
 // kate_division of `nsets` polynomials per proof: a + b * a_bs + s * a_stride divided by (X - pc[b].points[slot[s]])
 size_t poly_kate_tmp_elems(uint32_t n, uint32_t batch);
 int poly_kate_division(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const uint32_t* slots, uint32_t nsets, const Fe* a,

@@ -275,11 +275,12 @@ int poly_lookup_terms(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const Fe* 
 
 // permutation commit, one set per blockIdx.y:
 //   den = prod_c (v_c + beta*sigma_c + gamma),  num = prod_c (v_c + delta^c * omega^i * beta + gamma)
+// (set0: the column set blockIdx.y = 0 stands for -- the stand-alone entry asks for ONE set, written as product 0)
 __global__ __launch_bounds__(256) void perm_terms_kernel(DevCircuit c, Cols cols_all, const ProofConst* __restrict__ pc,
                                                          const Fe* sigma_val, const Fe* omega_tw, Fe* num, Fe* den,
-                                                         uint32_t per, uint32_t n) {
+                                                         uint32_t per, uint32_t n, uint32_t set0) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t s = blockIdx.y;
+    uint32_t s = blockIdx.y + set0;
     const uint32_t b = blockIdx.z;
     if (i >= n) return;
     const Cols cols = cols_of(cols_all, b);
@@ -297,15 +298,16 @@ __global__ __launch_bounds__(256) void perm_terms_kernel(DevCircuit c, Cols cols
         m = Fr::mul(m, Fr::add(Fr::add(dw, gamma), v));
         dw = Fr::mul(dw, fr_delta());
     }
-    stg(den + (size_t)(b * per + s) * n + i, d);
-    stg(num + (size_t)(b * per + s) * n + i, m);
+    stg(den + (size_t)(b * per + blockIdx.y) * n + i, d);
+    stg(num + (size_t)(b * per + blockIdx.y) * n + i, m);
 }
 
 int poly_perm_terms(zg_ctx* ctx, const DevCircuit& c, const Cols& cols, const ProofConst* pc, uint32_t nb,
-                    const Fe* sigma_val, const Fe* omega_tw, Fe* num, Fe* den, uint32_t per, uint32_t n) {
+                    const Fe* sigma_val, const Fe* omega_tw, Fe* num, Fe* den, uint32_t per, uint32_t n, int only_set) {
     if (!c.n_sets || !nb) return ZG_OK;
+    const uint32_t sets = only_set < 0 ? c.n_sets : 1u, set0 = only_set < 0 ? 0u : (uint32_t)only_set;
     ZG_LAUNCH(ctx, "perm_terms", nb * ((double)c.n_perm * n * 64 + (double)c.n_sets * n * 64), perm_terms_kernel,
-              dim3((n + 255) / 256, c.n_sets, nb), dim3(256), 0, c, cols, pc, sigma_val, omega_tw, num, den, per, n);
+              dim3((n + 255) / 256, sets, nb), dim3(256), 0, c, cols, pc, sigma_val, omega_tw, num, den, per, n, set0);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
@@ -1447,6 +1449,77 @@ int poly_combine_pairs(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, 
     return ZG_OK;
 }
 
+// zg_fr_lincomb_dev: out[i] = sum_j coeff_j * poly_j[i] for polynomials that live anywhere in HBM (the caller-run
+// create_proof's sum x^(n i) h_i and sum v^i p_i - eval).  The lazy sum of combine_pairs_kernel -- 81 multiply-adds per
+// term, one Montgomery reduction per chunk -- with the chunk's addresses and coefficients in the KERNEL ARGUMENTS: every
+// lane reads term t of the same chunk, so both come through the scalar unit, nothing is uploaded and the entry queues
+// without waiting.  The coefficients arrive times 2^5 and unpacked (the host does it once per launch, not every lane).
+// Bound: Dot9::reduce takes a sum below 2^521; a term of canonical operands is below r^2 < 2^507.2, so 2^13 terms fit --
+// the chunk, LC_CHUNK = 64 terms (what 4 KB of kernel arguments hold at 44 B a term), is far inside it.  Later chunks add
+// what the earlier ones left in `out` (canonical after every launch).
+constexpr uint32_t LC_CHUNK = ZG_LINCOMB_CHUNK;
+struct LincombArgs {
+    const Fe* poly[LC_CHUNK];
+    F9 w9[LC_CHUNK];  // coefficient * 2^261 mod r, unpacked
+    Fe sub0;
+    uint32_t count, first, has_sub;
+};
+static_assert(sizeof(LincombArgs) + 64 <= 4096, "LincombArgs must fit the kernel-argument segment");
+static_assert(LC_CHUNK <= (1u << 13), "one reduction per chunk: Dot9::reduce's bound");
+__global__ __launch_bounds__(256) void lincomb_kernel(LincombArgs a, Fe* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Dot9<Fr9Params> acc;
+    acc.zero();
+    uint32_t t = 0;
+    for (; t + 3 <= a.count; t += 3) {
+        const Fe p0 = ldg(a.poly[t] + i), p1 = ldg(a.poly[t + 1] + i), p2 = ldg(a.poly[t + 2] + i);
+        acc.mac(f9_unpack(p0), a.w9[t]);
+        acc.mac(f9_unpack(p1), a.w9[t + 1]);
+        acc.mac(f9_unpack(p2), a.w9[t + 2]);
+        acc.carry();
+    }
+    for (; t < a.count; t++) {
+        acc.mac(f9_unpack(ldg(a.poly[t] + i)), a.w9[t]);
+        acc.carry();
+    }
+    Fe r = f9_reduce_pack<Fr9Params>(acc.reduce());
+    if (!a.first) r = Fr::add(ldg(out + i), r);
+    if (a.has_sub && i == 0) r = Fr::sub(r, a.sub0);
+    stg(out + i, r);
+}
+
+int poly_lincomb(zg_ctx* ctx, const Fe* const* polys, const Fe* coeffs, size_t count, uint32_t n, const Fe* sub0, Fe* out) {
+    if (!n) return ZG_OK;
+    size_t j0 = 0;
+    do {
+        LincombArgs a;
+        memset(&a, 0, sizeof(a));
+        a.count = (uint32_t)std::min<size_t>(LC_CHUNK, count - j0);
+        a.first = j0 == 0;
+        a.has_sub = j0 == 0 && sub0 != nullptr;
+        if (a.has_sub) a.sub0 = *sub0;
+        for (uint32_t t = 0; t < a.count; t++) {
+            a.poly[t] = polys[j0 + t];
+            a.w9[t] = f9_unpack(Fr::mul(coeffs[j0 + t], Fr9Params::c261_fe()));
+        }
+        ZG_LAUNCH(ctx, "lincomb", ((double)a.count + (a.first ? 1 : 2)) * n * 32, lincomb_kernel, dim3((n + 255) / 256), dim3(256), 0, a,
+                  out, n);
+        j0 += a.count;
+    } while (j0 < count);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int poly_one_const(zg_ctx* ctx, WsScope& ws, const ProofConst& hc, ProofConst** out) {
+    ProofConst* d = ws.get<ProofConst>(1);
+    if (!d) return ZG_ERR_OOM;
+    ZG_HIP(hipMemcpyAsync(d, &hc, sizeof(hc), hipMemcpyHostToDevice, ctx->stream));
+    ZG_HIP(hipStreamSynchronize(ctx->stream));  // (hc is the caller's stack memory)
+    *out = d;
+    return ZG_OK;
+}
+
 // kate_division: q_i = a_{i+1} + z q_{i+1} (i = n-2 .. 0, q_{n-1} = 0) -- upstream's one-core recurrence.  Strip form,
 // one workgroup per polynomial: lane l owns the strip [l S, (l + 1) S) of coefficients, S = n / lanes.
 //   pass A   the strip's own contribution at its first element, H_l = sum_{i in strip} a_{i+1} z^(i - l S) (Horner,
@@ -1787,6 +1860,109 @@ int zg_kate_division_dev(zg_ctx* ctx, const void* d_a, size_t n, const zg_fr* z,
     ZG_TRY(poly_kate_division(ctx, dpc, 1, &slot0, 1, (const Fe*)d_a, n, 0, (Fe*)d_q, n, 0, tmp, (uint32_t)n));
     ZG_HIP(hipStreamSynchronize(ctx->stream));
     return ZG_OK;
+}
+
+// ---- the arithmetic level on device pointers: thin host code over the prover's own launch helpers
+
+// lookup::prover::permute_expression_pair: the prover's path (prove_batch.hip, permuted_queue) for ONE pair -- canonical
+// keys with the sentinel padding, the bitonic sort of both columns, the scan-built s' (sort.hip) -- then back to
+// Montgomery form on the usable rows and zeros behind them.
+int zg_permute_expression_pair_dev(zg_ctx* ctx, const void* d_input, const void* d_table, uint32_t k, uint32_t usable,
+                                   void* d_permuted_input, void* d_permuted_table) {
+    ZG_REQUIRE(ctx && d_input && d_table && d_permuted_input && d_permuted_table, ZG_ERR_INVALID_ARG,
+               "zg_permute_expression_pair_dev: null argument");
+    ZG_REQUIRE(k >= 4 && k <= 20, ZG_ERR_UNSUPPORTED, "zg_permute_expression_pair_dev: k=%u outside 4..20", k);
+    const uint32_t n = 1u << k;
+    ZG_REQUIRE(usable >= 1 && usable <= n, ZG_ERR_INVALID_ARG, "zg_permute_expression_pair_dev: %u usable rows of %u", usable, n);
+    ZG_REQUIRE(d_permuted_input != d_input && d_permuted_input != d_table && d_permuted_table != d_input &&
+                   d_permuted_table != d_table && d_permuted_input != d_permuted_table,
+               ZG_ERR_INVALID_ARG, "zg_permute_expression_pair_dev: an output aliases another column");
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    Fe* raw = ws.get<Fe>((size_t)4 * n);  // input keys -> a', table keys, s', the left-over list
+    uint32_t* u32 = ws.get<uint32_t>((size_t)2 * n + 3);
+    if (ws.failed) return ZG_ERR_OOM;
+    Fe *raw_in = raw, *raw_tab = raw + n, *sraw = raw + (size_t)2 * n, *left = raw + (size_t)3 * n;
+    uint32_t* d_err = u32 + (size_t)2 * n + 2;  // behind permute_pairs' scratch: zeroed by the same fill
+    ZG_TRY(poly_to_raw(ctx, (const Fe*)d_input, raw_in, n));
+    ZG_TRY(poly_to_raw(ctx, (const Fe*)d_table, raw_tab, n));
+    ZG_TRY(poly_sort_pad(ctx, raw, n, usable, 2));
+    ZG_TRY(poly_sort_keys(ctx, raw, n, 2));
+    ZG_TRY(poly_permute_pairs(ctx, raw_in, raw_tab, sraw, n, usable, 1, u32, left, d_err));
+    uint32_t h_err = 0;
+    ZG_HIP(hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, ctx->stream));
+    ZG_HIP(hipStreamSynchronize(ctx->stream));
+    ZG_REQUIRE(h_err == 0, ZG_ERR_CONSTRAINT,
+               "zg_permute_expression_pair_dev: an input value is missing from the table (ConstraintSystemFailure)");
+    ZG_TRY(poly_from_raw(ctx, raw_in, (Fe*)d_permuted_input, usable));
+    ZG_TRY(poly_from_raw(ctx, sraw, (Fe*)d_permuted_table, usable));
+    if (usable < n) {
+        ZG_HIP(hipMemsetAsync((Fe*)d_permuted_input + usable, 0, (size_t)(n - usable) * 32, ctx->stream));
+        ZG_HIP(hipMemsetAsync((Fe*)d_permuted_table + usable, 0, (size_t)(n - usable) * 32, ctx->stream));
+    }
+    return ZG_OK;
+}
+
+int zg_permute_expression_pair(zg_ctx* ctx, const zg_fr* input, const zg_fr* table, uint32_t k, uint32_t usable,
+                               zg_fr* permuted_input, zg_fr* permuted_table) {
+    ZG_REQUIRE(ctx && input && table && permuted_input && permuted_table, ZG_ERR_INVALID_ARG,
+               "zg_permute_expression_pair: null argument");
+    ZG_REQUIRE(k >= 4 && k <= 20, ZG_ERR_UNSUPPORTED, "zg_permute_expression_pair: k=%u outside 4..20", k);
+    const size_t n = (size_t)1 << k;
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    Fe* d = ws.get<Fe>(4 * n);
+    if (ws.failed) return ZG_ERR_OOM;
+    ZG_HIP(hipMemcpyAsync(d, input, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZG_HIP(hipMemcpyAsync(d + n, table, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZG_TRY(zg_permute_expression_pair_dev(ctx, d, d + n, k, usable, d + 2 * n, d + 3 * n));
+    ZG_HIP(hipMemcpyAsync(permuted_input, d + 2 * n, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZG_HIP(hipMemcpyAsync(permuted_table, d + 3 * n, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZG_HIP(hipStreamSynchronize(ctx->stream));
+    return ZG_OK;
+}
+
+int zg_lookup_product_terms_dev(zg_ctx* ctx, const void* d_input, const void* d_table, const void* d_permuted_input,
+                                const void* d_permuted_table, const zg_fr* beta, const zg_fr* gamma, size_t n, void* d_num,
+                                void* d_den) {
+    ZG_REQUIRE(ctx && d_input && d_table && d_permuted_input && d_permuted_table && beta && gamma && d_num && d_den,
+               ZG_ERR_INVALID_ARG, "zg_lookup_product_terms_dev: null argument");
+    ZG_REQUIRE(n < (1u << 28), ZG_ERR_UNSUPPORTED, "zg_lookup_product_terms_dev: n too large");
+    if (!n) return ZG_OK;
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    ProofConst hc;  // (a one-entry batch: lookup 0 of proof 0, product 0)
+    memset(&hc, 0, sizeof(hc));
+    hc.beta = to_fe(beta);
+    hc.gamma = to_fe(gamma);
+    ProofConst* dpc = nullptr;
+    ZG_TRY(poly_one_const(ctx, ws, hc, &dpc));
+    return poly_lookup_terms(ctx, dpc, 1, (const Fe*)d_input, (const Fe*)d_table, (const Fe*)d_permuted_input,
+                             (const Fe*)d_permuted_table, 0, 0, (Fe*)d_num, (Fe*)d_den, 1, 0, (uint32_t)n, 1);
+}
+
+int zg_fr_lincomb_dev(zg_ctx* ctx, const void* const* d_polys, const zg_fr* coeffs, size_t count, size_t n, const zg_fr* sub0,
+                      void* d_out) {
+    ZG_REQUIRE(ctx && d_out && (count == 0 || (d_polys && coeffs)), ZG_ERR_INVALID_ARG, "zg_fr_lincomb_dev: null argument");
+    ZG_REQUIRE(n < (1u << 28), ZG_ERR_UNSUPPORTED, "zg_fr_lincomb_dev: n too large");
+    for (size_t j = 0; j < count; j++) {
+        ZG_REQUIRE(d_polys[j], ZG_ERR_INVALID_ARG, "zg_fr_lincomb_dev: polynomial %zu is null", j);
+        ZG_REQUIRE(d_polys[j] != d_out, ZG_ERR_INVALID_ARG, "zg_fr_lincomb_dev: d_out is polynomial %zu", j);
+    }
+    ZG_ENTER(ctx);
+    Fe sub;
+    if (sub0) sub = to_fe(sub0);
+    return poly_lincomb(ctx, reinterpret_cast<const Fe* const*>(d_polys), reinterpret_cast<const Fe*>(coeffs), count, (uint32_t)n,
+                        sub0 ? &sub : nullptr, (Fe*)d_out);
+}
+
+int zg_fr_random_dev(zg_ctx* ctx, const uint8_t key[32], uint32_t tag, void* d_out, size_t count) {
+    ZG_REQUIRE(ctx && key && (d_out || !count), ZG_ERR_INVALID_ARG, "zg_fr_random_dev: null argument");
+    ZG_REQUIRE(count <= 0xffffffffull, ZG_ERR_UNSUPPORTED, "zg_fr_random_dev: %zu scalars", count);
+    ZG_ENTER(ctx);
+    uint32_t kw[8];
+    memcpy(kw, key, sizeof(kw));
+    return poly_rand_fill(ctx, kw, tag, (Fe*)d_out, (uint32_t)count);
 }
 
 }  // extern "C"

@@ -1087,9 +1087,11 @@ int zg_prover_fetch(zg_prover* p, uint32_t what, uint32_t index, zg_fr* out, siz
 // prover's resident proving key: from the coefficient forms of the witness-side polynomials and the four challenges
 // to h on EvaluationDomain's extended coset (2^ext_k values, library form).  Host pointers: this is the
 // arithmetic-level entry; inside create_proof the same kernel runs on slabs that never leave HBM.
-int zg_prover_evaluate_h(zg_prover* p, const zg_fr* advice_polys, const zg_fr* instance_polys, const zg_fr* perm_z_polys,
-                         const zg_fr* lookup_z_polys, const zg_fr* permuted_polys, const zg_fr* theta, const zg_fr* beta,
-                         const zg_fr* gamma, const zg_fr* y, zg_fr* h_out) {
+// (from_device: the families and h_out are device pointers -- zg_prover_evaluate_h_dev; the copies into slot 0 are then
+//  device-to-device, h is scaled straight into h_out and the call returns with the work queued)
+static int evaluate_h_impl(zg_prover* p, const void* advice_polys, const void* instance_polys, const void* perm_z_polys,
+                           const void* lookup_z_polys, const void* permuted_polys, const zg_fr* theta, const zg_fr* beta,
+                           const zg_fr* gamma, const zg_fr* y, void* h_out, bool from_device) {
     ZG_REQUIRE(p && theta && beta && gamma && y && h_out, ZG_ERR_INVALID_ARG, "zg_prover_evaluate_h: null argument");
     const PkDev& pk = *p->pk;
     ZG_REQUIRE((advice_polys || !pk.A) && (instance_polys || !pk.I) && (perm_z_polys || !pk.sets) &&
@@ -1102,30 +1104,101 @@ int zg_prover_evaluate_h(zg_prover* p, const zg_fr* advice_polys, const zg_fr* i
     const uint32_t n = pk.n;
     p->have_last = false;
     // slot 0's coefficient slab, in its order: advice, instance, permutation z, lookup z, a'/s'
-    struct Fam { const zg_fr* src; uint32_t ix, count; };
+    struct Fam { const void* src; uint32_t ix, count; };
+    const hipMemcpyKind kind = from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const Fam fams[] = {{advice_polys, p->ix_adv, pk.A}, {instance_polys, p->ix_inst, pk.I}, {perm_z_polys, p->ix_pz, pk.sets},
                         {lookup_z_polys, p->ix_lz, pk.NL}, {permuted_polys, p->ix_perm, 2 * pk.NL}};
     for (const Fam& f : fams)
         if (f.count)
-            ZG_HIP(hipMemcpyAsync(p->pp + (size_t)(f.ix - p->nsh) * n, f.src, (size_t)f.count * n * 32, hipMemcpyHostToDevice, st));
+            ZG_HIP(hipMemcpyAsync(p->pp + (size_t)(f.ix - p->nsh) * n, f.src, (size_t)f.count * n * 32, kind, st));
     ProofConst& c = p->hpc[0];
     memset(&c, 0, sizeof(c));
     c.theta = to_fe(theta); c.beta = to_fe(beta); c.gamma = to_fe(gamma);
     evalh_consts(c, to_fe(y), pk);
     p->pin.stage_reset();
     ZG_TRY(upload_consts(p, 1));
+    // (the scalars leave through the pinned staging range, which the next call on this prover rewinds: the device form
+    //  returns with work queued, so it waits here until they -- and the copies above -- have arrived)
+    if (from_device) ZG_HIP(hipStreamSynchronize(st));
     const PkDev::Dom& d = pk.dom[0];
     ZG_TRY(coeff_to_coset_dev(ctx, p->pp + (size_t)(p->ix_adv - p->nsh) * n, n, n, p->dbuf[0].cos, d.en, p->ncos, d.ek, pk.hat, pk.shift(d.zpow)));
     const EvalHArgs a = evalh_args(p, 0);
     ZG_TRY(poly_evaluate_h(ctx, a, d.en, 1, pk.A + pk.I + pk.F, (double)d.en));
+    // (the nine-limb kernel leaves h as x * 2^261: hand back the library form)
+    const Fe unhat = pk.hat ? Fr::inv(Fr::from_u64(32)) : Fr::one();
+    if (from_device) return poly_scale(ctx, p->dbuf[0].h, (Fe*)h_out, d.en, unhat);
     WsScope ws(ctx);
     Fe* tmp = ws.get<Fe>(d.en);
     if (!tmp) return ZG_ERR_OOM;
-    // (the nine-limb kernel leaves h as x * 2^261: hand back the library form)
-    ZG_TRY(poly_scale(ctx, p->dbuf[0].h, tmp, d.en, pk.hat ? Fr::inv(Fr::from_u64(32)) : Fr::one()));
+    ZG_TRY(poly_scale(ctx, p->dbuf[0].h, tmp, d.en, unhat));
     ZG_HIP(hipMemcpyAsync(h_out, tmp, (size_t)d.en * 32, hipMemcpyDeviceToHost, st));
     ZG_HIP(hipStreamSynchronize(st));
     return ZG_OK;
+}
+
+int zg_prover_evaluate_h(zg_prover* p, const zg_fr* advice_polys, const zg_fr* instance_polys, const zg_fr* perm_z_polys,
+                         const zg_fr* lookup_z_polys, const zg_fr* permuted_polys, const zg_fr* theta, const zg_fr* beta,
+                         const zg_fr* gamma, const zg_fr* y, zg_fr* h_out) {
+    return evaluate_h_impl(p, advice_polys, instance_polys, perm_z_polys, lookup_z_polys, permuted_polys, theta, beta, gamma, y,
+                           h_out, false);
+}
+
+int zg_prover_evaluate_h_dev(zg_prover* p, const void* d_advice_polys, const void* d_instance_polys, const void* d_perm_z_polys,
+                             const void* d_lookup_z_polys, const void* d_permuted_polys, const zg_fr* theta, const zg_fr* beta,
+                             const zg_fr* gamma, const zg_fr* y, void* d_h_out) {
+    return evaluate_h_impl(p, d_advice_polys, d_instance_polys, d_perm_z_polys, d_lookup_z_polys, d_permuted_polys, theta, beta,
+                           gamma, y, d_h_out, true);
+}
+
+// ---- the arithmetic level on device pointers: the prover's launch helpers over the CALLER's Lagrange columns and the
+// resident key (fixed columns, sigma values, the circuit image)
+static Cols caller_cols(const PkDev& pk, const void* d_advice, const void* d_instance) {
+    Cols c;
+    c.fixed = pk.fixed_val; c.advice = (const Fe*)d_advice; c.instance = (const Fe*)d_instance;
+    c.log_size = pk.k; c.rot_scale = 1;
+    c.adv_bs = 0; c.inst_bs = 0;
+    return c;
+}
+
+int zg_prover_lookup_compress_dev(zg_prover* p, uint32_t lookup, const void* d_advice, const void* d_instance, const zg_fr* theta,
+                                  void* d_input, void* d_table) {
+    ZG_REQUIRE(p && theta && d_input && d_table, ZG_ERR_INVALID_ARG, "zg_prover_lookup_compress_dev: null argument");
+    const PkDev& pk = *p->pk;
+    ZG_REQUIRE(lookup < pk.NL, ZG_ERR_INVALID_ARG, "zg_prover_lookup_compress_dev: lookup %u of %u", lookup, pk.NL);
+    ZG_REQUIRE((d_advice || !pk.A) && (d_instance || !pk.I), ZG_ERR_INVALID_ARG, "zg_prover_lookup_compress_dev: a column family is missing");
+    zg_ctx* ctx = p->ctx;
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    ProofConst hc;
+    memset(&hc, 0, sizeof(hc));
+    hc.theta = to_fe(theta);
+    ProofConst* dpc = nullptr;
+    ZG_TRY(poly_one_const(ctx, ws, hc, &dpc));
+    DevCircuit one = pk.dc;  // a circuit of ONE lookup: the kernel's lookup 0, written at column 0 of the outputs
+    one.lookups = pk.dc.lookups + lookup;
+    one.n_lookups = 1;
+    return poly_lookup_compress(ctx, one, caller_cols(pk, d_advice, d_instance), dpc, 1, (Fe*)d_input, (Fe*)d_table, pk.n);
+}
+
+uint32_t zg_prover_permutation_sets(const zg_prover* p) { return p ? p->pk->sets : 0; }
+
+int zg_prover_permutation_terms_dev(zg_prover* p, uint32_t set, const void* d_advice, const void* d_instance, const zg_fr* beta,
+                                    const zg_fr* gamma, void* d_num, void* d_den) {
+    ZG_REQUIRE(p && beta && gamma && d_num && d_den, ZG_ERR_INVALID_ARG, "zg_prover_permutation_terms_dev: null argument");
+    const PkDev& pk = *p->pk;
+    ZG_REQUIRE(set < pk.sets, ZG_ERR_INVALID_ARG, "zg_prover_permutation_terms_dev: set %u of %u", set, pk.sets);
+    ZG_REQUIRE((d_advice || !pk.A) && (d_instance || !pk.I), ZG_ERR_INVALID_ARG, "zg_prover_permutation_terms_dev: a column family is missing");
+    zg_ctx* ctx = p->ctx;
+    ZG_ENTER(ctx);
+    WsScope ws(ctx);
+    ProofConst hc;
+    memset(&hc, 0, sizeof(hc));
+    hc.beta = to_fe(beta);
+    hc.gamma = to_fe(gamma);
+    ProofConst* dpc = nullptr;
+    ZG_TRY(poly_one_const(ctx, ws, hc, &dpc));
+    return poly_perm_terms(ctx, pk.dc, caller_cols(pk, d_advice, d_instance), dpc, 1, pk.sigma_val, pk.omega_tw, (Fe*)d_num,
+                           (Fe*)d_den, 1, pk.n, (int)set);
 }
 
 // keygen_vk's commit_lagrange of every fixed column and permutation polynomial, with the MSM the prover commits with

@@ -53,6 +53,8 @@ def load() -> ctypes.CDLL:
     lib.zg_ctx_destroy.restype = None
     lib.zg_bases_free.argtypes = [c_void_p]
     lib.zg_bases_free.restype = None
+    lib.zg_prover_permutation_sets.restype = c_uint32
+    lib.zg_prover_permutation_sets.argtypes = [c_void_p]
     lib.zg_msm_var.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]
     lib.zg_msm_var_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint32, c_void_p]
     lib.zg_msm_var_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]
@@ -85,6 +87,9 @@ ABI_SYMBOLS = [
     "zg_prover_proof_size_multi", "zg_prover_prove_multi", "zg_prover_prove_multi_dev", "zg_prover_prove_images_multi",
     "zg_verifier_verify_multi",
     "zg_wnn_create", "zg_wnn_destroy", "zg_wnn_predict", "zg_wnn_predict_dev", "zg_wnn_accuracy",
+    "zg_prover_evaluate_h_dev", "zg_prover_lookup_compress_dev", "zg_permute_expression_pair_dev",
+    "zg_permute_expression_pair", "zg_lookup_product_terms_dev", "zg_prover_permutation_sets",
+    "zg_prover_permutation_terms_dev", "zg_fr_lincomb_dev", "zg_fr_random_dev",
 ]
 
 # zg_params_check: bits of `failed`
@@ -519,6 +524,40 @@ class Ctx:
         _check(self.lib.zg_kate_division_dev(self.h, c_void_p(d_a), c_size_t(n), _ptr(_fr(z)), c_void_p(d_q)))
         self.sync()
 
+    # ---- the arithmetic level on device pointers ----
+    def permute_expression_pair_dev(self, d_input: int, d_table: int, k: int, usable: int, d_pin: int, d_ptab: int):
+        """lookup::prover::permute_expression_pair on rows < usable; zeros behind them.  Blocks (ZG_ERR_CONSTRAINT)."""
+        _check(self.lib.zg_permute_expression_pair_dev(self.h, c_void_p(d_input), c_void_p(d_table), c_uint32(k),
+                                                       c_uint32(usable), c_void_p(d_pin), c_void_p(d_ptab)))
+
+    def permute_expression_pair(self, inp: np.ndarray, table: np.ndarray, usable: int):
+        inp, table = _fr(inp).reshape(-1, 4), _fr(table).reshape(-1, 4)
+        n = inp.shape[0]
+        assert table.shape[0] == n and n == 1 << (n.bit_length() - 1)
+        a, s = np.zeros_like(inp), np.zeros_like(inp)
+        _check(self.lib.zg_permute_expression_pair(self.h, _ptr(inp), _ptr(table), c_uint32(n.bit_length() - 1),
+                                                   c_uint32(usable), _ptr(a), _ptr(s)))
+        return a, s
+
+    def lookup_product_terms_dev(self, d_input: int, d_table: int, d_pin: int, d_ptab: int, beta, gamma, n: int,
+                                 d_num: int, d_den: int):
+        _check(self.lib.zg_lookup_product_terms_dev(self.h, c_void_p(d_input), c_void_p(d_table), c_void_p(d_pin),
+                                                    c_void_p(d_ptab), _ptr(_fr(beta)), _ptr(_fr(gamma)), c_size_t(n),
+                                                    c_void_p(d_num), c_void_p(d_den)))
+
+    def fr_lincomb_dev(self, d_polys, coeffs, n: int, d_out: int, sub0=None):
+        """d_out[i] = sum_j coeffs[j] * d_polys[j][i] (- sub0 at i = 0); d_polys: device addresses, coeffs: uint64[count, 4]."""
+        count = len(d_polys)
+        ptrs = (c_void_p * max(count, 1))(*[int(a) for a in d_polys])
+        cf = _fr(np.asarray(coeffs, dtype=np.uint64).reshape(-1, 4)) if count else np.zeros((1, 4), np.uint64)
+        assert count == 0 or cf.shape[0] == count
+        _check(self.lib.zg_fr_lincomb_dev(self.h, ptrs, _ptr(cf), c_size_t(count), c_size_t(n),
+                                          None if sub0 is None else _ptr(_fr(sub0)), c_void_p(d_out)))
+
+    def fr_random_dev(self, seed, tag: int, d_out: int, count: int):
+        """d_out[i] = rand_fr(key, tag, i): the blinding scalars of the prover level, under the same 32-byte key."""
+        _check(self.lib.zg_fr_random_dev(self.h, rng_key(seed), c_uint32(tag), c_void_p(d_out), c_size_t(count)))
+
     def coeff_to_extended(self, coeffs: np.ndarray, k: int, ext_k: int) -> np.ndarray:
         coeffs = _fr(coeffs).reshape(-1, 4)
         assert coeffs.shape[0] == 1 << k
@@ -878,6 +917,29 @@ class Prover:
         _check(self.ctx.lib.zg_prover_evaluate_h(self.h, *ptrs, _ptr(_fr(theta)), _ptr(_fr(beta)), _ptr(_fr(gamma)),
                                                  _ptr(_fr(y)), _ptr(out)))
         return out
+
+    def evaluate_h_dev(self, d_advice_polys: int, d_instance_polys: int, d_perm_z_polys: int, d_lookup_z_polys: int,
+                       d_permuted_polys: int, theta, beta, gamma, y, d_h_out: int):
+        """evaluate_h with every family and h in HBM (0 = a family the circuit does not have); asynchronous."""
+        ptrs = [c_void_p(a) if a else None for a in (d_advice_polys, d_instance_polys, d_perm_z_polys, d_lookup_z_polys,
+                                                     d_permuted_polys)]
+        _check(self.ctx.lib.zg_prover_evaluate_h_dev(self.h, *ptrs, _ptr(_fr(theta)), _ptr(_fr(beta)), _ptr(_fr(gamma)),
+                                                     _ptr(_fr(y)), c_void_p(d_h_out)))
+
+    def lookup_compress_dev(self, lookup: int, d_advice: int, d_instance: int, theta, d_input: int, d_table: int):
+        """compress_expressions of lookup `lookup` over the caller's Lagrange columns ([count][2^k] in HBM)."""
+        _check(self.ctx.lib.zg_prover_lookup_compress_dev(self.h, c_uint32(lookup), c_void_p(d_advice) if d_advice else None,
+                                                          c_void_p(d_instance) if d_instance else None, _ptr(_fr(theta)),
+                                                          c_void_p(d_input), c_void_p(d_table)))
+
+    def permutation_sets(self) -> int:
+        return int(self.ctx.lib.zg_prover_permutation_sets(self.h))
+
+    def permutation_terms_dev(self, s: int, d_advice: int, d_instance: int, beta, gamma, d_num: int, d_den: int):
+        """permutation::prover::commit's factors of column set `s`; chaining the sets is the caller's job."""
+        _check(self.ctx.lib.zg_prover_permutation_terms_dev(self.h, c_uint32(s), c_void_p(d_advice) if d_advice else None,
+                                                            c_void_p(d_instance) if d_instance else None, _ptr(_fr(beta)),
+                                                            _ptr(_fr(gamma)), c_void_p(d_num), c_void_p(d_den)))
 
     def set_overlap(self, enable, digit_tables: bool = False):
         """True (default): transforms on a side stream (latency); False: one stream per proof (throughput).

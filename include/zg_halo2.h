@@ -571,6 +571,76 @@ int zg_prover_enable_digit_tables(zg_prover *p, uint64_t max_bytes, uint64_t *by
 int zg_prover_evaluate_h(zg_prover *p, const zg_fr *advice_polys, const zg_fr *instance_polys, const zg_fr *perm_z_polys,
                          const zg_fr *lookup_z_polys, const zg_fr *permuted_polys, const zg_fr *theta, const zg_fr *beta,
                          const zg_fr *gamma, const zg_fr *y, zg_fr *h_out);
+/* The same (Evaluator::evaluate_h + the division by X^n - 1) with every polynomial family and d_h_out ([2^ext_k], library
+ * form) as DEVICE pointers: the families are copied device-to-device into slot 0, nothing crosses PCIe but the four
+ * challenges.  A family the circuit does not have may be NULL.  The call waits until those copies and the challenges have
+ * arrived (work queued on the stream before it completes); the transforms, the evaluation and the write of d_h_out are
+ * then asynchronous on the context stream. */
+int zg_prover_evaluate_h_dev(zg_prover *p, const void *d_advice_polys, const void *d_instance_polys,
+                             const void *d_perm_z_polys, const void *d_lookup_z_polys, const void *d_permuted_polys,
+                             const zg_fr *theta, const zg_fr *beta, const zg_fr *gamma, const zg_fr *y, void *d_h_out);
+
+/* ---- the arithmetic level on device pointers: the steps of create_proof between its MSMs
+ * and transforms, for a caller that keeps halo2's own create_proof and holds its columns in HBM.  Columns are [count][2^k],
+ * contiguous, zg_fr in Montgomery form.  Every entry holds the context lock and takes its scratch from the workspace pool.
+ * The entries that take challenges (theta / beta / gamma) or report an error upload those scalars first, which waits for the
+ * work queued on the stream before it; their kernels are then asynchronous on the context stream like every _dev entry. */
+
+/* lookup::prover::Argument::commit_permuted's `compress_expressions` (halo2_proofs src/plonk/lookup/prover.rs) for lookup
+ * `lookup` of the prover's circuit: row i of d_input / d_table ([2^k] each) is the theta-fold of the lookup's input / table
+ * expressions at row i -- sum_e theta^(width-1-e) expr_e, the first expression entering as it is -- over the caller's
+ * Lagrange columns d_advice [n_advice][2^k], d_instance [n_instance][2^k] (either may be NULL when the circuit has none) and
+ * the prover's resident fixed columns.  A query with rotation t reads row (i + t) mod 2^k.  All 2^k rows are written.
+ * lookup >= n_lookups is ZG_ERR_INVALID_ARG. */
+int zg_prover_lookup_compress_dev(zg_prover *p, uint32_t lookup, const void *d_advice, const void *d_instance,
+                                  const zg_fr *theta, void *d_input, void *d_table);
+/* lookup::prover::permute_expression_pair on rows < usable of two [2^k] columns: d_permuted_input = a', the input sorted
+ * by canonical value (Fr: Ord); d_permuted_table = s', which holds at the first row of every distinct a' value that same
+ * value (one instance is taken out of the table multiset) and at the repeated rows the left-over table values, ascending
+ * left-overs going to the repeated rows taken from the END (upstream pops a Vec of repeated rows).  Rows >= usable of both
+ * outputs are written as ZERO: the caller puts its blinding there, as upstream does after the call.  The inputs are not
+ * modified; an output may not alias an input.  4 <= k <= 20, else ZG_ERR_UNSUPPORTED (the range of the prover's own
+ * path: its sort works on whole power-of-two columns and its scans on at most 2^20 rows); usable = 0 or usable > 2^k is
+ * ZG_ERR_INVALID_ARG.  An input value that the table does not hold is ZG_ERR_CONSTRAINT (Error::ConstraintSystemFailure),
+ * the outputs are then undefined: to report it this entry BLOCKS until the device has finished -- the one entry of this
+ * group that does. */
+int zg_permute_expression_pair_dev(zg_ctx *ctx, const void *d_input, const void *d_table, uint32_t k, uint32_t usable,
+                                   void *d_permuted_input, void *d_permuted_table);
+/* Host-pointer form of the same ([2^k] each); blocking. */
+int zg_permute_expression_pair(zg_ctx *ctx, const zg_fr *input, const zg_fr *table, uint32_t k, uint32_t usable,
+                               zg_fr *permuted_input, zg_fr *permuted_table);
+/* lookup::prover::Permuted::commit_product's factors on all n rows: num[i] = (input[i] + beta)(table[i] + gamma),
+ * den[i] = (a'[i] + beta)(s'[i] + gamma).  The running product itself is zg_grand_product_dev(num, den). */
+int zg_lookup_product_terms_dev(zg_ctx *ctx, const void *d_input, const void *d_table, const void *d_permuted_input,
+                                const void *d_permuted_table, const zg_fr *beta, const zg_fr *gamma, size_t n,
+                                void *d_num, void *d_den);
+/* permutation::Argument::commit (halo2_proofs src/plonk/permutation/prover.rs) works on the permutation columns in
+ * chunks of cs_degree - 2: the number of those column sets, 0 for a circuit without permutation columns. */
+uint32_t zg_prover_permutation_sets(const zg_prover *p);
+/* permutation::prover::commit's factors of column set `set` on all 2^k rows:
+ *   num[i] = prod_col (v_col[i] + beta * delta^col * omega^i + gamma),  den[i] = prod_col (v_col[i] + beta * sigma_col[i] + gamma)
+ * over the columns col of the set (indices into zg_circuit.perm_columns; a last set that is not full holds fewer
+ * factors), v_col the Lagrange column the entry names -- from d_advice [n_advice][2^k], d_instance [n_instance][2^k] or
+ * the resident fixed columns -- and sigma_col from the resident key.  Chaining the sets is the caller's job, as it is
+ * upstream's: z of set s starts from z0 = z of set s - 1 at row `usable` = 2^k - (blinding_factors + 1), passed to
+ * zg_grand_product_dev.  set >= zg_prover_permutation_sets is ZG_ERR_INVALID_ARG. */
+int zg_prover_permutation_terms_dev(zg_prover *p, uint32_t set, const void *d_advice, const void *d_instance,
+                                    const zg_fr *beta, const zg_fr *gamma, void *d_num, void *d_den);
+/* The linear combinations of polynomials create_proof makes outside its evaluator: vanishing::Argument::construct's
+ * sum_i x^(n i) h_i (halo2_proofs src/plonk/vanishing/prover.rs) and ProverGWC::create_proof's sum_i v^i p_i - eval
+ * (src/poly/kzg/multiopen/gwc/prover.rs):  d_out[i] = sum_j coeffs[j] * d_polys[j][i], i < n, and *sub0 (may be NULL) is
+ * subtracted at i = 0.  d_polys and coeffs are HOST arrays of `count` entries; d_polys[j] is a device pointer to n
+ * elements (the same one may occur several times).  count = 0 gives zero (minus *sub0).  d_out equal to an input pointer is
+ * ZG_ERR_INVALID_ARG; n >= 2^28 is ZG_ERR_UNSUPPORTED.  Pointers and coefficients travel in the kernel arguments,
+ * ZG_LINCOMB_CHUNK terms per launch (nothing is uploaded, nothing waits).  What is written is canonical. */
+#define ZG_LINCOMB_CHUNK 64
+int zg_fr_lincomb_dev(zg_ctx *ctx, const void *const *d_polys, const zg_fr *coeffs, size_t count, size_t n,
+                      const zg_fr *sub0, void *d_out);
+/* d_out[i] = rand_fr(key, tag, i), i < count < 2^32: the scalars create_proof draws from its RNG, as the prover level
+ * draws them (above, "Randomness") -- vanishing::Argument::commit's random polynomial is tag 6, and a caller that wants
+ * the prover level's bytes blinds with the other tags of DESIGN.md. */
+int zg_fr_random_dev(zg_ctx *ctx, const uint8_t key[32], uint32_t tag, void *d_out, size_t count);
+
 /* z[0] = z0, z[i+1] = z[i] * num[i] / den[i], i + 1 < n  (the running product of lookup::prover::commit_product and
  * permutation::prover::commit; a zero denominator gives ratio 0, as halo2's BatchInvert leaves zeros alone).
  * Host pointers / device pointers. */
