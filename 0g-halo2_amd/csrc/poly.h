@@ -117,7 +117,18 @@ struct EvalHArgs {
     // grouped form of the nine-limb evaluation: the n_terms permutation / lookup terms that follow the gates are
     // weighted by pc->eh_ypow and summed per l-polynomial (0: the plain Horner fold in y)
     uint32_t n_terms;
+    // The terms by degree (poly_evaluate_h's modes EH_BOTH / EH_HIGH, the split domain's two parts): gate_cls[g] = (gate g
+    // is a high term) | e << 1, its class's Horner carry being multiplied by y^e before the gate is added; tail_lo /
+    // tail_hi = the power of y each class's gate sum ends on; bit s of set_hi / bit l of lk_hi = the product term of
+    // permutation set s / lookup l is high (every other term after the gates is low).  EH_BOTH stores the sum of all
+    // terms to h and the high terms' sum to h_hi (proof b's at h_hi + b * h_bs); EH_HIGH stores the high terms' to h.
+    const uint32_t* gate_cls;
+    uint32_t tail_lo, tail_hi, set_hi;
+    uint64_t lk_hi;
+    Fe* h_hi;
 };
+// which terms a launch of evaluate_h evaluates (EvalHArgs::gate_cls)
+enum EvalHMode : int { EH_ALL = 0, EH_BOTH = 1, EH_HIGH = 2 };
 
 // blinding scalar = f(seed, tag, index); identical to the oracle's definition
 enum {
@@ -183,8 +194,10 @@ size_t poly_grand_product_tmp_elems(uint32_t n, uint32_t batch);
 int poly_grand_product(zg_ctx* ctx, const Fe* num, const Fe* den, const Fe* d_z0, Fe* z, Fe* tmp, uint32_t n,
                        uint32_t batch, uint32_t chain, uint32_t last, uint32_t per = 0, size_t z_outer = 0, int half = 0);
 // n_columns = advice + instance + fixed columns of the circuit, unit_share = the rows of EvaluationDomain's extended domain
-// this launch stands for (both only shape the profile's byte charges)
-int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, uint32_t n_columns, double unit_share);
+// this launch stands for (both only shape the profile's byte charges); mode: every term into h, or the terms by degree
+// (EvalHArgs::gate_cls -- the grouped nine-limb kernel only)
+int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, uint32_t n_columns, double unit_share,
+                    EvalHMode mode = EH_ALL);
 // out[i] = U(col[(i + rot_off) mod en]),  U(x) = sum_{k=1..count} coef[k-1] x^k; everything in the 2^261 form
 int poly_gate_factor(zg_ctx* ctx, const Fe* col, uint32_t rot_off, uint32_t en, const Fe* coef, uint32_t count, Fe* out);
 // Coefficient-form polynomials a kernel may be asked for by index: indices below nsh name the proving key's

@@ -879,8 +879,16 @@ int poly_gate_factor(zg_ctx* ctx, const Fe* col, uint32_t rot_off, uint32_t en, 
 // round-robin, so -- as in ntt_pass_kernel -- workgroup L is renumbered to put consecutive numbers on ONE XCD: the nb
 // proofs of a tile then run side by side behind one L2, and the key's lines of that tile (fixed cosets, gate slabs, sigma,
 // l-polynomials: two thirds of what a row reads) are fetched once per batch instead of once per proof.
-template <bool GROUPED>
+//
+// MODE (GROUPED only): the terms by their degree, for the two parts of the split domain.  A term of degree <= m1 + 1 (low)
+// contributes a quotient part of degree < m1 n, which the first part's m1 n points fix alone; only the others (high) are
+// needed on the second part.  EH_BOTH (part 1) keeps the two classes in separate sums -- each class's gates in a Horner
+// carry of its own that skips the other class's places by a power of y (EvalHArgs::gate_cls), the high permutation sets
+// and lookup products in a fourth weighted sum -- and stores all terms / Z_H to h, the high ones / Z_H to h_hi; EH_HIGH
+// (part 2) evaluates the high terms alone and loads nothing that only a low term reads.  EH_ALL is the kernel as it was.
+template <bool GROUPED, int MODE = EH_ALL>
 __global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t en, uint32_t nb) {
+    static_assert(MODE == EH_ALL || GROUPED, "the terms by degree exist in the grouped form only");
     uint32_t bid = blockIdx.x;
     if ((gridDim.x & 7u) == 0) bid = (bid & 7u) * (gridDim.x >> 3) + (bid >> 3);
     const uint32_t tile = bid / nb;
@@ -908,7 +916,36 @@ __global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t 
         const Fe* base = q.kind == ZG_FIXED ? pr.cols.fixed : q.kind == ZG_ADVICE ? pr.cols.advice : pr.cols.instance;
         return ld9(base + ((size_t)q.column << a.cols.log_size) + ((idx + (uint32_t)(q.rotation * a.cols.rot_scale)) & mask));
     };
+    [[maybe_unused]] F9 vhi;  // MODE: the high gates' carry (`value` is the low gates')
+    if constexpr (MODE != EH_ALL) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) vhi.l[i] = 0;
+    }
     for (uint32_t g = 0; g < c.n_gates; g++) {
+        if constexpr (MODE != EH_ALL) {
+            const uint32_t cls = a.gate_cls[g];  // (wave-uniform)
+            if (MODE == EH_HIGH && !(cls & 1u)) continue;
+            const F9 inner = eval_poly9(c, a.monos_hat, pr.cols, a.gates_hat[g], idx);
+            const uint32_t common = a.gate_common[g];
+            const bool factored = common != 0xffffffffu;
+            F9 u = inner;
+            if (factored) {
+                const uint32_t slab = a.gate_slab[g];
+                const zg_poly uni = a.gate_uni[g];
+                if (slab != 0xffffffffu) u = ld9(a.gate_slabs + (size_t)slab * en + idx);
+                else if (uni.count) u = horner9(cell(common), a.uni_coef + uni.first, uni.count);
+                else u = cell(common);
+            }
+            // carry * y^e + gate: as fold2 / fold below, with the power of y that skips the other class's gates
+            auto step = [&](F9& carry) {
+                const F9 ye = f9_unpack(pc->eh_ypow[cls >> 1]);
+                if (factored) carry = Fr9::mul2<false>(f9_norm(carry), ye, u, inner);
+                else carry = f9_add(Fr9::mul(carry, ye), inner);
+            };
+            if (cls & 1u) step(vhi);
+            else step(value);
+            continue;
+        }
         const F9 inner = eval_poly9(c, a.monos_hat, pr.cols, a.gates_hat[g], idx);
         const uint32_t common = a.gate_common[g];  // (wave-uniform)
         if (common != 0xffffffffu) {
@@ -942,6 +979,108 @@ __global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t 
             ti = f9_add(Fr9::mul(ti, f9_unpack(pc->eh_theta)), eval_poly9(c, a.monos_hat, pr.cols, lk->tables[e], idx));
         }
     };
+    if constexpr (MODE != EH_ALL) {
+        // The grouped form below with the lactive sum in two, sa (low) and sh (high); the weights are the same.
+        constexpr bool LOW = MODE == EH_BOTH;  // the low terms are evaluated too
+        vhi = f9_norm(vhi);
+        uint32_t w = a.n_terms;
+        auto yw = [&](uint32_t e) { return f9_unpack(pc->eh_ypow[e]); };
+        F9 s0, sl, sa, sh;
+#pragma unroll
+        for (int i = 0; i < 9; i++) s0.l[i] = sl.l[i] = sa.l[i] = sh.l[i] = 0;
+        auto acc1 = [&](F9& s, uint32_t e, const F9& t) { s = f9_norm(f9_add(s, Fr9::mul(yw(e), t))); };
+        auto acc2 = [&](F9& s, uint32_t e, const F9& t, uint32_t e2, const F9& t2) {
+            s = f9_norm(f9_add(s, Fr9::mul2<false>(yw(e), t, yw(e2), t2)));
+        };
+        if (c.n_sets > 0) {
+            if (LOW) {
+                const F9 zf = ld9(pr.pz_cos + idx);
+                const F9 zl = ld9(pr.pz_cos + (size_t)(c.n_sets - 1) * en + idx);
+                acc1(s0, w - 1, f9_sub(one(), zf));
+                acc1(sl, w - 2, f9_sub(Fr9::sqr(zl), zl));
+                for (uint32_t s = 1; s < c.n_sets; s++) {
+                    const F9 t = f9_sub(ld9(pr.pz_cos + (size_t)s * en + idx), ld9(pr.pz_cos + (size_t)(s - 1) * en + r_last));
+                    acc1(s0, w - 2 - s, t);
+                }
+            }
+            w -= 2 + (c.n_sets - 1);
+            const bool scaled = a.sigma_sc != nullptr && pc->eh_scaled != 0;
+            F9 current_delta = ld9(a.ext_tw + idx);
+            if (!scaled) current_delta = Fr9::mul(f9_unpack(pc->eh_delta_start[a.zpow - 1]), current_delta);
+            for (uint32_t s = 0; s < c.n_sets; s++) {
+                uint32_t c0 = s * c.chunk, c1 = c0 + c.chunk;
+                if (c1 > c.n_perm) c1 = c.n_perm;
+                --w;
+                const bool high = (a.set_hi >> s) & 1u;  // (wave-uniform)
+                if (!LOW && !high) {  // (the unscaled term's delta chain walks on over the set's columns)
+                    if (!scaled)
+                        for (uint32_t col = c0; col < c1; col++) current_delta = Fr9::mul(current_delta, f9_unpack(a.delta));
+                    continue;
+                }
+                F9 left = ld9(pr.pz_cos + (size_t)s * en + r_next);
+                F9 right = ld9(pr.pz_cos + (size_t)s * en + idx);
+                for (uint32_t col = c0; col < c1; col++) {
+                    const zg_query q = c.perm_cols[col];
+                    const Fe* base = q.kind == ZG_FIXED ? pr.cols.fixed : q.kind == ZG_ADVICE ? pr.cols.advice : pr.cols.instance;
+                    const F9 v = ld9(base + ((size_t)q.column << a.cols.log_size) + idx);
+                    F9 fl, fr;
+                    if (scaled) {
+                        const F9 t = Fr9::mul(f9_add(v, f9_unpack(pc->eh_gamma)), f9_unpack(pc->eh_pcol[a.zpow - 1][col]));
+                        fl = f9_add(ld9(a.sigma_sc + (size_t)col * en + idx), t);
+                        fr = f9_add(current_delta, t);
+                    } else {
+                        const F9 sg = ld9(a.sigma_cos + (size_t)col * en + idx);
+                        fl = f9_norm(f9_add(f9_add(Fr9::mul(f9_unpack(pc->eh_beta), sg), v), f9_unpack(pc->eh_gamma)));
+                        fr = f9_norm(f9_add(f9_add(v, current_delta), f9_unpack(pc->eh_gamma)));
+                        current_delta = Fr9::mul(current_delta, f9_unpack(a.delta));
+                    }
+                    if (col + 1 < c1) {
+                        left = Fr9::mul(left, fl);
+                        right = Fr9::mul(right, fr);
+                    } else {
+                        left = Fr9::mul2<true>(left, f9_norm(fl), right, f9_norm(fr));
+                    }
+                }
+                const F9 t = Fr9::mul(scaled ? f9_unpack(pc->eh_pw[a.zpow - 1][s]) : yw(w), left);
+                if (high) sh = f9_norm(f9_add(sh, t));
+                else sa = f9_norm(f9_add(sa, t));
+            }
+        }
+        for (uint32_t l = 0; l < c.n_lookups; l++, w -= 5) {
+            const bool high = (a.lk_hi >> l) & 1u;  // (wave-uniform)
+            if (!LOW && !high) continue;
+            const DLookup* lk = c.lookups + l;
+            F9 ai, ti;
+            compress(lk, ai, ti);
+            const Fe* zc = pr.lz_cos + (size_t)l * en;
+            const Fe* ap = pr.pin_cos + (size_t)l * a.perm_stride;
+            const Fe* sp = pr.ptab_cos + (size_t)l * a.perm_stride;
+            const F9 z = ld9(zc + idx), apv = ld9(ap + idx), spv = ld9(sp + idx);
+            const F9 lft = Fr9::mul(f9_add(apv, f9_unpack(pc->eh_beta)), f9_norm(f9_add(spv, f9_unpack(pc->eh_gamma))));
+            const F9 rgt = Fr9::mul(f9_norm(f9_add(ai, f9_unpack(pc->eh_beta))), f9_norm(f9_add(ti, f9_unpack(pc->eh_gamma))));
+            const F9 prod = Fr9::mul2<true>(lft, ld9(zc + r_next), rgt, z);
+            if (high) acc1(sh, w - 3, prod);
+            if (LOW) {
+                const F9 ams = f9_sub(apv, spv);
+                acc2(s0, w - 1, f9_sub(one(), z), w - 4, ams);
+                acc1(sl, w - 2, f9_sub(Fr9::sqr(z), z));
+                const F9 last = Fr9::mul(ams, f9_sub(apv, ld9(ap + r_prev)));
+                if (high) acc1(sa, w - 5, last);
+                else acc2(sa, w - 3, prod, w - 5, last);
+            }
+        }
+        // high = vhi y^tail_hi + lactive sh;  low = value y^tail_lo + l0 s0 + llast sl + lactive sa;  both / Z_H
+        const F9 hi = Fr9::mul2<false>(vhi, yw(a.tail_hi), sh, lactive());
+        const F9 tz = ld9(a.t_eval + (idx & a.t_mask));
+        if (LOW) {
+            const F9 lo = f9_norm(f9_add(Fr9::mul2<false>(value, yw(a.tail_lo), s0, l0()), Fr9::mul2<false>(sl, llast(), sa, lactive())));
+            stg(pr.h + idx, f9_reduce_pack<Fr9Params>(Fr9::mul2<false>(lo, tz, hi, tz)));
+            stg(a.h_hi + (size_t)(bid - tile * nb) * a.h_bs + idx, f9_reduce_pack<Fr9Params>(Fr9::mul(hi, tz)));
+        } else {
+            stg(pr.h + idx, f9_reduce_pack<Fr9Params>(Fr9::mul(hi, tz)));
+        }
+        return;
+    }
     if (GROUPED) {
         // term i of the sequence (upstream's order) carries y^(T - 1 - i); `w` walks down from T - 1
         uint32_t w = a.n_terms;
@@ -1083,7 +1222,7 @@ __global__ __launch_bounds__(256) void evaluate_h9_kernel(EvalHArgs a, uint32_t 
     stg(pr.h + idx, f9_reduce_pack<Fr9Params>(value));
 }
 
-int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, uint32_t n_columns, double unit_share) {
+int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, uint32_t n_columns, double unit_share, EvalHMode mode) {
     if (!nb) return ZG_OK;
     ZG_REQUIRE(a.pc != nullptr && (a.zpow == 1 || a.zpow == 2), ZG_ERR_INVALID_ARG, "evaluate_h: per-proof scalars missing");
     // algorithmic bytes: every input coset read once + h written, as SURVEY.md 8d counts them -- `n_columns` advice,
@@ -1097,7 +1236,14 @@ int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, u
                "evaluate_h: the 2^261-form monomial table is missing");
     ZG_REQUIRE(!a.hat || c.n_gates == 0 || (a.gates_hat != nullptr && a.gate_common != nullptr && a.gate_uni != nullptr && a.uni_coef != nullptr && a.gate_slab != nullptr && a.gate_slabs != nullptr), ZG_ERR_INVALID_ARG,
                "evaluate_h: the factored gate table is missing");
-    if (a.hat && a.n_terms)
+    ZG_REQUIRE(mode == EH_ALL || (a.hat && a.n_terms && a.gate_cls != nullptr && (mode == EH_HIGH || a.h_hi != nullptr)),
+               ZG_ERR_INVALID_ARG, "evaluate_h: the terms by degree need the grouped nine-limb form and their classes");
+    const dim3 grid9((en + 255) / 256 * nb);
+    if (mode == EH_BOTH)
+        ZG_LAUNCH_U(ctx, "evaluate_h", nb * (arrays + 1.0) * en * 32.0, unit, (evaluate_h9_kernel<true, EH_BOTH>), grid9, dim3(256), 0, a, en, nb);
+    else if (mode == EH_HIGH)
+        ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, (evaluate_h9_kernel<true, EH_HIGH>), grid9, dim3(256), 0, a, en, nb);
+    else if (a.hat && a.n_terms)
         ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<true>, dim3((en + 255) / 256 * nb), dim3(256), 0, a, en, nb);
     else if (a.hat)
         ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<false>, dim3((en + 255) / 256 * nb), dim3(256), 0, a, en, nb);

@@ -226,6 +226,9 @@ struct ProveBatch {
     bool phase_cosets;  // the coset forms of a phase's columns: on the side stream while that phase's commitments run (latency
                         // form), or all at once before evaluate_h (throughput form)
     uint32_t dlo, dhi;
+    // The quotient's terms by degree (PkDev::QTerms): the second part of the split domain sees the high terms only -- and
+    // only the polynomials they read.  Not for a proof of several circuits, whose slots' quotients are folded per part.
+    bool by_degree;
     size_t pp_bs, adv_bs, inst_bs, perm_bs, zs_bs, pw_bs, wp_bs;  // strides between consecutive proofs
     // side stream: coefficient / coset forms of committed columns are computed there while the main stream runs the
     // commitment MSM (p->use_side == false: everything stays on the main stream -- the throughput configuration, where other
@@ -284,6 +287,7 @@ struct ProveBatch {
         phase_cosets = p->use_side || !split;
         dlo = split ? 1u : 0u;
         dhi = split ? 3u : 1u;
+        by_degree = split && pk.qt.active && p->qterms && !multi;
         pp_bs = (size_t)p->npp * n; adv_bs = (size_t)A * n; inst_bs = (size_t)I * n; perm_bs = (size_t)(2 * NL + 1) * n;
         zs_bs = (size_t)(S + NL + 1) * n; pw_bs = (size_t)p->max_points * n; wp_bs = (size_t)2 * p->max_points * n;
         polys.sh = pk.sh_polys; polys.pp = p->pp; polys.nsh = p->nsh; polys.n = n; polys.pp_bs = pp_bs;
@@ -334,13 +338,28 @@ struct ProveBatch {
         return g;
     }
     // coefficient forms (ix0 .. ix0 + per) of every proof -> their slabs on each part of the extended domain
+    // (by degree: the second part gets only the polynomials a high term reads -- PkDev::QTerms::part2 -- in runs of
+    //  neighbours, each to its own slab; the others' whole unit is then charged to the first part's launch)
     int to_cosets(zg_ctx* c, uint32_t ix0, uint32_t per) {
+        const uint8_t* keep = by_degree ? pk.qt.part2.data() + (ix0 - p->ix_adv) : nullptr;
+        uint32_t dropped = 0;
+        for (uint32_t i = 0; keep && i < per; i++) dropped += keep[i] ? 0u : 1u;
         for (uint32_t di = dlo; di < dhi; di++) {
             const PkDev::Dom& d = pk.dom[di];
-            const Grouping g = grouping(per, pp_bs, (size_t)p->ncos * d.en);
-            c->unit_next = (double)nb * per * ext_unit * ((double)d.en / parts_en);
-            ZG_TRY(coeff_to_coset_dev(c, pp_at(ix0), n, n, p->dbuf[di].cos + (size_t)(ix0 - p->ix_adv) * d.en, d.en, (size_t)nb * per,
-                                      d.ek, hat, pk.shift(d.zpow), &g));
+            const double share = (double)d.en / parts_en;
+            for (uint32_t r0 = 0; r0 < per;) {
+                uint32_t r1 = per;
+                if (keep && di == 2) {
+                    if (!keep[r0]) { r0++; continue; }
+                    for (r1 = r0; r1 < per && keep[r1];) r1++;
+                }
+                const uint32_t cnt = r1 - r0;
+                const Grouping g = grouping(cnt, pp_bs, (size_t)p->ncos * d.en);
+                c->unit_next = (double)nb * ext_unit * (cnt * share + (keep && di == 1 ? dropped * (1.0 - share) : 0.0));
+                ZG_TRY(coeff_to_coset_dev(c, pp_at(ix0 + r0), n, n, p->dbuf[di].cos + (size_t)(ix0 + r0 - p->ix_adv) * d.en, d.en,
+                                          (size_t)nb * cnt, d.ek, hat, pk.shift(d.zpow), &g));
+                r0 = r1;
+            }
         }
         return ZG_OK;
     }
@@ -420,7 +439,7 @@ struct ProveBatch {
         //  the last completed one's is a FIRST proof -- it may create tables and workspace, with synchronisations -- and is
         //  never gated: scheduling form, domain split, digit tables, batch, instance length, and the tuning generation,
         //  which every zg_tuning_set bumps)
-        return 1u | (uint64_t)p->use_side << 1 | (uint64_t)split << 2 | (uint64_t)(p->g->full_table.load() != nullptr) << 3 |
+        return 1u | (uint64_t)p->use_side << 1 | (uint64_t)split << 2 | (uint64_t)by_degree << 6 | (uint64_t)(p->g->full_table.load() != nullptr) << 3 |
                (uint64_t)(p->gl->full_table.load() != nullptr) << 4 | (uint64_t)ctx->msm_pair << 5 | (uint64_t)(nb & 0xFFu) << 8 |
                (uint64_t)(instance_len & 0xFFFFu) << 16 | (uint64_t)tuning_generation() << 32;
     }
@@ -730,7 +749,9 @@ struct ProveBatch {
         // ---- evaluate_h (+ division by X^n - 1) on every part of the extended domain, back to coefficients, h pieces
         for (uint32_t di = dlo; di < dhi; di++) {
             const EvalHArgs a = evalh_args(p, di);
-            ZG_TRY(poly_evaluate_h(ctx, a, pk.dom[di].en, nb, A + I + pk.F, (double)((size_t)1 << ek) * ((double)pk.dom[di].en / parts_en)));
+            // (by degree: all terms and, beside them, the high ones on the first part; the high ones alone on the second)
+            const EvalHMode mode = !by_degree ? EH_ALL : di == 1 ? EH_BOTH : EH_HIGH;
+            ZG_TRY(poly_evaluate_h(ctx, a, pk.dom[di].en, nb, A + I + pk.F, (double)((size_t)1 << ek) * ((double)pk.dom[di].en / parts_en), mode));
         }
         // multi: the slots' quotients into slot 0's, on each part, BEFORE the transforms back: those, the pieces and their
         // commitments then exist once (nq = 1)
@@ -755,8 +776,22 @@ struct ProveBatch {
             const size_t tb = (size_t)3 * L2;
             Fe *fold = p->split_tmp, *a2 = fold + L2, *bc = a2 + L2;
             ctx->unit_next = ext_inv_unit;  // (the three transforms of the split form stand for ONE extended_to_coeff)
+            //
+            // By degree, h = h_lo + h_hi with deg h_lo < L1 (both are polynomials when the statement holds: every term
+            // vanishes on H by itself).  A is as before -- all terms on the first coset, so A = h_lo + A_h with
+            // A_h = h_hi mod (X^L1 - c1) -- but only h_hi reaches past L1: B = (h_hi - A_h) / (c2 - c1) on the second coset,
+            // from the high terms there and A_h, the coefficients of the high terms on the first coset (ONE more transform
+            // of L1 points, into the first coset's h, which A has left).  h = A - c1 B + X^L1 B all the same.
             ZG_TRY(coset_to_coeff_dev(ctx, p->dbuf[1].h, d1.ek, L1, hp, hat, zeta, nq, L1, pp_bs));  // A, in place of the low pieces
-            ZG_TRY(poly_fold(ctx, nq, hp, pp_bs, L2, L1 / L2, e, fold, tb));                       // A mod (X^L2 - e)
+            const Fe* af = hp;
+            size_t af_bs = pp_bs;
+            if (by_degree) {
+                ctx->unit_next = 0.0;
+                ZG_TRY(coset_to_coeff_dev(ctx, p->h_hi, d1.ek, L1, p->dbuf[1].h, hat, zeta, nq, L1, L1));  // A_h
+                af = p->dbuf[1].h;
+                af_bs = L1;
+            }
+            ZG_TRY(poly_fold(ctx, nq, af, af_bs, L2, L1 / L2, e, fold, tb));                       // A (A_h) mod (X^L2 - e)
             ctx->unit_next = 0.0;
             ZG_TRY(coeff_to_coset_dev(ctx, fold, tb, L2, a2, tb, nq, d2.ek, false, zeta2));            // A on the second coset
             const Fe unhat = hat ? Fr::inv(Fr::from_u64(32)) : Fr::one();

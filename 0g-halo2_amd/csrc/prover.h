@@ -41,7 +41,9 @@ struct PkDev {
     Fe* sh_polys = nullptr;  // coefficient forms [F + P][n]: fixed, then sigma
     // The extended domain evaluate_h works on.  Either EvaluationDomain's own coset zeta * <omega_(2^ext_k)> (8n points
     // for degree 6), or -- split -- two cosets that together hold just the (degree - 1) * n points the quotient needs:
-    // zeta * <omega_(m1 n)> and zeta^2 * <omega_(m2 n)>, m1 + m2 = degree - 1 (4n + n).  Every coset slab exists per part.
+    // zeta * <omega_(m1 n)> and zeta^2 * <omega_(m2 n)>, m1 + m2 = degree - 1 (4n + n).  Every coset slab exists per part;
+    // the second part is there for the terms of degree > m1 + 1 only (QTerms below): the others' share of the quotient has
+    // degree < m1 n and the first part fixes it alone, so a witness polynomial no high term reads is not transformed there.
     struct Dom {
         uint32_t ek = 0, en = 0;
         int zpow = 1;  // the coset shift is zeta^zpow
@@ -53,7 +55,19 @@ struct PkDev {
     Dom dom[3];           // [0]: the single coset; [1], [2]: the two parts of the split domain (when it applies)
     uint32_t nparts = 1;  // 1, or 3 when the split domain is prepared too
     uint32_t NG = 0;
-    CheckInfo ck;         // the witness check's share of the key (check.hip): made at the first zg_prover_check_*
+    // The quotient's terms by degree, as ConstraintSystem::degree counts them (classify_terms, prover.hip): a term of
+    // degree <= m1 + 1 is low, the others high.  `active`: the key has a split domain, at least one low term, and
+    // ProofConst::eh_ypow holds the powers of y the gates' weights need -- the quotient may then take the high terms
+    // alone on the second part (ProveBatch::quotient_queue).
+    struct QTerms {
+        bool active = false;
+        std::vector<uint8_t> gate_hi, set_hi, lk_hi;  // per gate / permutation set (product term) / lookup (product term)
+        std::vector<uint8_t> part2;                   // per coset slab of a proof (zg_prover::ncos): a high term reads it
+        uint32_t* gate_cls = nullptr;                 // EvalHArgs::gate_cls, on the device
+        uint32_t tail_lo = 0, tail_hi = 0, set_mask = 0;
+        uint64_t lk_mask = 0;
+    } qt;
+    CheckInfo ck;        // the witness check's share of the key (check.hip): made at the first zg_prover_check_*
     ~PkDev() {
         (void)hipSetDevice(device);
         for (void* q : owned) (void)hipFree(q);
@@ -138,6 +152,8 @@ struct zg_prover {
     };
     DomBuf dbuf[3];
     zg::Fe* split_tmp = nullptr;  // [cap][3 * dom[2].en]
+    zg::Fe* h_hi = nullptr;       // the high terms' quotient on the first part (pk->qt.active): [cap][dom[1].en]
+    bool qterms = true;  // zg_prover_set_quotient_terms: 0 = every term on both parts, as without low terms
     zg::Fe *adv_val = nullptr /* [cap][A][n] */, *inst_val = nullptr /* [cap][I][n] */;
     zg::Fe *cin = nullptr, *ctab = nullptr /* [cap * NL][n] each */, *perm = nullptr /* [cap][2NL + 1][n]: a'_l, s'_l, random */,
        *zs = nullptr /* [cap][S + NL + 1][n] */;

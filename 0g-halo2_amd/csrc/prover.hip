@@ -87,7 +87,9 @@ void evalh_consts(ProofConst& c, const Fe& y, const PkDev& pk) {
             *cst = Fr::mul(*cst, c261);
         Fe ypw[EH_MAX_YPOW];
         Fe pw = Fr::one();
-        for (uint32_t j = 0; j <= n_terms && j < EH_MAX_YPOW; j++) {
+        // (with the terms by degree the gates are weighted from this table too: up to y^(n_terms + gates - 1))
+        const uint32_t top = n_terms + (pk.qt.active ? pk.NG : 0u);
+        for (uint32_t j = 0; j <= top && j < EH_MAX_YPOW; j++) {
             ypw[j] = pw;
             c.eh_ypow[j] = Fr::mul(pw, c261);
             pw = Fr::mul(pw, y);
@@ -152,6 +154,9 @@ EvalHArgs evalh_args(const zg_prover* p, uint32_t di) {
     a.gate_slab = pk.gate_slab;
     a.gate_slabs = d.gate_slabs;
     a.h = p->dbuf[di].h;
+    a.gate_cls = pk.qt.gate_cls; a.tail_lo = pk.qt.tail_lo; a.tail_hi = pk.qt.tail_hi;
+    a.set_hi = pk.qt.set_mask; a.lk_hi = pk.qt.lk_mask;
+    a.h_hi = di == 1 ? p->h_hi : nullptr;
     return a;
 }
 
@@ -201,6 +206,8 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
         ZG_TRY(dalloc_into(own, &p->dbuf[di].h, c * k.dom[di].en));
     }
     if (k.nparts == 3) ZG_TRY(dalloc_into(own, &p->split_tmp, c * 3 * k.dom[2].en));
+    p->h_hi = nullptr;
+    if (k.qt.active) ZG_TRY(dalloc_into(own, &p->h_hi, c * k.dom[1].en));
     ZG_TRY(dalloc_into(own, &p->adv_val, c * A * n));
     ZG_TRY(dalloc_into(own, &p->inst_val, c * I * n));
     if (I) ZG_HIP(hipMemset(p->inst_val, 0, c * I * n * 32));  // rows past the instance stay zero (prove refills only what it must)
@@ -650,6 +657,80 @@ void choose_domain_parts(PkDev* pk) {
     }
 }
 
+// The quotient's terms by degree (PkDev::QTerms), degrees as ConstraintSystem::degree counts them: a gate's polynomial
+// degree, selector included; c + 2 for the product term of a permutation set of c columns; max(4, 2 + input degree + table
+// degree) for a lookup's product term; 2 or 3 for every other term (l0 / l_last / chaining terms of the permutation and
+// the lookups' other four), which are therefore always low: m1 >= 2 wherever the domain is split.  A witness polynomial is
+// needed on the second part when a high term queries it at any rotation.
+int classify_terms(PkDev* pk, const zg_circuit* cs) {
+    PkDev::QTerms& qt = pk->qt;
+    const uint32_t NG = cs->n_gates, S = pk->sets, NL = pk->NL, A = pk->A, I = pk->I;
+    uint32_t m1 = 1;
+    while (m1 * 2 <= pk->qpd) m1 *= 2;  // (choose_domain_parts' first part)
+    const uint32_t low_max = m1 + 1;
+    auto degree = [&](const zg_poly& q) {
+        uint32_t d = 0;
+        for (uint32_t m = q.first; m < q.first + q.count; m++) d = std::max<uint32_t>(d, cs->monomials[m].n_factors);
+        return d;
+    };
+    qt.gate_hi.assign(NG, 0);
+    qt.set_hi.assign(S, 0);
+    qt.lk_hi.assign(NL, 0);
+    qt.part2.assign((size_t)A + I + S + 3 * NL, 0);
+    auto mark_cell = [&](const zg_query& q) {
+        if (q.kind == ZG_ADVICE) qt.part2[q.column] = 1;
+        else if (q.kind == ZG_INSTANCE) qt.part2[A + q.column] = 1;
+    };
+    auto mark = [&](const zg_poly& q) {
+        for (uint32_t m = q.first; m < q.first + q.count; m++)
+            for (uint32_t f = 0; f < cs->monomials[m].n_factors; f++) mark_cell(cs->queries[cs->monomials[m].factors[f]]);
+    };
+    bool any_low = S + NL > 0;
+    std::vector<uint32_t> cls(NG ? NG : 1, 0);
+    uint32_t last[2] = {0xffffffffu, 0xffffffffu};
+    for (uint32_t g = 0; g < NG; g++) {
+        const uint32_t hi = degree(cs->gates[g]) > low_max ? 1u : 0u;
+        qt.gate_hi[g] = (uint8_t)hi;
+        any_low |= !hi;
+        if (hi) mark(cs->gates[g]);
+        cls[g] = hi | (last[hi] == 0xffffffffu ? 1u : g - last[hi]) << 1;
+        last[hi] = g;
+    }
+    const uint32_t T = evalh_terms(*pk);
+    qt.tail_lo = last[0] == 0xffffffffu ? 0u : T + NG - 1 - last[0];
+    qt.tail_hi = last[1] == 0xffffffffu ? 0u : T + NG - 1 - last[1];
+    qt.set_mask = 0;
+    qt.lk_mask = 0;
+    for (uint32_t s = 0; s < S; s++) {
+        const uint32_t c0 = s * pk->chunk, c1 = std::min(pk->P, c0 + pk->chunk);
+        if (c1 - c0 + 2 <= low_max) continue;
+        qt.set_hi[s] = 1;
+        if (s < 32) qt.set_mask |= 1u << s;
+        qt.part2[A + I + s] = 1;
+        for (uint32_t col = c0; col < c1; col++) mark_cell(cs->perm_columns[col]);
+    }
+    for (uint32_t l = 0; l < NL; l++) {
+        const zg_lookup& lk = cs->lookups[l];
+        uint32_t din = 1, dtab = 1;  // (at least 1, as upstream counts them)
+        for (uint32_t e = 0; e < lk.width; e++) {
+            din = std::max(din, degree(lk.inputs[e]));
+            dtab = std::max(dtab, degree(lk.tables[e]));
+        }
+        if (std::max(4u, 2 + din + dtab) <= low_max) continue;
+        qt.lk_hi[l] = 1;
+        qt.lk_mask |= 1ull << l;
+        qt.part2[A + I + S + l] = 1;
+        qt.part2[A + I + S + NL + 2 * l] = qt.part2[A + I + S + NL + 2 * l + 1] = 1;
+        for (uint32_t e = 0; e < lk.width; e++) mark(lk.inputs[e]), mark(lk.tables[e]);
+    }
+    // (without low terms, without the split domain or its grouped nine-limb kernel, or with more terms than eh_ypow has
+    //  powers for, every term stays on both parts)
+    qt.active = pk->nparts == 3 && any_low && m1 >= 2 && T != 0 && T + NG < EH_MAX_YPOW && S <= 32 && NL < 64;
+    ZG_TRY(key_alloc(pk, &qt.gate_cls, cls.size()));
+    ZG_HIP(hipMemcpy(qt.gate_cls, cls.data(), cls.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return ZG_OK;
+}
+
 int alloc_key_slabs(PkDev* pk) {
     const uint32_t n = pk->n, F = pk->F, P = pk->P;
     ZG_TRY(key_alloc(pk, &pk->sh_polys, (size_t)(F + P) * n));
@@ -852,6 +933,7 @@ static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fi
     ZG_TRY(attach_bases(p, g, g_lagrange, shared_g, shared_gl));
     ZG_TRY(enable_tables(p));
     choose_domain_parts(pk);
+    ZG_TRY(classify_terms(pk, cs));
     ZG_TRY(alloc_key_slabs(pk));
     // keygen_pk's derived data: fixed / sigma polys + cosets, the gate slabs, l_0 / l_last / l_active_row, t_evaluations
     ZG_TRY(key_columns(ctx, pk, fixed_values, pk->F, pk->fixed_val, pk->sh_polys, &PkDev::Dom::fixed_cos));
@@ -917,6 +999,7 @@ int zg_prover_fork(const zg_prover* parent, zg_ctx* ctx, zg_prover** out) {
     p->use_side = parent->use_side;
     p->lat_split = parent->lat_split;
     p->naf_gl_w = parent->naf_gl_w;
+    p->qterms = parent->qterms;
     p->shard_lo = parent->shard_lo; p->shard_n = parent->shard_n; p->world = parent->world; p->rank = parent->rank;
     p->exchange = parent->exchange; p->exchange_user = parent->exchange_user;
     // (a communicator serialises its collectives on ONE stream: a fork does not inherit it)
@@ -980,6 +1063,28 @@ int zg_prover_phase_ms(const zg_prover* p, double* out, size_t cap) {
 int zg_prover_gate_stats(const zg_prover* p, uint64_t* out, size_t cap) {
     ZG_REQUIRE(p && out, ZG_ERR_INVALID_ARG, "zg_prover_gate_stats: null argument");
     for (size_t i = 0; i < cap && i < 4; i++) out[i] = p->gate_stats[i];
+    return ZG_OK;
+}
+
+int zg_prover_set_quotient_terms(zg_prover* p, int enable) {
+    ZG_REQUIRE(p, ZG_ERR_INVALID_ARG, "zg_prover_set_quotient_terms: null prover");
+    ZG_ENTER(p->ctx);
+    ZG_TRY(prover_drain(p));
+    p->qterms = enable != 0;
+    p->warm_sig = 0;  // (another launch sequence: the next proof is a first proof)
+    return ZG_OK;
+}
+
+int zg_prover_quotient_terms(const zg_prover* p, uint32_t* out, size_t cap, size_t* count) {
+    ZG_REQUIRE(p && count, ZG_ERR_INVALID_ARG, "zg_prover_quotient_terms: null argument");
+    const PkDev::QTerms& qt = p->pk->qt;
+    std::vector<uint32_t> v = {qt.active ? 1u : 0u, (uint32_t)qt.gate_hi.size(), (uint32_t)qt.set_hi.size(), (uint32_t)qt.lk_hi.size(),
+                               (uint32_t)qt.part2.size()};
+    for (const std::vector<uint8_t>* part : {&qt.gate_hi, &qt.set_hi, &qt.lk_hi, &qt.part2}) v.insert(v.end(), part->begin(), part->end());
+    *count = v.size();
+    if (!out) return ZG_OK;
+    ZG_REQUIRE(cap >= v.size(), ZG_ERR_INVALID_ARG, "zg_prover_quotient_terms: need %zu words", v.size());
+    memcpy(out, v.data(), v.size() * sizeof(uint32_t));
     return ZG_OK;
 }
 

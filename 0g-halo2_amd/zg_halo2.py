@@ -90,6 +90,7 @@ ABI_SYMBOLS = [
     "zg_prover_evaluate_h_dev", "zg_prover_lookup_compress_dev", "zg_permute_expression_pair_dev",
     "zg_permute_expression_pair", "zg_lookup_product_terms_dev", "zg_prover_permutation_sets",
     "zg_prover_permutation_terms_dev", "zg_fr_lincomb_dev", "zg_fr_random_dev",
+    "zg_prover_set_quotient_terms", "zg_prover_quotient_terms",
 ]
 
 # zg_params_check: bits of `failed`
@@ -968,6 +969,25 @@ class Prover:
         out = (ctypes.c_uint64 * 4)()
         _check(self.ctx.lib.zg_prover_gate_stats(self.h, out, c_size_t(4)))
         return dict(zip(("gated_proofs", "gates_armed", "remade_plain", "yields"), (int(x) for x in out)))
+
+    def set_quotient_terms(self, enable: bool):
+        """zg_prover_set_quotient_terms: False = every term of the quotient on both parts of the split domain"""
+        _check(self.ctx.lib.zg_prover_set_quotient_terms(self.h, ctypes.c_int(1 if enable else 0)))
+
+    def quotient_terms(self) -> dict:
+        """zg_prover_quotient_terms: the quotient's terms by degree -- active, and 0 / 1 lists: gates (high), sets and
+        lookups (product term high), part2 (per coset slab of a proof: advice, instance, permutation z, lookup z, then
+        a'_l, s'_l interleaved -- transformed onto the split domain's second part)"""
+        count = c_size_t(0)
+        _check(self.ctx.lib.zg_prover_quotient_terms(self.h, None, c_size_t(0), ctypes.byref(count)))
+        out = (ctypes.c_uint32 * count.value)()
+        _check(self.ctx.lib.zg_prover_quotient_terms(self.h, out, c_size_t(count.value), ctypes.byref(count)))
+        v = [int(x) for x in out]
+        res, at = {"active": bool(v[0])}, 5
+        for name, ln in zip(("gates", "sets", "lookups", "part2"), v[1:5]):
+            res[name] = v[at:at + ln]
+            at += ln
+        return res
 
     def vk_commitments(self):
         """keygen_vk's commitments: (fixed uint64[n_fixed, 8], sigma uint64[n_perm_columns, 8]), affine."""

@@ -538,6 +538,19 @@ int zg_prover_phase_ms(const zg_prover *p, double *out, size_t cap);
  * launches nothing ahead): out[0] proofs made in the gated order, out[1] gates armed, out[2] proofs re-made in the plain
  * order because a gate ran into its time limit or was let go, out[3] gates let go early by a blocking call. */
 int zg_prover_gate_stats(const zg_prover *p, uint64_t *out, size_t cap);
+/* The quotient's terms by degree.  On the split extended domain (zg_prover_set_overlap) only the terms of the highest
+ * degrees need the second part's points: a term of degree d <= m1 + 1 contributes a quotient part of degree < m1 n, which
+ * the first part (m1 n points) fixes alone.  The prover therefore evaluates only the high terms on the second part and
+ * transforms only the witness polynomials they read onto it.  Proof bytes of a statement that holds do not depend on it
+ * (for one that does not, see zg_prover_set_overlap: deterministic bytes that verify nowhere, in either setting).
+ * enable = 0: every term on both parts (tests and A/B measurements); 1 (default): by degree, where the key has low terms. */
+int zg_prover_set_quotient_terms(zg_prover *p, int enable);
+/* ... and what the key's classification is: out = { active, G, S, L, C, G words: gate g is high, S words: permutation
+ * set s's product term is high, L words: lookup l's product term is high, C words: coset slab c of a proof (advice,
+ * instance, permutation z, lookup z, then a'_l and s'_l interleaved) is read by a high term and kept on the second part }.
+ * active = 0: no split domain or no low term -- every term is evaluated everywhere.  *count = the words needed; out may be
+ * NULL to ask for it. */
+int zg_prover_quotient_terms(const zg_prover *p, uint32_t *out, size_t cap, size_t *count);
 
 /* Scheduling of one proof on its GPU.  enable = 1 (default): the coefficient / coset transforms run on a
  * second HIP stream beside the commitment MSMs -- lowest latency for a lone proof.  enable = 0: one
