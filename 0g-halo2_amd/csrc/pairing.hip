@@ -295,7 +295,84 @@ bool pairing_product_is_one(const Affine* p, const zg_g2_affine* q, size_t n) {
     return f12_is_one(final_exp(acc));
 }
 
+// t * q on the twist, t a Montgomery scalar: left to right over the bits of the canonical integer, with the affine group
+// law above (an SRS contribution multiplies two G2 points, once).  q must have canonical coordinates and lie on the
+// twist, or be the identity (0,0), which gives the identity; the subgroup is not asked for.  nullptr = done, else why not.
+const char* g2_mul_host(const zg_g2_affine& q, const Fe& t, zg_g2_affine* out) {
+    G2 g;
+    std::memcpy(&g.x, &q.x, sizeof(Fq2));
+    std::memcpy(&g.y, &q.y, sizeof(Fq2));
+    if (!fq_canonical(g.x.c0) || !fq_canonical(g.x.c1) || !fq_canonical(g.y.c0) || !fq_canonical(g.y.c1))
+        return "a coordinate is not below q";
+    g.inf = f2_is_zero(g.x) && f2_is_zero(g.y);
+    if (!g.inf) {
+        const Fq2 xi = {Fq::from_u64(9), Fq::one()};
+        const Fq2 b = f2_mul_fq(f2_inv(xi), Fq::from_u64(3));
+        if (!f2_eq(f2_sqr(g.y), f2_add(f2_mul(f2_sqr(g.x), g.x), b))) return "not on the twist y^2 = x^3 + 3/(9+u)";
+    }
+    const Fe e = Fr::to_raw(t);
+    G2 acc = {f2_zero(), f2_zero(), true};
+    for (int i = 7; i >= 0; i--)
+        for (int bit = 31; bit >= 0; bit--) {
+            acc = g2_dbl(acc);
+            if ((e.l[i] >> bit) & 1) acc = g2_add(acc, g);
+        }
+    if (acc.inf) acc.x = acc.y = f2_zero();
+    std::memcpy(&out->x, &acc.x, sizeof(Fq2));
+    std::memcpy(&out->y, &acc.y, sizeof(Fq2));
+    return nullptr;
+}
+
+// bn256::G2Affine::generator()
+zg_g2_affine g2_generator() {
+    static const uint32_t RAW[4][8] = {
+        {0xd992f6ed, 0x46debd5c, 0xf75edadd, 0x674322d4, 0x5e5c4479, 0x426a0066, 0x121f1e76, 0x1800deef},   // x.c0
+        {0xaef312c2, 0x97e485b7, 0x35a9e712, 0xf1aa4933, 0x31fb5d25, 0x7260bfb7, 0x920d483a, 0x198e9393},   // x.c1
+        {0x66fa7daa, 0x4ce6cc01, 0x0c43d37b, 0xe3d1e769, 0x8dcb408f, 0x4aab7180, 0xdb8c6deb, 0x12c85ea5},   // y.c0
+        {0xd122975b, 0x55acdadc, 0x70b38ef3, 0xbc4b3133, 0x690c3395, 0xec9e99ad, 0x585ff075, 0x090689d0}};  // y.c1
+    Fe m[4];
+    for (int c = 0; c < 4; c++) {
+        Fe r;
+        for (int j = 0; j < 8; j++) r.l[j] = RAW[c][j];
+        m[c] = Fq::from_raw(r);
+    }
+    zg_g2_affine o;
+    std::memcpy(&o.x, &m[0], 2 * sizeof(Fe));
+    std::memcpy(&o.y, &m[2], 2 * sizeof(Fe));
+    return o;
+}
+
 }  // namespace zg
+
+static bool fr_scalar_canonical(const zg_fr* t) {
+    zg::Fe v;
+    std::memcpy(&v, t, sizeof v);
+    for (int i = 7; i >= 0; i--) {
+        if (v.l[i] < zg::FrParams::p(i)) return true;
+        if (v.l[i] > zg::FrParams::p(i)) return false;
+    }
+    return false;
+}
+
+extern "C" int zg_g2_mul(const zg_g2_affine* q, const zg_fr* t, zg_g2_affine* out) {
+    ZG_REQUIRE(q && t && out, ZG_ERR_INVALID_ARG, "zg_g2_mul: null argument");
+    ZG_REQUIRE(fr_scalar_canonical(t), ZG_ERR_INVALID_ARG, "zg_g2_mul: the scalar's limbs are not below r");
+    zg::Fe tv;
+    std::memcpy(&tv, t, sizeof tv);
+    zg_g2_affine r;
+    const char* why = zg::g2_mul_host(*q, tv, &r);
+    ZG_REQUIRE(!why, ZG_ERR_INVALID_ARG, "zg_g2_mul: q: %s", why);
+    *out = r;
+    return ZG_OK;
+}
+
+extern "C" int zg_params_g2(const zg_fr* s, zg_g2_affine* g2, zg_g2_affine* s_g2) {
+    ZG_REQUIRE(s && g2 && s_g2, ZG_ERR_INVALID_ARG, "zg_params_g2: null argument");
+    ZG_REQUIRE(fr_scalar_canonical(s), ZG_ERR_INVALID_ARG, "zg_params_g2: the scalar's limbs are not below r");
+    const zg_g2_affine gen = zg::g2_generator();
+    *g2 = gen;
+    return zg_g2_mul(&gen, s, s_g2);
+}
 
 extern "C" int zg_pairing_check(const zg_g1_affine* p, const zg_g2_affine* q, size_t n, int* result) {
     ZG_REQUIRE(result && ((p && q) || n == 0), ZG_ERR_INVALID_ARG, "zg_pairing_check: null argument");

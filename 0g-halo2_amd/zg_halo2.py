@@ -58,6 +58,8 @@ def load() -> ctypes.CDLL:
     lib.zg_msm_var.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]
     lib.zg_msm_var_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint32, c_void_p]
     lib.zg_msm_var_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]
+    lib.zg_g1_mul_each.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.zg_g1_mul_each_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     _lib = lib
     return lib
 
@@ -91,10 +93,14 @@ ABI_SYMBOLS = [
     "zg_permute_expression_pair", "zg_lookup_product_terms_dev", "zg_prover_permutation_sets",
     "zg_prover_permutation_terms_dev", "zg_fr_lincomb_dev", "zg_fr_random_dev",
     "zg_prover_set_quotient_terms", "zg_prover_quotient_terms",
+    "zg_g1_mul_each", "zg_g1_mul_each_dev", "zg_params_g2", "zg_g2_mul", "zg_params_update", "zg_params_update_dev",
+    "zg_params_check_update",
 ]
 
 # zg_params_check: bits of `failed`
 SRS_G1_MALFORMED, SRS_G1_IDENTITY, SRS_G2, SRS_POWERS, SRS_LAGRANGE = 1, 2, 4, 8, 16
+# zg_params_check_update: two more
+SRS_UPDATE_BASE, SRS_UPDATE_LINK = 32, 64
 
 
 def tuning_names() -> list:
@@ -246,6 +252,22 @@ def pairing_check(p: np.ndarray, q: np.ndarray) -> int:
     return res.value
 
 
+def params_g2(s: np.ndarray):
+    """zg_params_g2: the G2 half of ParamsKZG::new -> (g2, s_g2), uint64[16] each; no device needed."""
+    g2 = np.zeros(16, np.uint64)
+    s_g2 = np.zeros(16, np.uint64)
+    _check(load().zg_params_g2(_ptr(_fr(s)), _ptr(g2), _ptr(s_g2)))
+    return g2, s_g2
+
+
+def g2_mul(q: np.ndarray, t: np.ndarray) -> np.ndarray:
+    """zg_g2_mul: t * q on the twist (uint64[16] G2 affine, (0,0) = identity); no device needed."""
+    q = np.ascontiguousarray(q, dtype=np.uint64).reshape(16)
+    out = np.zeros(16, np.uint64)
+    _check(load().zg_g2_mul(_ptr(q), _ptr(_fr(t)), _ptr(out)))
+    return out
+
+
 def xyzz_sum_ranks(parts: np.ndarray) -> np.ndarray:
     """parts: uint64[world, count, 16] extended-Jacobian partial sums -> uint64[count, 12] normalised sums."""
     parts = np.ascontiguousarray(parts, dtype=np.uint64)
@@ -387,6 +409,64 @@ class Ctx:
         verdict, failed = c_int(-1), c_uint32(0)
         _check(self.lib.zg_params_check(self.h, c_uint32(k), _ptr(g), _ptr(gl) if gl is not None else None, _ptr(g2),
                                         _ptr(s_g2), rng_key(key), ctypes.byref(verdict), ctypes.byref(failed)))
+        return verdict.value, failed.value
+
+    def g1_mul_each(self, points: np.ndarray, scalars: np.ndarray) -> np.ndarray:
+        """zg_g1_mul_each: out[i] = scalars[i] * points[i]; points uint64[n, 8] affine, scalars uint64[n, 4] Montgomery
+        -> uint64[n, 8] affine, (0,0) = identity."""
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        assert points.shape[0] == scalars.shape[0]
+        out = np.zeros_like(points)
+        _check(self.lib.zg_g1_mul_each(self.h, _ptr(points), _ptr(scalars), c_size_t(points.shape[0]), _ptr(out)))
+        return out
+
+    def g1_mul_each_dev(self, d_points: int, d_scalars: int, n: int, d_out: int):
+        """zg_g1_mul_each_dev: device addresses (d_out may be d_points); asynchronous on the context stream."""
+        _check(self.lib.zg_g1_mul_each_dev(self.h, c_void_p(d_points), c_void_p(d_scalars), c_size_t(n), c_void_p(d_out)))
+
+    def params_update(self, k: int, t: np.ndarray, g: np.ndarray, g2: np.ndarray, s_g2: np.ndarray, lagrange: bool = True):
+        """zg_params_update: one contribution t to the SRS (g, g2, s_g2) of 2^k points ->
+        (g_out, g_lagrange_out or None, s_g2_out, record); record = uint64[24]: t * g[0] (8 words), t * g2 (16 words)."""
+        n = 1 << k
+        g = np.ascontiguousarray(np.asarray(g).reshape(-1, 8), dtype=np.uint64)
+        assert g.shape[0] == n, f"{g.shape[0]} points for k = {k}"
+        g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
+        s_g2 = np.ascontiguousarray(s_g2, dtype=np.uint64).reshape(16)
+        g_out = np.zeros((n, 8), np.uint64)
+        gl_out = np.zeros((n, 8), np.uint64) if lagrange else None
+        s_g2_out = np.zeros(16, np.uint64)
+        record = np.zeros(24, np.uint64)
+        _check(self.lib.zg_params_update(self.h, c_uint32(k), _ptr(_fr(t)), _ptr(g), _ptr(g2), _ptr(s_g2), _ptr(g_out),
+                                         _ptr(gl_out) if lagrange else None, _ptr(s_g2_out), _ptr(record)))
+        return g_out, gl_out, s_g2_out, record
+
+    def params_update_dev(self, k: int, t: np.ndarray, d_g: int, d_g_out: int, d_gl_out: int = 0):
+        """zg_params_update_dev: the G1 part on device addresses (d_g_out may be d_g; d_gl_out = 0: no Lagrange basis);
+        asynchronous on the context stream."""
+        _check(self.lib.zg_params_update_dev(self.h, c_uint32(k), _ptr(_fr(t)), c_void_p(d_g), c_void_p(d_g_out),
+                                             c_void_p(d_gl_out) if d_gl_out else None))
+
+    def params_check_update(self, k: int, prev_g01: np.ndarray, g_next: np.ndarray, g_lagrange_next, g2: np.ndarray,
+                            s_g2_next: np.ndarray, record: np.ndarray, key):
+        """zg_params_check_update: is (g_next, g_lagrange_next or None, g2, s_g2_next) the update that `record` describes of
+        the SRS whose first two points are prev_g01 (uint64[2, 8])?  -> (verdict, failed); failed: SRS_* bits."""
+        n = 1 << k
+        prev = np.ascontiguousarray(np.asarray(prev_g01).reshape(-1, 8)[:2], dtype=np.uint64)
+        assert prev.shape[0] == 2
+        g = np.ascontiguousarray(np.asarray(g_next).reshape(-1, 8), dtype=np.uint64)
+        assert g.shape[0] == n, f"{g.shape[0]} points for k = {k}"
+        gl = None
+        if g_lagrange_next is not None:
+            gl = np.ascontiguousarray(np.asarray(g_lagrange_next).reshape(-1, 8), dtype=np.uint64)
+            assert gl.shape[0] == n
+        g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
+        s_g2 = np.ascontiguousarray(s_g2_next, dtype=np.uint64).reshape(16)
+        record = np.ascontiguousarray(record, dtype=np.uint64).reshape(24)
+        verdict, failed = c_int(-1), c_uint32(0)
+        _check(self.lib.zg_params_check_update(self.h, c_uint32(k), _ptr(prev), _ptr(g), _ptr(gl) if gl is not None else None,
+                                               _ptr(g2), _ptr(s_g2), _ptr(record), rng_key(key), ctypes.byref(verdict),
+                                               ctypes.byref(failed)))
         return verdict.value, failed.value
 
     # ---- MSM ----

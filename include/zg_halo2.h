@@ -294,6 +294,67 @@ int zg_params_check(zg_ctx *ctx, uint32_t k, const zg_g1_affine *g,
                     const zg_g2_affine *g2, const zg_g2_affine *s_g2,
                     const uint8_t key[32], int *verdict, uint32_t *failed);
 
+/* out[i] = scalars[i] * points[i], i < n: n independent variable-base multiplications (what an SRS contribution is made
+ * of; upstream would write `points.iter().zip(scalars).map(|(p, s)| p * s)` and normalise).  Scalars are Montgomery
+ * residues, as zg_msm takes them.  Points may be any points of the curve, (0,0), repeats and P beside -P included; they
+ * are not validated (a point off the curve gives garbage in ITS slot).  A zero scalar or an identity point gives (0,0)
+ * and disturbs no neighbour.  The output is affine, canonical Montgomery coordinates, hence bit-exact whatever the
+ * order of the operations.  n = 0 is ZG_OK and launches nothing; a null pointer with n > 0 is ZG_ERR_INVALID_ARG;
+ * n >= 2^28 is ZG_ERR_UNSUPPORTED.  The _dev form takes device pointers (points and out n * 64 B, scalars n * 32 B;
+ * d_out == d_points is allowed) and is asynchronous on the context stream.  One lane per point, signed 2-bit windows,
+ * one shared inversion per wave. */
+int zg_g1_mul_each(zg_ctx *ctx, const zg_g1_affine *points, const zg_fr *scalars, size_t n, zg_g1_affine *out);
+int zg_g1_mul_each_dev(zg_ctx *ctx, const void *d_points, const void *d_scalars, size_t n, void *d_out);
+
+/* The G2 half of ParamsKZG::new (ParamsKZG::setup: g2 = G2Affine::generator(), s_g2 = g2 * s), on the host: with
+ * zg_params_new it makes a complete ParamsKZG, which zg_verifier_create and an SRS file need.  s: Montgomery, limbs
+ * below r (else ZG_ERR_INVALID_ARG); s = 0 gives s_g2 = (0,0). */
+int zg_params_g2(const zg_fr *s, zg_g2_affine *g2, zg_g2_affine *s_g2);
+/* out = t * q on the twist, on the host; the identity is (0,0), as input and as output (t = 0, or t = the order of q).
+ * A q with a coordinate not below q or off y^2 = x^3 + 3/(9+u), and a t whose limbs are not below r, are
+ * ZG_ERR_INVALID_ARG and leave out as it was.  The subgroup is not asked for (zg_params_check does that). */
+int zg_g2_mul(const zg_g2_affine *q, const zg_fr *t, zg_g2_affine *out);
+
+/* One contribution to an updatable SRS: the string of s becomes the string of s*t,
+ *     g_out[i] = t^i * g[i] (i < 2^k),   s_g2_out = t * s_g2,   g_lagrange_out = g_to_lagrange(g_out),   g2 unchanged,
+ * and *record = (t * g[0], t * g2) is the public half of the step, which zg_params_check_update reads.  Parties that
+ * each apply a t of their own, one after the other, end with an SRS whose scalar nobody knows if ONE of them forgot
+ * theirs.  The powers t^i are made on the device and multiplied through the kernel of zg_g1_mul_each; g_lagrange_out
+ * (may be NULL: not computed) comes from the path of zg_params_lagrange_dev and never visits the host; the two G2
+ * products run on the host.  t = 0 or limbs not below r is ZG_ERR_INVALID_ARG, k > 24 ZG_ERR_UNSUPPORTED, a g2 or s_g2
+ * that zg_g2_mul refuses ZG_ERR_INVALID_ARG: all are decided before anything is written.  g_out may be g.  The _dev
+ * form takes device pointers (d_g_out may equal d_g; d_g_lagrange_out may be NULL, and may be neither of the other
+ * two), does the G1 part only and is asynchronous on the context stream.
+ * The workspace that held the powers of t is zeroed before it returns to the context's pool.  That is best effort:
+ * t itself travels in kernel arguments, and registers and LDS are not cleared; a caller who must forget t forgets its
+ * own copy and destroys the context. */
+typedef struct { zg_g1_affine t_g1; zg_g2_affine t_g2; } zg_srs_contribution;
+int zg_params_update(zg_ctx *ctx, uint32_t k, const zg_fr *t,
+                     const zg_g1_affine *g, const zg_g2_affine *g2, const zg_g2_affine *s_g2,
+                     zg_g1_affine *g_out, zg_g1_affine *g_lagrange_out /* may be NULL */,
+                     zg_g2_affine *s_g2_out, zg_srs_contribution *record);
+int zg_params_update_dev(zg_ctx *ctx, uint32_t k, const zg_fr *t, const void *d_g, void *d_g_out /* may equal d_g */,
+                         void *d_g_lagrange_out /* may be NULL */);
+
+/* Is `next` the update of `prev` that `record` describes?  *verdict / *failed as zg_params_check, with two more bits:
+ *   (a) zg_params_check(k, g_next, g_lagrange_next, g2, s_g2_next, key) accepts -- the same code, the same bits;
+ *   (b) ZG_SRS_UPDATE_BASE  g_next[0] is not prev g[0] (a step multiplies g[0] by t^0);
+ *   (c) ZG_SRS_UPDATE_LINK  record->t_g2 is non-canonical, off the twist, the identity or outside the r-torsion;
+ *                           record->t_g1 is non-canonical, off the curve or the identity; or one of
+ *                           e(t_g1, g2) = e(prev g[0], t_g2) (the record's halves carry ONE t) and
+ *                           e(g_next[1], g2) = e(prev g[1], t_g2) (g_next[1] = t * prev g[1]) fails.
+ * With (a), (c) fixes every g_next[i] and s_g2_next.  prev_g01: the previous string's g[0] and g[1] -- all of it that
+ * the check needs.  k = 0 has no g[1]: ZG_ERR_INVALID_ARG; k > 22 ZG_ERR_UNSUPPORTED, as for zg_params_check.  A
+ * rejected step is not an error of the call.  Both pairings run on the host.
+ * What this is NOT: there is no hash-chained transcript and no random beacon, and the pair (t_g1, t_g2) is a
+ * knowledge-of-exponent style record of one step, not a ceremony protocol -- who contributed, in what order, and that
+ * nobody adapted a t to a later party's are a ceremony's to establish. */
+enum { ZG_SRS_UPDATE_BASE = 32, ZG_SRS_UPDATE_LINK = 64 };
+int zg_params_check_update(zg_ctx *ctx, uint32_t k, const zg_g1_affine prev_g01[2] /* prev g[0], g[1] */,
+                           const zg_g1_affine *g_next, const zg_g1_affine *g_lagrange_next /* may be NULL */,
+                           const zg_g2_affine *g2, const zg_g2_affine *s_g2_next,
+                           const zg_srs_contribution *record, const uint8_t key[32], int *verdict, uint32_t *failed);
+
 /* ------------------------------------------------------------------ NTT
  * Replaces halo2_proofs::arithmetic::best_fft and the EvaluationDomain wrappers
  * (halo2_proofs/src/poly/domain.rs upstream: lagrange_to_coeff, coeff_to_extended,
