@@ -48,6 +48,7 @@ struct Cols {
 // Per-proof scalars of a lock-step batch: one entry per proof in HBM, rewritten by the host at every transcript step
 // (kernels read their proof's entry through the scalar cache: the proof index is workgroup-uniform).
 constexpr uint32_t PC_MAX_POINTS = 16;
+constexpr uint32_t PC_U_SLOT = PC_MAX_POINTS;  // ProofConst::points: the slot of SHPLONK's u, behind the rotations'
 constexpr uint32_t EH_MAX_YPOW = 48;  // evaluate_h's grouped form: powers of y, one per term after the gates (+ 1)
 // evaluate_h's scaled permutation term (EvalHArgs::sigma_sc): the most permutation columns / sets it holds constants for
 constexpr uint32_t EH_MAX_PCOLS = 16, EH_MAX_PSETS = 8;
@@ -65,7 +66,7 @@ struct alignas(16) ProofConst {
     uint32_t eh_scaled, eh_pad[7];
     Fe xn;                      // x^n (vanishing::evaluate's Horner variable)
     Fe v;                       // GWC's v
-    Fe points[PC_MAX_POINTS];   // opening points x * omega^rotation, by slot
+    Fe points[PC_MAX_POINTS + 1];  // opening points x * omega^rotation, by slot; the last one: SHPLONK's u (PC_U_SLOT)
     Fe subs[PC_MAX_POINTS];     // eval_batch of GWC point set s
     Fe fold_w;                  // a proof of several circuits: the weight of this slot's quotient in the proof's (poly_fold_slots)
 };
@@ -236,10 +237,22 @@ int poly_fold_slots(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, Fe* h, size_
 // length), minus pc[0].subs[s] at X^0; out + s * out_stride
 int poly_combine_pairs(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, const uint32_t* d_lists, const uint32_t* firsts,
                        const uint32_t* counts, uint32_t nsets, Fe* out, size_t out_stride, uint32_t n);
+// SHPLONK: output o of proof b = sum_t d_coef[b * coef_bs + firsts[o] + t] * poly(d_lists[firsts[o] + t])
+// (entry = slot << 16 | polynomial index, the slot counted from b), plus, with `extra`, d_coef[.. + counts[o]] * extra[b * extra_bs ..],
+// minus d_corr[b * corr_bs + o * ncorr + i] at i < ncorr; to out + b * out_bs + o * out_stride.  d_coef: device memory, the
+// coefficients times 2^5 and unpacked (f9_unpack(Fr::mul(c, Fr9Params::c261_fe()))).
+struct F9;
+int poly_combine_weighted(zg_ctx* ctx, const PolySet& polys, uint32_t nb, const uint32_t* d_lists, const uint32_t* firsts,
+                          const uint32_t* counts, uint32_t nouts, const F9* d_coef, size_t coef_bs, const Fe* d_corr, uint32_t ncorr,
+                          size_t corr_bs, const Fe* extra, size_t extra_bs, Fe* out, size_t out_stride, size_t out_bs, uint32_t n);
+// out[b * out_bs + i] = sum_(s < rows) in[b * in_bs + s * in_stride + i]
+int poly_sum_rows(zg_ctx* ctx, uint32_t nb, const Fe* in, size_t in_stride, size_t in_bs, uint32_t rows, Fe* out, size_t out_bs,
+                  uint32_t n);
 // out[i] = sum_j coeffs[j] * polys[j][i], i < n, minus *sub0 (may be null) at i = 0; polys and coeffs are HOST arrays of
 // `count` entries (device pointers / library-form scalars) that travel in the kernel arguments, 64 terms per launch
 int poly_lincomb(zg_ctx* ctx, const Fe* const* polys, const Fe* coeffs, size_t count, uint32_t n, const Fe* sub0, Fe* out);
 // kate_division of `nsets` polynomials per proof: a + b * a_bs + s * a_stride divided by (X - pc[b].points[slot[s]])
+// (slot: a rotation's point slot, or PC_U_SLOT for SHPLONK's u)
 size_t poly_kate_tmp_elems(uint32_t n, uint32_t batch);
 int poly_kate_division(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const uint32_t* slots, uint32_t nsets, const Fe* a,
                        size_t a_stride, size_t a_bs, Fe* q, size_t q_stride, size_t q_bs, Fe* tmp, uint32_t n);

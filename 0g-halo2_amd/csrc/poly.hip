@@ -1595,6 +1595,100 @@ int poly_combine_pairs(zg_ctx* ctx, const PolySet& polys, const ProofConst* pc, 
     return ZG_OK;
 }
 
+// SHPLONK's two weighted combinations: output o = blockIdx.y of proof b = blockIdx.z is
+//   sum_t coef[b][first[o] + t] * poly(lists[first[o] + t])  [+ coef[b][first[o] + count[o]] * extra[b]]  -  corr[b][o]
+// over list entries of combine_pairs_kernel's form (slot << 16 | polynomial index; the slot counts from b, so a batch of
+// single proofs lists slot 0 and a proof of several circuits is launched as b = 0 alone).  The coefficients differ per
+// proof and per term -- y^j v^i c_(i,r) for the numerators, y^j v^i z_i / z_0 for L -- so they live in device memory beside
+// ProofConst[b], already times 2^5 and unpacked by the host; every lane of a workgroup reads the same one.  The lazy sum
+// of the siblings: 81 multiply-adds a term, one reduction per chunk of HC9_MAX terms.  corr: the interpolants' share,
+// ncorr <= PC_MAX_POINTS low coefficients per output (one, the constant, for L).
+struct WeightedOuts {
+    uint32_t first[HC_MAX_SETS], count[HC_MAX_SETS];
+};
+__global__ __launch_bounds__(256) void combine_weighted_kernel(PolySet ps, const uint32_t* __restrict__ lists,
+                                                               const F9* __restrict__ coef, size_t coef_bs, WeightedOuts outs,
+                                                               const Fe* __restrict__ corr, uint32_t ncorr, size_t corr_bs,
+                                                               const Fe* __restrict__ extra, size_t extra_bs, Fe* __restrict__ out,
+                                                               size_t out_stride, size_t out_bs, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, o = blockIdx.y, b = blockIdx.z;
+    if (i >= n) return;
+    const uint32_t* list = lists + outs.first[o];
+    const F9* cf = coef + (size_t)b * coef_bs + outs.first[o];
+    const uint32_t count = outs.count[o];
+    auto at = [&](uint32_t j) {
+        const uint32_t e = list[j];
+        return poly_of(ps, e & 0xffffu, (e >> 16) + b) + i;
+    };
+    Fe r = fe_zero();
+    for (uint32_t j0 = 0; j0 < count; j0 += HC9_MAX) {
+        const uint32_t chunk = count - j0 < HC9_MAX ? count - j0 : HC9_MAX;
+        Dot9<Fr9Params> acc;
+        acc.zero();
+        uint32_t t = 0;
+        for (; t + 3 <= chunk; t += 3) {
+            const Fe p0 = ldg(at(j0 + t)), p1 = ldg(at(j0 + t + 1)), p2 = ldg(at(j0 + t + 2));
+            acc.mac(f9_unpack(p0), cf[j0 + t]);
+            acc.mac(f9_unpack(p1), cf[j0 + t + 1]);
+            acc.mac(f9_unpack(p2), cf[j0 + t + 2]);
+            acc.carry();
+        }
+        for (; t < chunk; t++) {
+            acc.mac(f9_unpack(ldg(at(j0 + t))), cf[j0 + t]);
+            acc.carry();
+        }
+        r = Fr::add(r, f9_reduce_pack<Fr9Params>(acc.reduce()));
+    }
+    if (extra) {
+        Dot9<Fr9Params> acc;
+        acc.zero();
+        acc.mac(f9_unpack(ldg(extra + (size_t)b * extra_bs + i)), cf[count]);
+        acc.carry();
+        r = Fr::add(r, f9_reduce_pack<Fr9Params>(acc.reduce()));
+    }
+    if (i < ncorr) r = Fr::sub(r, ldg(corr + (size_t)b * corr_bs + (size_t)o * ncorr + i));
+    stg(out + (size_t)b * out_bs + (size_t)o * out_stride + i, r);
+}
+
+int poly_combine_weighted(zg_ctx* ctx, const PolySet& polys, uint32_t nb, const uint32_t* d_lists, const uint32_t* firsts,
+                          const uint32_t* counts, uint32_t nouts, const F9* d_coef, size_t coef_bs, const Fe* d_corr, uint32_t ncorr,
+                          size_t corr_bs, const Fe* extra, size_t extra_bs, Fe* out, size_t out_stride, size_t out_bs, uint32_t n) {
+    if (!nouts || !nb || !n) return ZG_OK;
+    ZG_REQUIRE(nouts <= HC_MAX_SETS && ncorr <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "poly_combine_weighted: %u outputs", nouts);
+    WeightedOuts outs;
+    memset(&outs, 0, sizeof(outs));
+    double total = 0;
+    for (uint32_t o = 0; o < nouts; o++) {
+        outs.first[o] = firsts[o];
+        outs.count[o] = counts[o];
+        total += counts[o] + (extra ? 2 : 1);
+    }
+    ZG_LAUNCH(ctx, "combine_weighted", (double)nb * total * n * 32, combine_weighted_kernel, dim3((n + 255) / 256, nouts, nb), dim3(256),
+              0, polys, d_lists, d_coef, coef_bs, outs, d_corr, ncorr, corr_bs, extra, extra_bs, out, out_stride, out_bs, n);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+// SHPLONK's h1: out[b][i] = sum_(s < rows) in[b][s][i] -- the per-point quotients, canonical values, into one polynomial
+__global__ __launch_bounds__(256) void sum_rows_kernel(const Fe* __restrict__ in, size_t in_stride, size_t in_bs, uint32_t rows,
+                                                       Fe* __restrict__ out, size_t out_bs, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= n) return;
+    const Fe* p = in + (size_t)b * in_bs + i;
+    Fe r = ldg(p);
+    for (uint32_t s = 1; s < rows; s++) r = Fr::add(r, ldg(p + (size_t)s * in_stride));
+    stg(out + (size_t)b * out_bs + i, r);
+}
+
+int poly_sum_rows(zg_ctx* ctx, uint32_t nb, const Fe* in, size_t in_stride, size_t in_bs, uint32_t rows, Fe* out, size_t out_bs,
+                  uint32_t n) {
+    if (!nb || !rows || !n) return ZG_OK;
+    ZG_LAUNCH(ctx, "sum_rows", (double)nb * (rows + 1) * n * 32, sum_rows_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, in, in_stride,
+              in_bs, rows, out, out_bs, n);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
 // zg_fr_lincomb_dev: out[i] = sum_j coeff_j * poly_j[i] for polynomials that live anywhere in HBM (the caller-run
 // create_proof's sum x^(n i) h_i and sum v^i p_i - eval).  The lazy sum of combine_pairs_kernel -- 81 multiply-adds per
 // term, one Montgomery reduction per chunk -- with the chunk's addresses and coefficients in the KERNEL ARGUMENTS: every
@@ -1799,7 +1893,7 @@ int poly_kate_division(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const uin
     KdSlots ks;
     memset(&ks, 0, sizeof(ks));
     for (uint32_t s = 0; s < nsets; s++) {
-        ZG_REQUIRE(slots[s] < PC_MAX_POINTS, ZG_ERR_INVALID_ARG, "kate division: point slot %u", slots[s]);
+        ZG_REQUIRE(slots[s] <= PC_U_SLOT, ZG_ERR_INVALID_ARG, "kate division: point slot %u", slots[s]);
         ks.slot[s] = slots[s];
     }
     if (ctx->msm_pair && n <= (1u << 18)) {  // latency form (tmp per poly_kate_tmp_elems(n, nb * nsets))

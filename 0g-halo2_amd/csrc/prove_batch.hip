@@ -13,6 +13,7 @@
 // stream while the main stream works through the commitment MSM and the host hashes.
 #include <algorithm>
 #include <chrono>
+#include <map>
 
 #include "prover.h"
 #include "field9.h"
@@ -260,6 +261,19 @@ struct ProveBatch {
     struct EvRef { uint32_t circuit; size_t ev; };          // an evaluation of the proof: evq index `ev` of a circuit (multi)
     std::vector<std::vector<EvRef>> set_evs;
     uint32_t n_per = 0;  // multi: evaluations per circuit; the shared ones follow them in slot 0's row
+    // ---- SHPLONK (zg_prover_set_multiopen): construct_intermediate_sets' result for the circuit --
+    // commitments in first-appearance order, grouped by the set of points they are opened at -- and per proof what the
+    // second half needs of the first
+    const bool shplonk;
+    struct OQ { uint32_t poly, slot; size_t ev; uint32_t circuit; };  // an opening query: polynomial, point slot, its evaluation
+    struct SCom { uint32_t entry; std::vector<EvRef> evs; };           // a commitment (slot << 16 | polynomial); evs[i]: at set point i
+    struct SSet { uint32_t mask; std::vector<uint32_t> slots; std::vector<SCom> coms; };
+    std::vector<SSet> ssets;
+    std::vector<uint32_t> tslots;                 // T: every point slot a query names
+    std::vector<uint32_t> sh_first, sh_count;     // the numerators' lists, one per point of T; then L's (index tslots.size())
+    size_t sh_nlist = 0, sh_ncoef = 0;            // entries of all lists; coefficients per proof (both halves use [0, ..))
+    struct SProof { Fe y, v; std::vector<std::vector<Fe>> R; };  // R[i]: sum_j y^j R_ij(X), coefficients
+    std::vector<SProof> sproof;
     // ---- the gate (run())
     enum Wait { W_ADVICE, W_PERMUTED, W_PRODUCTS, W_QUOTIENT, W_EVALS, W_GWC };
     bool gated = false, armed = false;
@@ -279,7 +293,7 @@ struct ProveBatch {
         : p(p_), advice_host(advice_host_), advice_dev(advice_dev_), instance(instance_), instance_len(instance_len_), keys(keys_),
           proofs(proofs_), proof_cap(proof_cap_), proof_lens(proof_lens_), statuses(statuses_), pk(*p_->pk), ctx(p_->ctx),
           st(p_->ctx->stream), nb((uint32_t)count), multi(multi_), ntr(multi_ ? 1u : (uint32_t)count), nq(ntr), tr(ntr),
-          status(count, ZG_OK) {
+          status(count, ZG_OK), shplonk(p_->multiopen == ZG_MULTIOPEN_SHPLONK) {
         n = pk.n; k = pk.k; ek = pk.ext_k; bf = pk.bf; usable = pk.usable;
         A = pk.A; I = pk.I; P = pk.P; NL = pk.NL; S = pk.sets; Q = pk.qpd;
         hat = pk.hat;
@@ -445,6 +459,7 @@ struct ProveBatch {
     }
     bool gate_wanted() {
         const int v = knob(K_LAT_GATE);
+        if (shplonk) return false;  // (its second half starts from h1 on the host: the plain order)
         if (no_gate || (v < 0 ? LAT_GATE_DEFAULT : v) == 0 || !p->use_side || nb != 1 || p->world > 1 || p->rccl_comm) return false;
         if (p->warm_sig != form_sig()) return false;  // (first-use allocations and their synchronisations are behind us)
         // (a runtime that completes every launch before it submits the next one would never reach publish())
@@ -916,12 +931,12 @@ struct ProveBatch {
         ZG_TICK("evals: queued");
         return ZG_OK;
     }
+    // evaluation `e` (evq index) of circuit c of a multi proof: a shared one lives in slot 0's row
+    const Fe& ev_of(uint32_t c, size_t e) const { return ev_all[(size_t)(evq[e].shared ? 0 : c) * p->max_evals + evq[e].at]; }
     // (the evaluations into the transcripts, then v and each point set's v-weighted evaluation: needs openings_lists())
     int evaluations_absorb() {
         ZG_HIP(hipEventSynchronize(p->evs[W_EVALS]));
         ZG_TICK("evals on the host");
-        // evaluation `e` (evq index) of circuit c of a multi proof: a shared one lives in slot 0's row
-        auto ev_of = [&](uint32_t c, size_t e) -> const Fe& { return ev_all[(size_t)(evq[e].shared ? 0 : c) * p->max_evals + evq[e].at]; };
         if (multi) {
             // every circuit's advice evaluations | fixed, random, sigma once | every circuit's permutation evaluations |
             // every circuit's lookup evaluations
@@ -933,6 +948,7 @@ struct ProveBatch {
                 for (size_t i = e_pz; i < e_lk; i++) t.write_scalar(ev_of(c, i));
             for (uint32_t c = 0; c < nb; c++)
                 for (size_t i = e_lk; i < e_written; i++) t.write_scalar(ev_of(c, i));
+            if (shplonk) return shplonk_numerator_tables();
             const Fe v = t.squeeze();
             for (uint32_t b = 0; b < nb; b++) p->hpc[b].v = v;
             for (uint32_t s = 0; s < nsets; s++) {  // eval_batch of a set: Horner in v over all circuits' evaluations, list order
@@ -944,6 +960,7 @@ struct ProveBatch {
         for (uint32_t b = 0; b < nb && !multi; b++) {
             const Fe* ev = ev_all + (size_t)b * p->max_evals;
             for (size_t i = 0; i < e_written; i++) tr[b].write_scalar(ev[i]);
+            if (shplonk) continue;
             ProofConst& c = p->hpc[b];
             c.v = tr[b].squeeze();
             for (uint32_t s = 0; s < nsets; s++) {
@@ -952,6 +969,7 @@ struct ProveBatch {
                 c.subs[s] = eval_batch;
             }
         }
+        if (shplonk) return shplonk_numerator_tables();
         ZG_TICK("v");
         ZG_TRY(publish());
         ZG_TICK("v uploaded");
@@ -962,7 +980,6 @@ struct ProveBatch {
     int openings_lists() {
         // ---- opening queries in create_proof's order: (poly, point slot, index of the evaluation)
         // (multi: circuit after circuit its advice, permutation and lookup queries, then once what all circuits share)
-        struct OQ { uint32_t poly, slot; size_t ev; uint32_t circuit; };
         std::vector<OQ> oq;
         for (uint32_t circ = 0; circ < (multi ? nb : 1u); circ++) {
             for (size_t i = 0; i < e_fixed; i++) oq.push_back({evq[i].poly, evq[i].slot, i, circ});
@@ -997,6 +1014,7 @@ struct ProveBatch {
         oq.push_back({p->ix_hpoly, 0, e_h, 0});
         oq.push_back({p->ix_random, 0, e_random, 0});
 
+        if (shplonk) return shplonk_sets(oq);
         // ---- ProverGWC::create_proof: the point sets (circuit only), then per proof its v-weighted evaluation batches
         nsets = 0;
         lists.clear(); counts.clear(); set_slot.clear(); set_evs.clear(); firsts.clear();
@@ -1046,6 +1064,7 @@ struct ProveBatch {
         return ZG_OK;
     }
     int openings_queue() {
+        if (shplonk) return shplonk_h1_queue();
         // poly_batch of every point set in one launch: set s -> wpoly[2s]
         // (their own region of d_idx, behind the evaluation lists: nothing else writes there between proofs)
         uint32_t* d_lists = multi ? p->d_mlists : d_hlist + 64;
@@ -1066,6 +1085,7 @@ struct ProveBatch {
         return ZG_OK;
     }
     int openings_absorb() {
+        if (shplonk) return shplonk_finish();
         ZG_TRY(wait_points(p, (size_t)nq * nsets, pts, W_GWC));
         ZG_TICK("gwc: points on the host");
         for (uint32_t b = 0; b < nq; b++)
@@ -1073,6 +1093,252 @@ struct ProveBatch {
         return ZG_OK;
     }
 
+
+    // ---- SHPLONK (ProverSHPLONK::create_proof, v2023_04_20 src/poly/kzg/multiopen/shplonk/prover.rs)
+    // construct_intermediate_sets: commitments by first appearance, rotation sets by equal point sets, in the order of
+    // their first commitment (circuit only).  The lists of both combinations follow from it: per point r of T the
+    // commitments of every set that holds r, and for L every commitment once.
+    int shplonk_sets(const std::vector<OQ>& oq) {
+        ZG_REQUIRE(p->sh_h1 != nullptr, ZG_ERR_INVALID_ARG, "zg_prover_prove: no SHPLONK buffers (zg_prover_set_multiopen)");
+        ZG_REQUIRE(p->nsh + p->npp <= 0x10000u, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u polynomials", p->nsh + p->npp);
+        struct Com { uint32_t entry, mask; std::vector<std::pair<uint32_t, EvRef>> at; };
+        std::vector<Com> coms;
+        std::map<uint32_t, size_t> com_of;
+        uint32_t tmask = 0;
+        for (const OQ& q : oq) {
+            const uint32_t entry = (multi ? q.circuit << 16 : 0u) | q.poly;
+            auto it = com_of.find(entry);
+            if (it == com_of.end()) {
+                it = com_of.emplace(entry, coms.size()).first;
+                coms.push_back({entry, 0u, {}});
+            }
+            Com& c = coms[it->second];
+            if (c.mask >> q.slot & 1u) continue;  // (a point set: the same query twice counts once)
+            c.mask |= 1u << q.slot;
+            c.at.push_back({q.slot, {q.circuit, q.ev}});
+            tmask |= 1u << q.slot;
+        }
+        ssets.clear(); tslots.clear();
+        for (uint32_t sl = 0; sl < PC_MAX_POINTS; sl++)
+            if (tmask >> sl & 1u) tslots.push_back(sl);
+        for (const Com& c : coms) {
+            size_t i = 0;
+            while (i < ssets.size() && ssets[i].mask != c.mask) i++;
+            if (i == ssets.size()) {
+                ssets.push_back({c.mask, {}, {}});
+                for (uint32_t sl = 0; sl < PC_MAX_POINTS; sl++)
+                    if (c.mask >> sl & 1u) ssets[i].slots.push_back(sl);
+            }
+            SCom sc{c.entry, {}};
+            for (uint32_t sl : ssets[i].slots)
+                for (const auto& a : c.at)
+                    if (a.first == sl) sc.evs.push_back(a.second);
+            ssets[i].coms.push_back(std::move(sc));
+        }
+        ZG_REQUIRE(ssets.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu rotation sets (max %u)", ssets.size(), HC_MAX_SETS);
+        ZG_REQUIRE(tslots.size() <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu opening points", tslots.size());
+        lists.clear(); sh_first.clear(); sh_count.clear();
+        for (uint32_t r : tslots) {
+            sh_first.push_back((uint32_t)lists.size());
+            for (const SSet& s : ssets)
+                if (s.mask >> r & 1u)
+                    for (const SCom& c : s.coms) lists.push_back(c.entry);
+            sh_count.push_back((uint32_t)lists.size() - sh_first.back());
+        }
+        sh_ncoef = lists.size() > coms.size() + 1 ? lists.size() : coms.size() + 1;
+        sh_first.push_back((uint32_t)lists.size());
+        for (const SSet& s : ssets)
+            for (const SCom& c : s.coms) lists.push_back(c.entry);
+        sh_count.push_back((uint32_t)coms.size());
+        lists.push_back(0);  // (the place of h1's coefficient: it is no polynomial of the set)
+        sh_nlist = lists.size();
+        ZG_REQUIRE(sh_nlist <= 2 * p->sh_terms + 16 && (size_t)(multi ? 1 : nb) * sh_ncoef <= p->sh_terms + p->cap, ZG_ERR_UNSUPPORTED,
+                   "zg_prover_prove: %zu opening queries (room for %zu)", oq.size(), p->sh_terms);
+        ZG_TICK("rotation sets listed");
+        return ZG_OK;
+    }
+    const Fe& sh_ev(uint32_t b, const EvRef& r) const { return multi ? ev_of(r.circuit, r.ev) : ev_all[(size_t)b * p->max_evals + evq[r.ev].at]; }
+    // x[i] <- 1 / x[i] with ONE field inversion (Montgomery's trick; no entry is zero: differences of distinct points)
+    static void invert_all(std::vector<Fe>& x) {
+        std::vector<Fe> pre(x.size());
+        Fe acc = Fr::one();
+        for (size_t i = 0; i < x.size(); i++) {
+            pre[i] = acc;
+            acc = Fr::mul(acc, x[i]);
+        }
+        Fe inv = Fr::inv(acc);
+        for (size_t i = x.size(); i-- > 0;) {
+            const Fe xi = x[i];
+            x[i] = Fr::mul(inv, pre[i]);
+            inv = Fr::mul(inv, xi);
+        }
+    }
+    static F9 coef9(const Fe& c) { return f9_unpack(Fr::mul(c, Fr9Params::c261_fe())); }
+    // the two tables of a half, every proof's, to the device (behind the work already queued)
+    int shplonk_upload(const std::vector<F9>& coef, const std::vector<Fe>& corr) {
+        std::vector<F9> padded(coef);
+        while (padded.size() * sizeof(F9) % 16) padded.push_back(F9{});  // (whole 16-byte words: h2d's kernel form)
+        ZG_TRY(h2d(p, p->sh_coef, padded.data(), padded.size() * sizeof(F9)));
+        return h2d(p, p->sh_corr, corr.data(), corr.size() * sizeof(Fe));
+    }
+    // y, v, then per proof the numerators' coefficients: y^j v^i c_(i,r) on commitment j of set i in the list of point r,
+    // c_(i,r) = 1 / prod_(p in S_i, p != r) (r - p), and the low coefficients of sum_(i: r in S_i) v^i c_(i,r) R_i(X),
+    // R_i = sum_j y^j R_ij the interpolant of the y-combined evaluations on S_i (the host holds them: eval_batch's place)
+    int shplonk_numerator_tables() {
+        const uint32_t np = multi ? 1u : nb, nT = (uint32_t)tslots.size();
+        sproof.assign(np, SProof{});
+        std::vector<F9> coef((size_t)np * sh_ncoef, F9{});
+        std::vector<Fe> corr((size_t)np * nT * PC_MAX_POINTS, fe_zero());
+        for (uint32_t b = 0; b < np; b++) {
+            SProof& sp = sproof[b];
+            sp.y = tr[b].squeeze();
+            sp.v = tr[b].squeeze();
+            const Fe* pt = p->hpc[b].points;
+            sp.R.resize(ssets.size());
+            std::vector<std::vector<Fe>> cinv(ssets.size());
+            {  // every c_(i,a) of the proof under one inversion
+                std::vector<Fe> den;
+                for (const SSet& s : ssets)
+                    for (size_t a = 0; a < s.slots.size(); a++) {
+                        Fe d = Fr::one();
+                        for (size_t c = 0; c < s.slots.size(); c++)
+                            if (c != a) d = Fr::mul(d, Fr::sub(pt[s.slots[a]], pt[s.slots[c]]));
+                        den.push_back(d);
+                    }
+                invert_all(den);
+                size_t at = 0;
+                for (size_t i = 0; i < ssets.size(); i++) {
+                    cinv[i].assign(den.begin() + at, den.begin() + at + ssets[i].slots.size());
+                    at += ssets[i].slots.size();
+                }
+            }
+            Fe vi = Fr::one();
+            for (size_t i = 0; i < ssets.size(); i++, vi = Fr::mul(vi, sp.v)) {
+                const SSet& s = ssets[i];
+                const size_t m = s.slots.size();
+                sp.R[i].assign(m, fe_zero());
+                for (size_t a = 0; a < m; a++) {
+                    Fe e = fe_zero(), yj = Fr::one();  // the y-combined evaluation at this point
+                    for (const SCom& c : s.coms) {
+                        e = Fr::add(e, Fr::mul(yj, sh_ev(b, c.evs[a])));
+                        yj = Fr::mul(yj, sp.y);
+                    }
+                    // e c_(i,a) prod_(c != a) (X - p_c) into R_i
+                    std::vector<Fe> num(1, Fr::mul(e, cinv[i][a]));
+                    for (size_t c = 0; c < m; c++) {
+                        if (c == a) continue;
+                        num.push_back(fe_zero());
+                        for (size_t d2 = num.size() - 1; d2 > 0; d2--) num[d2] = Fr::sub(num[d2 - 1], Fr::mul(num[d2], pt[s.slots[c]]));
+                        num[0] = Fr::neg(Fr::mul(num[0], pt[s.slots[c]]));
+                    }
+                    for (size_t d2 = 0; d2 < m; d2++) sp.R[i][d2] = Fr::add(sp.R[i][d2], num[d2]);
+                }
+            }
+            for (uint32_t o = 0; o < nT; o++) {
+                F9* cf = &coef[(size_t)b * sh_ncoef + sh_first[o]];
+                Fe* cr = &corr[((size_t)b * nT + o) * PC_MAX_POINTS];
+                size_t at = 0;
+                vi = Fr::one();
+                for (size_t i = 0; i < ssets.size(); i++, vi = Fr::mul(vi, sp.v)) {
+                    const SSet& s = ssets[i];
+                    if (!(s.mask >> tslots[o] & 1u)) continue;
+                    size_t a = 0;
+                    while (s.slots[a] != tslots[o]) a++;
+                    const Fe w = Fr::mul(vi, cinv[i][a]);
+                    Fe wy = w;
+                    for (size_t j = 0; j < s.coms.size(); j++, wy = Fr::mul(wy, sp.y)) cf[at++] = coef9(wy);
+                    for (size_t d2 = 0; d2 < sp.R[i].size(); d2++) cr[d2] = Fr::add(cr[d2], Fr::mul(w, sp.R[i][d2]));
+                }
+            }
+        }
+        ZG_TICK("y, v (multi-open)");
+        ZG_TRY(shplonk_upload(coef, corr));
+        lap(4);
+        return ZG_OK;
+    }
+    // h1 = sum_i v^i N_i / Z_(S_i) as |T| first-order divisions: per point r the combination sum_(i: r in S_i) v^i c_(i,r) N_i
+    // (one launch for all of them), the batched Kate division by (X - r), and the sum of the quotients
+    int shplonk_h1_queue() {
+        const uint32_t np = multi ? 1u : nb, nT = (uint32_t)tslots.size();
+        ZG_TRY(h2d_list(p, p->sh_lists, lists));
+        ZG_TRY(poly_combine_weighted(ctx, polys, np, p->sh_lists, sh_first.data(), sh_count.data(), nT, p->sh_coef, sh_ncoef, p->sh_corr,
+                                     PC_MAX_POINTS, (size_t)nT * PC_MAX_POINTS, nullptr, 0, p->wpoly, (size_t)2 * n, wp_bs, n));
+        ZG_TRY(poly_kate_division(ctx, p->d_pc, np, tslots.data(), nT, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n, wp_bs,
+                                  p->ktmp, n));
+        ZG_TRY(poly_sum_rows(ctx, np, p->wpoly + n, (size_t)2 * n, wp_bs, nT, p->sh_h1, n, n));
+        ctx->msm_dense_hint = true;
+        const int st_c = commit(p, phase_msm(dense_g(p), p->sh_h1, n, 1, n, np), W_GWC);
+        ctx->msm_dense_hint = false;
+        ZG_TRY(st_c);
+        ZG_TICK("h1: queued");
+        return ZG_OK;
+    }
+    // h1 -> u; L = sum_i v^i z_i sum_j y^j (P_ij - R_ij(u)) - Z_T(u) h1 with every coefficient already over z_0; h2 = L / (X - u)
+    int shplonk_finish() {
+        const uint32_t np = multi ? 1u : nb, nT = (uint32_t)tslots.size(), oL = nT;
+        ZG_TRY(wait_points(p, np, pts, W_GWC));
+        ZG_TICK("h1 on the host");
+        std::vector<F9> coef((size_t)np * sh_ncoef, F9{});
+        std::vector<Fe> corr(np, fe_zero());
+        Fe u{};
+        for (uint32_t b = 0; b < nb; b++) {
+            if (b < np) {
+                tr[b].write_point(pts[b]);
+                u = tr[b].squeeze();
+            }
+            p->hpc[b].points[PC_U_SLOT] = u;
+        }
+        std::vector<Fe> z0inv_all(np);  // every proof's 1 / z_0 under one inversion
+        for (uint32_t b = 0; b < np; b++) {
+            const Fe* pt = p->hpc[b].points;
+            Fe z0 = Fr::one();
+            for (uint32_t r : tslots)
+                if (!(ssets[0].mask >> r & 1u)) z0 = Fr::mul(z0, Fr::sub(pt[PC_U_SLOT], pt[r]));
+            z0inv_all[b] = z0;
+        }
+        invert_all(z0inv_all);
+        for (uint32_t b = 0; b < np; b++) {
+            const SProof& sp = sproof[b];
+            const Fe* pt = p->hpc[b].points;
+            const Fe ub = pt[PC_U_SLOT];
+            Fe zT = Fr::one();
+            for (uint32_t r : tslots) zT = Fr::mul(zT, Fr::sub(ub, pt[r]));
+            std::vector<Fe> z(ssets.size(), Fr::one());
+            for (size_t i = 0; i < ssets.size(); i++)
+                for (uint32_t r : tslots)
+                    if (!(ssets[i].mask >> r & 1u)) z[i] = Fr::mul(z[i], Fr::sub(ub, pt[r]));
+            const Fe z0inv = z0inv_all[b];
+            F9* cf = &coef[(size_t)b * sh_ncoef];
+            size_t at = 0;
+            Fe vi = Fr::one(), rsum = fe_zero();
+            for (size_t i = 0; i < ssets.size(); i++, vi = Fr::mul(vi, sp.v)) {
+                const Fe w = Fr::mul(Fr::mul(vi, z[i]), z0inv);
+                Fe wy = w;
+                for (size_t j = 0; j < ssets[i].coms.size(); j++, wy = Fr::mul(wy, sp.y)) cf[at++] = coef9(wy);
+                Fe ru = fe_zero();  // R_i(u)
+                for (size_t d2 = sp.R[i].size(); d2-- > 0;) ru = Fr::add(Fr::mul(ru, ub), sp.R[i][d2]);
+                rsum = Fr::add(rsum, Fr::mul(w, ru));
+            }
+            cf[at] = coef9(Fr::neg(Fr::mul(zT, z0inv)));
+            corr[b] = rsum;
+        }
+        ZG_TICK("u");
+        ZG_TRY(publish());
+        ZG_TRY(shplonk_upload(coef, corr));
+        const uint32_t firstL = 0;  // (L's coefficients start the table of this half; its list is the last one)
+        ZG_TRY(poly_combine_weighted(ctx, polys, np, p->sh_lists + sh_first[oL], &firstL, &sh_count[oL], 1, p->sh_coef, sh_ncoef, p->sh_corr, 1,
+                                     1, p->sh_h1, n, p->wpoly, (size_t)2 * n, wp_bs, n));
+        const uint32_t uslot = PC_U_SLOT;
+        ZG_TRY(poly_kate_division(ctx, p->d_pc, np, &uslot, 1, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n, wp_bs, p->ktmp, n));
+        ctx->msm_dense_hint = true;
+        const int st_c = commit(p, phase_msm(dense_g(p), p->wpoly + n, (size_t)2 * n, 1, wp_bs, np), W_GWC);
+        ctx->msm_dense_hint = false;
+        ZG_TRY(st_c);
+        ZG_TICK("h2: queued");
+        ZG_TRY(wait_points(p, np, pts, W_GWC));
+        for (uint32_t b = 0; b < np; b++) tr[b].write_point(pts[b]);
+        return ZG_OK;
+    }
     int finish() {
         int first_bad = ZG_OK;
         if (gate_failed()) {  // (every gate kernel has ended: the last commitments came from behind them)
@@ -1114,6 +1380,8 @@ static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
                             uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, int* statuses) {
     ZG_REQUIRE(p && proofs && proof_lens && keys, ZG_ERR_INVALID_ARG, "zg_prover_prove: null argument");
     ZG_TRY(batch_args_ok("zg_prover_prove", "proofs", p, count, instance, instance_len));
+    ZG_REQUIRE(p->multiopen != ZG_MULTIOPEN_SHPLONK || (p->world <= 1 && !p->rccl_comm), ZG_ERR_UNSUPPORTED,
+               "zg_prover_prove: the SHPLONK multi-open is not made on a point-range shard of the SRS");
     ZG_REQUIRE(p->world > 1 || p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG,
                "zg_prover_prove: the base sets hold %u of %u points and no shard was declared (zg_prover_set_shard)", p->shard_n, p->pk->n);
     ZG_ENTER(p->ctx);
@@ -1154,7 +1422,7 @@ size_t zg_prover_proof_size_multi(const zg_prover* p, size_t circuits) {
     const PkDev& k = *p->pk;
     const size_t per_points = k.A + 3 * k.NL + k.sets;
     const size_t per_scalars = k.advice_queries.size() + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
-    const size_t max_open = 2 + k.advice_queries.size() + k.fixed_queries.size();
+    const size_t max_open = p->multiopen == ZG_MULTIOPEN_SHPLONK ? 2 : 2 + k.advice_queries.size() + k.fixed_queries.size();
     return 64 * (circuits * per_points + 1 + k.qpd + max_open) + 32 * (circuits * per_scalars + k.fixed_queries.size() + 1 + k.P);
 }
 

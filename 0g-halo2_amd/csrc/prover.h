@@ -168,6 +168,15 @@ struct zg_prover {
     // a proof of several circuits: its opening lists over (slot, polynomial) pairs, sized for `cap` circuits
     uint32_t* d_mlists = nullptr;
     size_t mlists_cap = 0;
+    // The multi-open argument (zg_prover_set_multiopen): GWC, or SHPLONK with its own buffers (alloc_slots, sized with the
+    // slots): h1 [cap][n], the two combinations' index lists, their per-proof coefficients (unpacked nine-limb values) and
+    // the interpolants' low coefficients
+    int multiopen = 0;
+    zg::Fe* sh_h1 = nullptr;
+    uint32_t* sh_lists = nullptr;
+    zg::F9* sh_coef = nullptr;
+    zg::Fe* sh_corr = nullptr;
+    size_t sh_terms = 0;  // opening queries of `cap` circuits: sh_lists holds 2 * sh_terms + 16 entries, sh_coef sh_terms + cap + 16
     std::map<uint32_t*, std::vector<uint32_t>> uploaded_lists;  // what h2d_list left at each destination
     std::vector<size_t> inst_filled;  // per slot: rows of inst_val that may be non-zero
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_err = nullptr;

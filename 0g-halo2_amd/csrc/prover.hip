@@ -167,6 +167,7 @@ namespace {
 void free_slots(zg_prover* p) {
     for (void* q : p->slot_owned) (void)hipFree(q);
     p->slot_owned.clear();
+    p->sh_h1 = nullptr;  // (SHPLONK's buffers went with the slots)
     if (p->pin.host) (void)hipHostFree(p->pin.host);
     p->pin = PinnedArena{};
     p->gate_seq = 0;  // (the gate word goes with the arena: a new one starts at zero, and a gate opens at its number or later)
@@ -238,12 +239,27 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
     ZG_TRY(dalloc_into(own, &p->ktmp, poly_kate_tmp_elems(n, cap * p->max_points)));
     ZG_TRY(dalloc_into(own, &p->d_pc, c));
     p->hpc.assign(cap, ProofConst{});
+    // SHPLONK's buffers, while the prover is set to it: per slot h1 and PC_MAX_POINTS + 1 rows of low
+    // coefficients; the lists and coefficients for the opening queries of `cap` single proofs, or of one proof of `cap`
+    // circuits -- the numerators' and L's behind each other
+    size_t sh_stage = 0;
+    if (p->multiopen == ZG_MULTIOPEN_SHPLONK) {
+        p->sh_terms = p->mlists_cap + c * (k.fixed_queries.size() + P + 2);
+        const size_t n_coef = p->sh_terms + c + 16, n_corr = c * (PC_MAX_POINTS + 1) * PC_MAX_POINTS;
+        ZG_TRY(dalloc_into(own, &p->sh_lists, 2 * p->sh_terms + 16));
+        ZG_TRY(dalloc_into(own, &p->sh_coef, n_coef));
+        ZG_TRY(dalloc_into(own, &p->sh_corr, n_corr));
+        ZG_TRY(dalloc_into(own, &p->sh_h1, c * n));
+        // (both halves of a batch stage their two tables and the lists: room for them, so that no upload falls back to a
+        //  pageable copy and its synchronise)
+        sh_stage = 2 * (n_coef * sizeof(F9) + n_corr * sizeof(Fe) + 256) + (2 * p->sh_terms + 16) * 4;
+    }
     // pinned (PinnedArena): commitments D2H (128 B each), evaluations D2H, error flags, then the H2D staging range
     PinnedArena& pin = p->pin;
     pin.evals_at = (c * p->maxv * sizeof(XYZZ) + 4095) & ~size_t(4095);
     pin.errors_at = pin.evals_at + c * p->max_evals * sizeof(Fe);
     pin.stage_begin = pin.evals_at + ((c * p->max_evals * sizeof(Fe) + c * NL * 4 + 4095) & ~size_t(4095));
-    pin.cap = pin.stage_begin + (1u << 20) + c * 16 * sizeof(ProofConst) + c * (size_t)k.I * 4096;
+    pin.cap = pin.stage_begin + (1u << 20) + c * 16 * sizeof(ProofConst) + c * (size_t)k.I * 4096 + sh_stage;
     // Kernels store results here that the host reads right after an event.  COHERENT (fine-grained), said explicitly:
     // with any flag but the default the runtime takes the coherence of host memory from HIP_HOST_COHERENT, and an event's
     // default release is device scope, which promises nothing about non-coherent host memory (the non-coherent form with a
@@ -878,12 +894,34 @@ int advice_into_slots(zg_prover* p, uint32_t nb, const zg_fr* const* advice_host
 
 extern "C" {
 
+int zg_prover_set_multiopen(zg_prover* p, int scheme) {
+    ZG_REQUIRE(p, ZG_ERR_INVALID_ARG, "zg_prover_set_multiopen: null prover");
+    ZG_REQUIRE(scheme == ZG_MULTIOPEN_GWC || scheme == ZG_MULTIOPEN_SHPLONK, ZG_ERR_INVALID_ARG, "zg_prover_set_multiopen: scheme %d", scheme);
+    ZG_ENTER(p->ctx);
+    if (scheme == p->multiopen) return ZG_OK;
+    ZG_TRY(prover_drain(p));
+    const int before = p->multiopen;
+    p->multiopen = scheme;
+    p->warm_sig = 0;
+    // SHPLONK's buffers and its share of the staging range come with the slots: allocate them anew (a prover that goes
+    // back to GWC keeps what it has).  A failure leaves the prover without slots, as a failed zg_prover_set_batch does.
+    if (scheme == ZG_MULTIOPEN_SHPLONK && p->cap && !p->sh_h1) {
+        p->have_last = false;
+        const int st = alloc_slots(p, p->cap);
+        if (st != ZG_OK) p->multiopen = before;
+        return st;
+    }
+    return ZG_OK;
+}
+
+int zg_prover_multiopen(const zg_prover* p) { return p ? p->multiopen : ZG_MULTIOPEN_GWC; }
+
 size_t zg_prover_proof_size(const zg_prover* p) {
     if (!p) return 0;
     const PkDev& k = *p->pk;
     size_t points = k.A + 2 * k.NL + k.sets + k.NL + 1 + k.qpd;
     size_t scalars = k.advice_queries.size() + k.fixed_queries.size() + 1 + k.P + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
-    size_t max_open = 2 + k.advice_queries.size() + k.fixed_queries.size();
+    size_t max_open = p->multiopen == ZG_MULTIOPEN_SHPLONK ? 2 : 2 + k.advice_queries.size() + k.fixed_queries.size();
     return 64 * (points + max_open) + 32 * scalars;
 }
 
@@ -1000,6 +1038,7 @@ int zg_prover_fork(const zg_prover* parent, zg_ctx* ctx, zg_prover** out) {
     p->lat_split = parent->lat_split;
     p->naf_gl_w = parent->naf_gl_w;
     p->qterms = parent->qterms;
+    p->multiopen = parent->multiopen;
     p->shard_lo = parent->shard_lo; p->shard_n = parent->shard_n; p->world = parent->world; p->rank = parent->rank;
     p->exchange = parent->exchange; p->exchange_user = parent->exchange_user;
     // (a communicator serialises its collectives on ONE stream: a fork does not inherit it)

@@ -45,11 +45,13 @@ struct alignas(16) VMono {
 struct VQuery {
     uint32_t term;  // term index of the commitment, SHARED | index, or HREF
     uint32_t eval;  // index into the proof's evaluations
-    uint32_t set;   // opening point set
-    uint32_t vpow;  // power of v within the set
+    uint32_t set;   // opening point set (SHPLONK: rotation set i)
+    uint32_t vpow;  // power of v within the set (SHPLONK: j, the commitment's place in its set = its power of y)
+    uint32_t pt;    // SHPLONK: the query's (set, point) pair in VArgs::f_pt; FIRST_PT: the commitment's first query
 };
+constexpr uint32_t FIRST_PT = 0x80000000u;
 
-enum { CH_THETA, CH_BETA, CH_GAMMA, CH_Y, CH_X, CH_V, CH_U, CH_N };
+enum { CH_THETA, CH_BETA, CH_GAMMA, CH_Y, CH_X, CH_V, CH_U, CH_SY, CH_N };  // (CH_SY: SHPLONK's y, squeezed where GWC squeezes v)
 enum { ST_OK = 1, ST_TRAILING = 0, ST_MALFORMED = -1 };
 
 struct VArgs {
@@ -68,6 +70,15 @@ struct VArgs {
     uint32_t n_gates, n_lookups, n_queries, n_iev, n_oq;
     uint32_t A, F, I, P, NL, sets, chunk, qpd, bf, nsets, nAQ, nFQ;
     uint32_t NE, NP, NT, ev_h;  // evaluations (with the expected h(x) last), per-proof points, terms
+    // the multi-open argument: nW points end a proof (GWC: one W per point set; SHPLONK: h1, h2), the last nL of them are
+    // the left side's terms (every W; h2).  SHPLONK: nS rotation sets over the nT points of T;
+    // set i holds the points f_pt[s_first[i] .. s_first[i + 1]) (indices into T, nF pairs in all) and s_mask[i] says
+    // which points of T are its own; t_wr[t] = omega^rotation of point t
+    uint32_t scheme, nW, nL, nS, nT, nF, nwork;
+    const uint32_t* s_first;
+    const uint32_t* s_mask;
+    const uint32_t* f_pt;
+    const Fe* t_wr;
     // proofs of NC circuit instances: where the families start among a proof's points (circuit c's share of a family
     // follows circuit c-1's: A advice, 2 NL permuted, `sets` permutation z, NL lookup z) and among its evaluations (nAQ
     // advice, npz permutation, 5 NL lookup evaluations per circuit)
@@ -201,9 +212,21 @@ __host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
     for (uint32_t c = 0; c < a.qpd && ok; c++) ok = read_point(r, s, pts[pi++]);
     if (ok) ch[CH_X] = sp_squeeze(s);
     for (uint32_t c = 0; c < a.ev_h && ok; c++) ok = read_scalar(r, s, ev[ei++]);
-    if (ok) ch[CH_V] = sp_squeeze(s);
-    for (uint32_t c = 0; c < a.nsets && ok; c++) ok = read_point(r, s, pts[pi++]);
-    if (ok) ch[CH_U] = sp_squeeze(s);
+    if (a.scheme == ZG_MULTIOPEN_SHPLONK) {  // y, v | h1 | u | h2
+        if (ok) {
+            ch[CH_SY] = sp_squeeze(s);
+            ch[CH_V] = sp_squeeze(s);
+            ok = read_point(r, s, pts[pi++]);
+        }
+        if (ok) {
+            ch[CH_U] = sp_squeeze(s);
+            ok = read_point(r, s, pts[pi++]);
+        }
+    } else {
+        if (ok) ch[CH_V] = sp_squeeze(s);
+        for (uint32_t c = 0; c < a.nsets && ok; c++) ok = read_point(r, s, pts[pi++]);
+        if (ok) ch[CH_U] = sp_squeeze(s);
+    }
     a.status[b] = !ok ? ST_MALFORMED : r.pos != r.len ? ST_TRAILING : ST_OK;
 }
 // One wave per proof, every lane running the same code on the same data (identical stores), so the per-proof work runs
@@ -257,8 +280,10 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
     const Fe* ch = a.ch + (size_t)b * CH_N;
     Fe* qe = a.qe + (size_t)b * (a.n_queries + a.n_iev);
     Fe* iev = qe + a.n_queries;
-    Fe* den = a.tmp + (size_t)b * 2 * a.ninv;
+    Fe* den = a.tmp + (size_t)b * (2 * a.ninv + a.nwork);
     Fe* pre = den + a.ninv;
+    Fe* tp = pre + a.ninv;  // SHPLONK: the nT points of T, then v^i z'_i per rotation set
+    Fe* vz = tp + a.nT;
     Fe* sc = a.sc + (size_t)b * a.NT;
     const Fe* inst_all = a.inst + (size_t)b * a.NC * a.I * a.ilen;
     const Fe x = ch[CH_X], y = ch[CH_Y], beta = ch[CH_BETA], gamma = ch[CH_GAMMA], theta = ch[CH_THETA];
@@ -278,7 +303,24 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
             wi = Fr::mul(wi, a.omega);
         }
     }
-    batch_inv(den, pre, 1 + nl + a.n_iev * a.ilen);  // (the same denominators serve every circuit of the proof)
+    // SHPLONK: per (set, point) pair the barycentric denominator prod_(q in S_i, q != p) (p - q), then z_0 = prod_(r in T \ S_0) (u - r)
+    const uint32_t d_sh = 1 + nl + a.n_iev * a.ilen;
+    const bool shplonk = a.scheme == ZG_MULTIOPEN_SHPLONK;
+    if (shplonk) {
+        for (uint32_t t = 0; t < a.nT; t++) tp[t] = Fr::mul(x, a.t_wr[t]);
+        for (uint32_t i = 0; i < a.nS; i++)
+            for (uint32_t f = a.s_first[i]; f < a.s_first[i + 1]; f++) {
+                Fe d = one;
+                for (uint32_t g = a.s_first[i]; g < a.s_first[i + 1]; g++)
+                    if (g != f) d = Fr::mul(d, Fr::sub(tp[a.f_pt[f]], tp[a.f_pt[g]]));
+                den[d_sh + f] = d;
+            }
+        Fe z0 = one;
+        for (uint32_t t = 0; t < a.nT; t++)
+            if (!(a.s_mask[0] >> t & 1u)) z0 = Fr::mul(z0, Fr::sub(u, tp[t]));
+        den[d_sh + a.nF] = z0;
+    }
+    batch_inv(den, pre, d_sh + (shplonk ? a.nF + 1 : 0));  // (the same denominators serve every circuit of the proof)
     // l_i(x) = (x^n - 1)/n * omega^i / (x - omega^i)
     const Fe num = Fr::mul(Fr::sub(xn, one), a.ifft_div);
     Fe llast = fe_zero(), l0 = fe_zero(), lblind = fe_zero();
@@ -354,12 +396,39 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
 
     // term scalars: u^j v^k on each commitment (x_n^i more on the h pieces), -sum u^j e_j on g0, u^j and u^j z_j on W_j
     for (uint32_t t = 0; t < a.NT; t++) sc[t] = fe_zero();
-    const uint32_t T_SHARED = a.NP + a.nsets, T_G0 = a.NT - 1, PT_H = a.PT_RAND + 1, PT_W = PT_H + a.qpd;
+    const uint32_t T_SHARED = a.NP + a.nL, T_G0 = a.NT - 1, PT_H = a.PT_RAND + 1, PT_W = PT_H + a.qpd;
     Fe g0 = fe_zero();
+    if (shplonk) {
+        // the Lagrange basis of every set at u, prod_(q != p) (u - q) / prod_(q != p) (p - q), in the denominators' place;
+        // v^i z'_i with z'_0 = 1, z'_i = z_i / z_0, z_i = prod_(r in T \ S_i) (u - r)
+        for (uint32_t i = 0; i < a.nS; i++)
+            for (uint32_t f = a.s_first[i]; f < a.s_first[i + 1]; f++) {
+                Fe l = den[d_sh + f];
+                for (uint32_t g = a.s_first[i]; g < a.s_first[i + 1]; g++)
+                    if (g != f) l = Fr::mul(l, Fr::sub(u, tp[a.f_pt[g]]));
+                den[d_sh + f] = l;
+            }
+        Fe vi = one;
+        for (uint32_t i = 0; i < a.nS; i++) {
+            Fe z = one;
+            for (uint32_t t = 0; t < a.nT; t++)
+                if (!(a.s_mask[i] >> t & 1u)) z = Fr::mul(z, Fr::sub(u, tp[t]));
+            vz[i] = i ? Fr::mul(vi, Fr::mul(z, den[d_sh + a.nF])) : one;
+            vi = Fr::mul(vi, v);
+        }
+    }
+    const Fe sy = ch[shplonk ? CH_SY : CH_V];
     for (uint32_t q = 0; q < a.n_oq; q++) {
         const VQuery oq = a.oq[q];
-        const Fe coef = Fr::mul(Fr::pow_u64(u, oq.set), Fr::pow_u64(v, oq.vpow));
-        g0 = Fr::sub(g0, Fr::mul(coef, ev[oq.eval]));
+        // GWC: u^j v^k on the commitment and the evaluation.  SHPLONK: v^i z'_i y^j on the commitment, once, and on
+        // R_ij(u), of which this query's evaluation is the share of one point
+        const Fe coef = shplonk ? Fr::mul(vz[oq.set], Fr::pow_u64(sy, oq.vpow)) : Fr::mul(Fr::pow_u64(u, oq.set), Fr::pow_u64(v, oq.vpow));
+        if (shplonk) {
+            g0 = Fr::sub(g0, Fr::mul(Fr::mul(coef, ev[oq.eval]), den[d_sh + (oq.pt & ~FIRST_PT)]));
+            if (!(oq.pt & FIRST_PT)) continue;
+        } else {
+            g0 = Fr::sub(g0, Fr::mul(coef, ev[oq.eval]));
+        }
         if (oq.term == HREF) {
             Fe c = coef;
             for (uint32_t i = 0; i < a.qpd; i++) {
@@ -372,11 +441,19 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
         }
     }
     sc[T_G0] = g0;
-    Fe uj = one;
-    for (uint32_t j = 0; j < a.nsets; j++) {
-        sc[a.NP + j] = uj;
-        sc[PT_W + j] = Fr::add(sc[PT_W + j], Fr::mul(uj, Fr::mul(x, a.set_wr[j])));
-        uj = Fr::mul(uj, u);
+    if (shplonk) {  // R_b = ... - Z_0 h1 + u h2 with Z_0 = prod_(r in S_0) (u - r); the left side is h2
+        Fe Z0 = one;
+        for (uint32_t f = a.s_first[0]; f < a.s_first[1]; f++) Z0 = Fr::mul(Z0, Fr::sub(u, tp[a.f_pt[f]]));
+        sc[PT_W] = Fr::neg(Z0);
+        sc[PT_W + 1] = u;
+        sc[a.NP] = one;
+    } else {
+        Fe uj = one;
+        for (uint32_t j = 0; j < a.nsets; j++) {
+            sc[a.NP + j] = uj;
+            sc[PT_W + j] = Fr::add(sc[PT_W + j], Fr::mul(uj, Fr::mul(x, a.set_wr[j])));
+            uj = Fr::mul(uj, u);
+        }
     }
     for (uint32_t t = 0; t < a.NT; t++) sc[t] = Fr::to_raw(sc[t]);
 }
@@ -407,10 +484,10 @@ __global__ __launch_bounds__(TERMS_WG) void verify_terms(VArgs a) {
     if (live) {
         const Affine* pts = a.pts + (size_t)b * a.NP;
         const Fe* sc = a.sc + (size_t)b * a.NT;
-        const uint32_t PT_W = a.NP - a.nsets;
+        const uint32_t PT_L = a.NP - a.nL;  // (the left side's points end the proof: every W of GWC, SHPLONK's h2)
         for (uint32_t t = tid; t < a.NT; t += TERMS_WG) {
-            const bool left = t >= a.NP && t < a.NP + a.nsets;
-            const Affine p = t < a.NP ? pts[t] : left ? pts[PT_W + t - a.NP] : a.shared[t - a.NP - a.nsets];
+            const bool left = t >= a.NP && t < a.NP + a.nL;
+            const Affine p = t < a.NP ? pts[t] : left ? pts[PT_L + t - a.NP] : a.shared[t - a.NP - a.nL];
             const XYZZ m = xyzz_mul_raw(p, sc[t].l);
             if (left) accl = xyzz_add(accl, m);
             else accr = xyzz_add(accr, m);
@@ -460,11 +537,16 @@ struct zg_verifier {
     std::vector<void*> owned;  // circuit arrays
     // what the query table of a proof of NC circuits is built from, and the tables made so far (by NC)
     std::vector<zg_query> advice_queries, fixed_queries;
+    int scheme = ZG_MULTIOPEN_GWC;  // zg_verifier_set_multiopen
     struct Table {
         const VQuery* oq = nullptr;
         uint32_t n_oq = 0;
+        // SHPLONK: the rotation sets (VArgs)
+        uint32_t nS = 0, nT = 0, nF = 0;
+        const uint32_t *s_first = nullptr, *s_mask = nullptr, *f_pt = nullptr;
+        const Fe* t_wr = nullptr;
     };
-    std::map<uint32_t, Table> tables;
+    std::map<std::pair<uint32_t, int>, Table> tables;  // by (circuits, scheme)
     // batch buffers, grown on demand (cap: proofs; pts / ev / sc: elements, their size per proof follows NC)
     size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0, pts_cap = 0, ev_cap = 0, sc_cap = 0;
     std::vector<void*> batch;
@@ -564,7 +646,7 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
             set_rot.push_back(key);
             set_size.push_back(0);
         }
-        oq.push_back({term, eval, j, set_size[j]++});
+        oq.push_back({term, eval, j, set_size[j]++, 0});
     };
     for (uint32_t c = 0; c < NC; c++) {
         const uint32_t pt_adv = c * a.A, pt_lk = a.PT_LK + c * 2 * a.NL, pt_pz = a.PT_PZ + c * a.sets, pt_lz = a.PT_LZ + c * a.NL;
@@ -588,15 +670,85 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
     for (uint32_t c = 0; c < a.P; c++) add(0, SHARED | (a.F + c), a.EV_SIG + c);
     add(0, HREF, a.ev_h);
     add(0, a.PT_RAND, EV_RAND);
-    // v-powers run down within a set: the first query of a set of m gets v^(m-1)
-    for (VQuery& q : oq) q.vpow = set_size[q.set] - 1 - q.vpow;
     a.nsets = (uint32_t)set_rot.size();
     a.n_oq = (uint32_t)oq.size();
-    a.NP = a.PT_RAND + 1 + a.qpd + a.nsets;
-    a.NT = a.NP + a.nsets + a.F + a.P + 1;
-    auto it = v->tables.find(NC);
+    a.scheme = (uint32_t)v->scheme;
+    const bool shplonk = v->scheme == ZG_MULTIOPEN_SHPLONK;
+    a.nW = shplonk ? 2 : a.nsets;
+    a.nL = shplonk ? 1 : a.nsets;
+    a.NP = a.PT_RAND + 1 + a.qpd + a.nW;
+    a.NT = a.NP + a.nL + a.F + a.P + 1;
+    auto it = v->tables.find({NC, v->scheme});
     if (it == v->tables.end()) {
         zg_verifier::Table t;
+        if (shplonk) {
+            // construct_intermediate_sets over the same queries (`set` is the query's point so far): commitments by first
+            // appearance -- a term index names one -- with the points they are opened at; rotation sets by equal point
+            // sets, in the order of their first commitment; T = the points, numbered as GWC numbers its sets
+            ZG_REQUIRE(set_rot.size() <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "zg_verifier: %zu opening points (max %u)", set_rot.size(),
+                       PC_MAX_POINTS);
+            std::vector<uint32_t> com_term, com_mask, set_mask, set_count;
+            {  // a commitment's points are a SET: a (commitment, point) pair queried twice counts once, as in the prover
+                std::vector<VQuery> once;
+                for (const VQuery& q : oq) {
+                    bool dup = false;
+                    for (const VQuery& o : once) dup = dup || (o.term == q.term && o.set == q.set);
+                    if (!dup) once.push_back(q);
+                }
+                oq.swap(once);
+                a.n_oq = (uint32_t)oq.size();
+            }
+            for (const VQuery& q : oq) {
+                size_t c = 0;
+                while (c < com_term.size() && com_term[c] != q.term) c++;
+                if (c == com_term.size()) {
+                    com_term.push_back(q.term);
+                    com_mask.push_back(0);
+                }
+                com_mask[c] |= 1u << q.set;
+            }
+            std::vector<uint32_t> com_set(com_term.size()), com_j(com_term.size());
+            for (size_t c = 0; c < com_term.size(); c++) {
+                size_t i = 0;
+                while (i < set_mask.size() && set_mask[i] != com_mask[c]) i++;
+                if (i == set_mask.size()) {
+                    set_mask.push_back(com_mask[c]);
+                    set_count.push_back(0);
+                }
+                com_set[c] = (uint32_t)i;
+                com_j[c] = set_count[i]++;
+            }
+            ZG_REQUIRE(set_mask.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_verifier: %zu rotation sets (max %u)", set_mask.size(),
+                       HC_MAX_SETS);
+            std::vector<uint32_t> s_first(1, 0), f_pt;
+            for (uint32_t m : set_mask) {
+                for (uint32_t t = 0; t < set_rot.size(); t++)
+                    if (m >> t & 1u) f_pt.push_back(t);
+                s_first.push_back((uint32_t)f_pt.size());
+            }
+            std::vector<char> seen(com_term.size(), 0);
+            for (VQuery& q : oq) {
+                size_t c = 0;
+                while (com_term[c] != q.term) c++;
+                const uint32_t i = com_set[c];
+                uint32_t f = s_first[i];
+                while (f_pt[f] != q.set) f++;
+                q.pt = f | (seen[c] ? 0u : FIRST_PT);
+                seen[c] = 1;
+                q.set = i;
+                q.vpow = com_j[c];
+            }
+            std::vector<Fe> t_wr;
+            for (int64_t r : set_rot) t_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
+            t.nS = (uint32_t)set_mask.size(); t.nT = (uint32_t)set_rot.size(); t.nF = (uint32_t)f_pt.size();
+            ZG_TRY(upload(v, &t.s_first, s_first));
+            ZG_TRY(upload(v, &t.s_mask, set_mask));
+            ZG_TRY(upload(v, &t.f_pt, f_pt));
+            ZG_TRY(upload(v, &t.t_wr, t_wr));
+        } else {
+            // v-powers run down within a set: the first query of a set of m gets v^(m-1)
+            for (VQuery& q : oq) q.vpow = set_size[q.set] - 1 - q.vpow;
+        }
         ZG_TRY(upload(v, &t.oq, oq));
         t.n_oq = a.n_oq;
         if (!a.set_wr) {  // (the point sets do not depend on NC)
@@ -604,9 +756,13 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
             for (int64_t r : set_rot) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
             ZG_TRY(upload(v, &a.set_wr, set_wr));
         }
-        it = v->tables.emplace(NC, t).first;
+        it = v->tables.emplace(std::make_pair(NC, v->scheme), t).first;
     }
-    a.oq = it->second.oq;
+    const zg_verifier::Table& t = it->second;
+    a.oq = t.oq;
+    a.n_oq = t.n_oq;  // (SHPLONK's table holds a repeated (commitment, point) pair once)
+    a.nS = t.nS; a.nT = t.nT; a.nF = t.nF; a.nwork = t.nT + t.nS;
+    a.s_first = t.s_first; a.s_mask = t.s_mask; a.f_pt = t.f_pt; a.t_wr = t.t_wr;
     return ZG_OK;
 }
 
@@ -753,6 +909,16 @@ void zg_verifier_destroy(zg_verifier* v) {
     delete v;
 }
 
+int zg_verifier_set_multiopen(zg_verifier* v, int scheme) {
+    ZG_REQUIRE(v, ZG_ERR_INVALID_ARG, "zg_verifier_set_multiopen: null verifier");
+    ZG_REQUIRE(scheme == ZG_MULTIOPEN_GWC || scheme == ZG_MULTIOPEN_SHPLONK, ZG_ERR_INVALID_ARG, "zg_verifier_set_multiopen: scheme %d", scheme);
+    ZG_ENTER(v->ctx);
+    v->scheme = scheme;
+    return ZG_OK;
+}
+
+int zg_verifier_multiopen(const zg_verifier* v) { return v ? v->scheme : ZG_MULTIOPEN_GWC; }
+
 int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const* proofs, const size_t* proof_lens,
                              const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
     return zg_verifier_verify_multi(v, count, 1, proofs, proof_lens, instance, instance_len, key, verdicts);
@@ -800,8 +966,9 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
             if (fe_is_zero(rb[b])) rb[b].l[0] = 1;  // (a zero weight would hide the proof; probability 2^-254)
         }
         // inversion scratch per proof: x^n - 1, the bf + 2 Lagrange denominators, one per instance slot and row (twice)
-        a.ninv = 1 + (a.bf + 2) + a.n_iev * (uint32_t)instance_len;
-        ZG_TRY(ensure(v, count, total, count * per_inst, count * 2 * (size_t)a.ninv));
+        // (SHPLONK: one more per (set, point) pair and z_0; behind the two halves its nT points and nS set weights)
+        a.ninv = 1 + (a.bf + 2) + a.n_iev * (uint32_t)instance_len + (a.scheme == ZG_MULTIOPEN_SHPLONK ? a.nF + 1 : 0);
+        ZG_TRY(ensure(v, count, total, count * per_inst, count * (2 * (size_t)a.ninv + a.nwork)));
         a.count = (uint32_t)count;
         a.ilen = (uint32_t)instance_len;
         hipStream_t st = ctx->stream;

@@ -95,7 +95,11 @@ ABI_SYMBOLS = [
     "zg_prover_set_quotient_terms", "zg_prover_quotient_terms",
     "zg_g1_mul_each", "zg_g1_mul_each_dev", "zg_params_g2", "zg_g2_mul", "zg_params_update", "zg_params_update_dev",
     "zg_params_check_update",
+    "zg_prover_set_multiopen", "zg_prover_multiopen", "zg_verifier_set_multiopen", "zg_verifier_multiopen",
 ]
+
+# zg_prover_set_multiopen / zg_verifier_set_multiopen: the multi-open argument a proof ends with
+MULTIOPEN_GWC, MULTIOPEN_SHPLONK = 0, 1
 
 # zg_params_check: bits of `failed`
 SRS_G1_MALFORMED, SRS_G1_IDENTITY, SRS_G2, SRS_POWERS, SRS_LAGRANGE = 1, 2, 4, 8, 16
@@ -776,6 +780,17 @@ class Prover:
     def set_batch(self, max_batch: int):
         _check(self.ctx.lib.zg_prover_set_batch(self.h, c_size_t(max_batch)))
 
+    def set_multiopen(self, scheme: int):
+        """zg_prover_set_multiopen: MULTIOPEN_GWC (default) or MULTIOPEN_SHPLONK; the size bounds follow it."""
+        self.ctx.lib.zg_prover_set_multiopen.argtypes = [c_void_p, ctypes.c_int]
+        _check(self.ctx.lib.zg_prover_set_multiopen(self.h, ctypes.c_int(scheme)))
+        self.proof_cap = int(self.ctx.lib.zg_prover_proof_size(self.h))
+
+    @property
+    def multiopen(self) -> int:
+        self.ctx.lib.zg_prover_multiopen.argtypes = [c_void_p]
+        return int(self.ctx.lib.zg_prover_multiopen(self.h))
+
     @property
     def batch(self) -> int:
         return int(self.ctx.lib.zg_prover_batch(self.h))
@@ -1132,6 +1147,16 @@ class Verifier:
                                       ctypes.byref(h)))
         self.h = h
         ctx._adopt(self)
+
+    def set_multiopen(self, scheme: int):
+        """zg_verifier_set_multiopen: which multi-open argument the proofs end with (MULTIOPEN_GWC / MULTIOPEN_SHPLONK)."""
+        self.ctx.lib.zg_verifier_set_multiopen.argtypes = [c_void_p, ctypes.c_int]
+        _check(self.ctx.lib.zg_verifier_set_multiopen(self.h, ctypes.c_int(scheme)))
+
+    @property
+    def multiopen(self) -> int:
+        self.ctx.lib.zg_verifier_multiopen.argtypes = [c_void_p]
+        return int(self.ctx.lib.zg_verifier_multiopen(self.h))
 
     def verify(self, proofs, instances, key) -> list:
         """Verdict per proof: 1 accepted, 0 rejected, < 0 malformed.  instances[b]: uint64[n_instance, len, 4];

@@ -621,6 +621,23 @@ int zg_prover_quotient_terms(const zg_prover *p, uint32_t *out, size_t cap, size
  * polynomial h from fewer evaluations) and the MSM reductions spend one lane per EC addition.  Proof bytes do
  * not depend on it. */
 int zg_prover_set_overlap(zg_prover *p, int enable);
+/* The multi-open argument a prover ends its proofs with.  ZG_MULTIOPEN_GWC (default): halo2's ProverGWC, one witness
+ * commitment per distinct opening point.  ZG_MULTIOPEN_SHPLONK: ProverSHPLONK (halo2_proofs v2023_04_20
+ * src/poly/kzg/multiopen/shplonk/; snark-verifier's Bdfg21): TWO commitments whatever the number of points, so a proof is
+ * 64 * (point sets - 2) bytes shorter; everything up to and including the evaluations is the GWC proof's, byte for byte.
+ * Order and equations: DESIGN.md section 16.  A property of the prover object, like zg_prover_set_overlap: it governs
+ * zg_prover_prove, _dev, _batch, _batch_dev, _images, zg_prover_prove_multi, _multi_dev, _images_multi and the two
+ * proof-size bounds; a fork starts with its parent's value.  The buffers SHPLONK needs, and its share of the pinned
+ * staging range, are allocated HERE and resized by zg_prover_set_batch, never inside a proof: the first switch to SHPLONK
+ * allocates the prover's slots anew, as zg_prover_set_batch does -- addresses from zg_prover_advice_slot and the slots'
+ * contents do not survive it (ZG_ERR_OOM leaves the prover without slots and the setting unchanged).  Both scheduling forms make the same bytes; a SHPLONK prover makes its
+ * proofs in the plain order -- the ZG_LAT_GATE gate does not arm, because the second commitment starts from the first
+ * one's challenge.  On a point-range shard (zg_prover_set_shard*) a SHPLONK proof is refused with ZG_ERR_UNSUPPORTED.
+ * More than 16 rotation sets or distinct opening points: ZG_ERR_UNSUPPORTED at the proof; an identity h1 or h2 is
+ * refused as every identity commitment is.  Any other scheme value: ZG_ERR_INVALID_ARG, nothing changes. */
+enum { ZG_MULTIOPEN_GWC = 0, ZG_MULTIOPEN_SHPLONK = 1 };
+int zg_prover_set_multiopen(zg_prover *p, int scheme);
+int zg_prover_multiopen(const zg_prover *p);
 /* Builds the digit tables (zg_bases_enable_digit_table) of the prover's three base sets -- ParamsKZG::g, ::g_lagrange and
  * the running sums of g_lagrange -- which a LONE proof (zg_prover_set_overlap(p, 1)) then uses instead of Pippenger buckets:
  * 2.9 -> 2.2 ms per create_proof at k = 14.  Footprint: 3 x ceil(255 / c) * 2^(c-1) * n * 64 B -- 78 GB at n = 2^14 (c = 11),
@@ -863,6 +880,13 @@ int zg_verifier_verify_batch(zg_verifier *v, size_t count, const uint8_t *const 
 int zg_verifier_verify_multi(zg_verifier *v, size_t count, size_t circuits, const uint8_t *const *proofs,
                              const size_t *proof_lens, const zg_fr *const *instance, size_t instance_len,
                              const uint8_t key[32], int *verdicts);
+/* Which multi-open argument the proofs handed to zg_verifier_verify_batch / _multi end with (ZG_MULTIOPEN_*, default GWC;
+ * VerifierSHPLONK: DESIGN.md section 16).  Verdict classes are the same: a point of the tail that is off the curve, at
+ * infinity or not canonical gives a negative verdict, trailing bytes or a failing equation 0.  Query tables are built per
+ * (scheme, circuits) at first use and kept.  More than 16 rotation sets or opening points: ZG_ERR_UNSUPPORTED from the
+ * verification call.  Any other value: ZG_ERR_INVALID_ARG, nothing changes. */
+int zg_verifier_set_multiopen(zg_verifier *v, int scheme);
+int zg_verifier_multiopen(const zg_verifier *v);
 /* Host helper (no device): *result = 1 iff prod_i e(p[i], q[i]) = 1 in GT (BN254 optimal ate pairing); identity
  * points contribute 1.  The points are taken to be in G1 and G2.  bn256::multi_miller_loop + final_exponentiation. */
 int zg_pairing_check(const zg_g1_affine *p, const zg_g2_affine *q, size_t n, int *result);
