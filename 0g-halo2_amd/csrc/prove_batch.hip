@@ -239,7 +239,7 @@ struct ProveBatch {
     double parts_en, ext_unit;  // (profile charges: SURVEY.md 8d counts one coeff_to_extended as (n + 2^ext_k) * 32 B whatever parts it is computed on)
     // ---- state carried from phase to phase
     PolySet polys;
-    std::vector<EvmTranscript> tr;
+    std::vector<Transcript> tr;  // (EvmTranscript or halo2's Blake2b one: zg_prover_set_transcript)
     std::vector<int> status;
     std::vector<Jac> pts;
     Fe* random_row = nullptr;  // (proof 0's; proof b's is perm_bs further)
@@ -296,6 +296,7 @@ struct ProveBatch {
           status(count, ZG_OK), shplonk(p_->multiopen == ZG_MULTIOPEN_SHPLONK) {
         n = pk.n; k = pk.k; ek = pk.ext_k; bf = pk.bf; usable = pk.usable;
         A = pk.A; I = pk.I; P = pk.P; NL = pk.NL; S = pk.sets; Q = pk.qpd;
+        for (Transcript& t : tr) t.blake2b = p->transcript == ZG_TRANSCRIPT_BLAKE2B;
         hat = pk.hat;
         split = pk.nparts == 3 && (!p->use_side || p->lat_split);
         phase_cosets = p->use_side || !split;
@@ -314,7 +315,7 @@ struct ProveBatch {
     }
 
     Fe* pp_at(uint32_t ix) const { return p->pp + (size_t)(ix - p->nsh) * n; }  // proof 0's polynomial ix (>= nsh)
-    EvmTranscript& T(uint32_t b) { return tr[multi ? 0 : b]; }                  // the transcript slot b writes into
+    Transcript& T(uint32_t b) { return tr[multi ? 0 : b]; }                     // the transcript slot b writes into
     // a challenge into every slot's scalars: each proof's own, or the one proof's for all its circuits
     void squeeze_into(Fe ProofConst::*field) {
         for (uint32_t b = 0; b < nb; b++) p->hpc[b].*field = b < ntr ? tr[b].squeeze() : p->hpc[0].*field;
@@ -940,7 +941,7 @@ struct ProveBatch {
         if (multi) {
             // every circuit's advice evaluations | fixed, random, sigma once | every circuit's permutation evaluations |
             // every circuit's lookup evaluations
-            EvmTranscript& t = tr[0];
+            Transcript& t = tr[0];
             for (uint32_t c = 0; c < nb; c++)
                 for (size_t i = 0; i < e_fixed; i++) t.write_scalar(ev_of(c, i));
             for (size_t i = e_fixed; i < e_pz; i++) t.write_scalar(ev_of(0, i));
@@ -1349,17 +1350,17 @@ struct ProveBatch {
             return ZG_ERR_HIP;
         }
         for (uint32_t b = 0; b < ntr; b++) {
-            if (status[b] == ZG_OK && tr[b].failed) {
-                set_error("zg_prover_prove: a commitment of proof %u is the identity point; EvmTranscript cannot absorb it", b);
+            if (status[b] == ZG_OK && tr[b].failed()) {
+                set_error("zg_prover_prove: a commitment of proof %u is the identity point; %s cannot absorb it", b, tr[b].name());
                 status[b] = ZG_ERR_INVALID_ARG;
             }
-            if (status[b] == ZG_OK && tr[b].stream.size() > proof_cap) {
-                set_error("zg_prover_prove: proof buffer too small (%zu > %zu)", tr[b].stream.size(), proof_cap);
+            if (status[b] == ZG_OK && tr[b].stream().size() > proof_cap) {
+                set_error("zg_prover_prove: proof buffer too small (%zu > %zu)", tr[b].stream().size(), proof_cap);
                 status[b] = ZG_ERR_INVALID_ARG;
             }
             if (status[b] == ZG_OK) {
-                memcpy(proofs[b], tr[b].stream.data(), tr[b].stream.size());
-                proof_lens[b] = tr[b].stream.size();
+                memcpy(proofs[b], tr[b].stream().data(), tr[b].stream().size());
+                proof_lens[b] = tr[b].stream().size();
             } else {
                 proof_lens[b] = 0;
                 if (first_bad == ZG_OK) first_bad = status[b];
@@ -1423,7 +1424,8 @@ size_t zg_prover_proof_size_multi(const zg_prover* p, size_t circuits) {
     const size_t per_points = k.A + 3 * k.NL + k.sets;
     const size_t per_scalars = k.advice_queries.size() + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
     const size_t max_open = p->multiopen == ZG_MULTIOPEN_SHPLONK ? 2 : 2 + k.advice_queries.size() + k.fixed_queries.size();
-    return 64 * (circuits * per_points + 1 + k.qpd + max_open) + 32 * (circuits * per_scalars + k.fixed_queries.size() + 1 + k.P);
+    const size_t point_bytes = p->transcript == ZG_TRANSCRIPT_BLAKE2B ? 32 : 64;
+    return point_bytes * (circuits * per_points + 1 + k.qpd + max_open) + 32 * (circuits * per_scalars + k.fixed_queries.size() + 1 + k.P);
 }
 
 int zg_prover_prove_multi(zg_prover* p, size_t circuits, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,

@@ -172,6 +172,7 @@ struct zg_prover {
     // slots): h1 [cap][n], the two combinations' index lists, their per-proof coefficients (unpacked nine-limb values) and
     // the interpolants' low coefficients
     int multiopen = 0;
+    int transcript = 0;  // zg_prover_set_transcript: ZG_TRANSCRIPT_EVM, or halo2's Blake2b transcript with compressed points
     zg::Fe* sh_h1 = nullptr;
     uint32_t* sh_lists = nullptr;
     zg::F9* sh_coef = nullptr;

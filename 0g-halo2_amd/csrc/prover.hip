@@ -916,13 +916,24 @@ int zg_prover_set_multiopen(zg_prover* p, int scheme) {
 
 int zg_prover_multiopen(const zg_prover* p) { return p ? p->multiopen : ZG_MULTIOPEN_GWC; }
 
+int zg_prover_set_transcript(zg_prover* p, int transcript) {
+    ZG_REQUIRE(p, ZG_ERR_INVALID_ARG, "zg_prover_set_transcript: null prover");
+    ZG_REQUIRE(transcript == ZG_TRANSCRIPT_EVM || transcript == ZG_TRANSCRIPT_BLAKE2B, ZG_ERR_INVALID_ARG,
+               "zg_prover_set_transcript: transcript %d", transcript);
+    ZG_ENTER(p->ctx);
+    p->transcript = transcript;  // (host state only: read when a batch of proofs starts)
+    return ZG_OK;
+}
+
+int zg_prover_transcript(const zg_prover* p) { return p ? p->transcript : ZG_TRANSCRIPT_EVM; }
+
 size_t zg_prover_proof_size(const zg_prover* p) {
     if (!p) return 0;
     const PkDev& k = *p->pk;
     size_t points = k.A + 2 * k.NL + k.sets + k.NL + 1 + k.qpd;
     size_t scalars = k.advice_queries.size() + k.fixed_queries.size() + 1 + k.P + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
     size_t max_open = p->multiopen == ZG_MULTIOPEN_SHPLONK ? 2 : 2 + k.advice_queries.size() + k.fixed_queries.size();
-    return 64 * (points + max_open) + 32 * scalars;
+    return (p->transcript == ZG_TRANSCRIPT_BLAKE2B ? 32 : 64) * (points + max_open) + 32 * scalars;
 }
 
 void zg_prover_destroy(zg_prover* p) {
@@ -1039,6 +1050,7 @@ int zg_prover_fork(const zg_prover* parent, zg_ctx* ctx, zg_prover** out) {
     p->naf_gl_w = parent->naf_gl_w;
     p->qterms = parent->qterms;
     p->multiopen = parent->multiopen;
+    p->transcript = parent->transcript;
     p->shard_lo = parent->shard_lo; p->shard_n = parent->shard_n; p->world = parent->world; p->rank = parent->rank;
     p->exchange = parent->exchange; p->exchange_user = parent->exchange_user;
     // (a communicator serialises its collectives on ONE stream: a fork does not inherit it)

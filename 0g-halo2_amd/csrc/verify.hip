@@ -10,6 +10,9 @@
 // k over a set's queries in query order.  Four launches and one host step:
 //   verify_replay   one wave per proof: the EvmTranscript read back (Keccak-f[1600]), every point and
 //                   scalar validated as it is read, the challenges theta, beta, gamma, y, x, v, u squeezed;
+//                   (zg_verifier_set_transcript(ZG_TRANSCRIPT_BLAKE2B), DESIGN.md section 17: g1_decompress_kernel of
+//                   g1_compress.hip first -- one lane per commitment of the batch, y from x -- then verify_replay_b2,
+//                   the same walk over the decompressed points with BLAKE2b and little-endian scalars)
 //   verify_scalars  one wave per proof: x^n, l_0 / l_last / l_blind and the instance evaluations (Lagrange form,
 //                   O(instance_len) per query) with one batched inversion, the expected h(x) from the gates, the
 //                   permutation and the lookups folded with y, then every term's scalar of L_b and R_b;
@@ -18,15 +21,18 @@
 //   verify_fold     one workgroup: L = sum_b r_b L_b, R = sum_b r_b R_b;
 //   host            e(L, [s]_2) e(-R, [1]_2) = 1 (pairing.hip), outside the context lock; if it fails, the batch is
 //                   bisected over the weighted pairs down to the proofs that fail alone.
+#include <array>
 #include <cstring>
 #include <map>
 
+#include "blake2b.h"
 #include "keccak.h"
 #include "poly.h"
 
 namespace zg {
 
 bool pairing_product_is_one(const Affine* p, const zg_g2_affine* q, size_t n);
+int g1_decompress_dev(zg_ctx* ctx, const uint8_t* d_in, size_t n, Affine* d_out, uint8_t* d_valid);
 
 namespace {
 
@@ -92,6 +98,10 @@ struct VArgs {
     const Fe* inst;  // [count][NC][I][ilen]
     uint32_t ilen, count;
     Affine* pts;     // [count][NP]
+    // Blake2b transcript: the proofs' commitments gathered for g1_decompress_kernel, its flags, and the length of a proof
+    uint8_t* enc;    // [count][NP][32]
+    uint8_t* pvalid; // [count][NP]
+    uint64_t b2_len;
     Fe* ev;          // [count][NE]
     Fe* ch;          // [count][CH_N]
     int* status;     // [count]
@@ -229,6 +239,82 @@ __host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
     }
     a.status[b] = !ok ? ST_MALFORMED : r.pos != r.len ? ST_TRAILING : ST_OK;
 }
+// The same walk for halo2's Blake2b transcript (blake2b.h; the format: include/zg_halo2.h, zg_prover_set_transcript).  A
+// proof is a fixed layout of 32-byte items, so a short one is malformed before anything is read; the commitments are in
+// pts already, decompressed by g1_decompress_kernel with their flags in pvalid (an invalid encoding and the identity are
+// refused here, where the transcript would refuse them); scalars are little-endian canonical integers below r.
+__host__ __device__ bool b2_point(Blake2b& s, const Affine& p, uint8_t valid, uint64_t& pos) {
+    pos += 32;
+    if (!valid || affine_is_identity(p)) return false;
+    b2_byte(s, 1);
+    b2_int(s, Fq::to_raw(p.x));
+    b2_int(s, Fq::to_raw(p.y));
+    return true;
+}
+__host__ __device__ bool b2_scalar(Blake2b& s, const uint8_t* b, uint64_t& pos, Fe& out) {
+    Fe v;
+    for (int i = 0; i < 8; i++)
+        v.l[i] = (uint32_t)b[pos + 4 * i] | ((uint32_t)b[pos + 4 * i + 1] << 8) | ((uint32_t)b[pos + 4 * i + 2] << 16) |
+                 ((uint32_t)b[pos + 4 * i + 3] << 24);
+    pos += 32;
+    if (!below_modulus<FrParams>(v)) return false;
+    out = Fr::from_raw(v);
+    b2_byte(s, 2);
+    b2_int(s, v);
+    return true;
+}
+__host__ __device__ void replay_one_b2(const VArgs& a, uint32_t b) {
+    if (a.len[b] < a.b2_len) {
+        a.status[b] = ST_MALFORMED;
+        return;
+    }
+    Blake2b s;
+    b2_init_halo2(s);
+    const uint8_t* bytes = a.bytes + a.off[b];
+    const Affine* pts = a.pts + (size_t)b * a.NP;
+    const uint8_t* pv = a.pvalid + (size_t)b * a.NP;
+    Fe* ev = a.ev + (size_t)b * a.NE;
+    Fe* ch = a.ch + (size_t)b * CH_N;
+    b2_byte(s, 2);
+    b2_int(s, Fr::to_raw(a.vk_repr));
+    const Fe* inst = a.inst + (size_t)b * a.NC * a.I * a.ilen;
+    for (uint32_t i = 0; i < a.NC * a.I * a.ilen; i++) {
+        b2_byte(s, 2);
+        b2_int(s, Fr::to_raw(inst[i]));
+    }
+    bool ok = true;
+    uint32_t pi = 0, ei = 0;
+    uint64_t pos = 0;
+#define B2_POINTS(count)                                                 \
+    for (uint32_t c = 0; c < (count) && ok; c++, pi++) ok = b2_point(s, pts[pi], pv[pi], pos)
+    B2_POINTS(a.NC * a.A);
+    if (ok) ch[CH_THETA] = b2_squeeze(s);
+    B2_POINTS(a.NC * 2 * a.NL);
+    if (ok) {
+        ch[CH_BETA] = b2_squeeze(s);
+        ch[CH_GAMMA] = b2_squeeze(s);
+    }
+    B2_POINTS(a.NC * (a.sets + a.NL) + 1);
+    if (ok) ch[CH_Y] = b2_squeeze(s);
+    B2_POINTS(a.qpd);
+    if (ok) ch[CH_X] = b2_squeeze(s);
+    for (uint32_t c = 0; c < a.ev_h && ok; c++) ok = b2_scalar(s, bytes, pos, ev[ei++]);
+    if (a.scheme == ZG_MULTIOPEN_SHPLONK) {  // y, v | h1 | u | h2
+        if (ok) {
+            ch[CH_SY] = b2_squeeze(s);
+            ch[CH_V] = b2_squeeze(s);
+        }
+        B2_POINTS(1);
+        if (ok) ch[CH_U] = b2_squeeze(s);
+        B2_POINTS(1);
+    } else {
+        if (ok) ch[CH_V] = b2_squeeze(s);
+        B2_POINTS(a.nsets);
+        if (ok) ch[CH_U] = b2_squeeze(s);
+    }
+#undef B2_POINTS
+    a.status[b] = !ok ? ST_MALFORMED : a.b2_len != a.len[b] ? ST_TRAILING : ST_OK;
+}
 // One wave per proof, every lane running the same code on the same data (identical stores), so the per-proof work runs
 // in uniform control flow.  63 of the 64 lanes are redundant; the layout is kept because the one-lane-per-proof form of
 // these two kernels gave wrong field products on the device (the same bodies are right on the host), for a reason not
@@ -236,6 +322,10 @@ __host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
 __global__ __launch_bounds__(64) void verify_replay(VArgs a) {
     const uint32_t b = blockIdx.x;
     if (b < a.count) replay_one(a, b);
+}
+__global__ __launch_bounds__(64) void verify_replay_b2(VArgs a) {
+    const uint32_t b = blockIdx.x;
+    if (b < a.count) replay_one_b2(a, b);
 }
 
 // in-place inversion of x[0..m) (zeros stay zero) with one field inversion; pre = m scratch elements
@@ -538,6 +628,7 @@ struct zg_verifier {
     // what the query table of a proof of NC circuits is built from, and the tables made so far (by NC)
     std::vector<zg_query> advice_queries, fixed_queries;
     int scheme = ZG_MULTIOPEN_GWC;  // zg_verifier_set_multiopen
+    int transcript = ZG_TRANSCRIPT_EVM;  // zg_verifier_set_transcript
     struct Table {
         const VQuery* oq = nullptr;
         uint32_t n_oq = 0;
@@ -545,8 +636,12 @@ struct zg_verifier {
         uint32_t nS = 0, nT = 0, nF = 0;
         const uint32_t *s_first = nullptr, *s_mask = nullptr, *f_pt = nullptr;
         const Fe* t_wr = nullptr;
+        // Blake2b transcript: the byte offset of every point of a proof (a fixed layout of 32-byte items), its length
+        std::vector<uint32_t> pt_off;
+        uint64_t b2_len = 0;
     };
-    std::map<std::pair<uint32_t, int>, Table> tables;  // by (circuits, scheme)
+    std::map<std::array<int, 3>, Table> tables;  // by (transcript, scheme, circuits)
+    const Table* table = nullptr;                // the one in use (set_circuits)
     // batch buffers, grown on demand (cap: proofs; pts / ev / sc: elements, their size per proof follows NC)
     size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0, pts_cap = 0, ev_cap = 0, sc_cap = 0;
     std::vector<void*> batch;
@@ -595,6 +690,8 @@ int ensure(zg_verifier* v, size_t count, size_t bytes, size_t inst, size_t tmp) 
     ZG_TRY(grow(v, (uint64_t**)&a.len, count));
     ZG_TRY(grow(v, (Fe**)&a.inst, inst));
     ZG_TRY(grow(v, &a.pts, count * a.NP));
+    ZG_TRY(grow(v, &a.enc, count * a.NP * 32));
+    ZG_TRY(grow(v, &a.pvalid, count * a.NP));
     ZG_TRY(grow(v, &a.ev, count * a.NE));
     ZG_TRY(grow(v, &a.ch, count * CH_N));
     ZG_TRY(grow(v, &a.status, count));
@@ -678,9 +775,16 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
     a.nL = shplonk ? 1 : a.nsets;
     a.NP = a.PT_RAND + 1 + a.qpd + a.nW;
     a.NT = a.NP + a.nL + a.F + a.P + 1;
-    auto it = v->tables.find({NC, v->scheme});
+    const std::array<int, 3> table_key = {v->transcript, v->scheme, (int)NC};
+    auto it = v->tables.find(table_key);
     if (it == v->tables.end()) {
         zg_verifier::Table t;
+        if (v->transcript == ZG_TRANSCRIPT_BLAKE2B) {
+            // items in read order: the points up to and including the h pieces | ev_h evaluations | the multi-open's points
+            const uint32_t before = a.PT_RAND + 1 + a.qpd;
+            for (uint32_t pt = 0; pt < a.NP; pt++) t.pt_off.push_back(32 * (pt + (pt >= before ? a.ev_h : 0)));
+            t.b2_len = 32 * ((uint64_t)a.NP + a.ev_h);
+        }
         if (shplonk) {
             // construct_intermediate_sets over the same queries (`set` is the query's point so far): commitments by first
             // appearance -- a term index names one -- with the points they are opened at; rotation sets by equal point
@@ -756,9 +860,11 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
             for (int64_t r : set_rot) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
             ZG_TRY(upload(v, &a.set_wr, set_wr));
         }
-        it = v->tables.emplace(std::make_pair(NC, v->scheme), t).first;
+        it = v->tables.emplace(table_key, t).first;
     }
     const zg_verifier::Table& t = it->second;
+    v->table = &t;
+    a.b2_len = t.b2_len;
     a.oq = t.oq;
     a.n_oq = t.n_oq;  // (SHPLONK's table holds a repeated (commitment, point) pair once)
     a.nS = t.nS; a.nT = t.nT; a.nF = t.nF; a.nwork = t.nT + t.nS;
@@ -919,6 +1025,17 @@ int zg_verifier_set_multiopen(zg_verifier* v, int scheme) {
 
 int zg_verifier_multiopen(const zg_verifier* v) { return v ? v->scheme : ZG_MULTIOPEN_GWC; }
 
+int zg_verifier_set_transcript(zg_verifier* v, int transcript) {
+    ZG_REQUIRE(v, ZG_ERR_INVALID_ARG, "zg_verifier_set_transcript: null verifier");
+    ZG_REQUIRE(transcript == ZG_TRANSCRIPT_EVM || transcript == ZG_TRANSCRIPT_BLAKE2B, ZG_ERR_INVALID_ARG,
+               "zg_verifier_set_transcript: transcript %d", transcript);
+    ZG_ENTER(v->ctx);
+    v->transcript = transcript;
+    return ZG_OK;
+}
+
+int zg_verifier_transcript(const zg_verifier* v) { return v ? v->transcript : ZG_TRANSCRIPT_EVM; }
+
 int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const* proofs, const size_t* proof_lens,
                              const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
     return zg_verifier_verify_multi(v, count, 1, proofs, proof_lens, instance, instance_len, key, verdicts);
@@ -953,13 +1070,18 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
             len[b] = proof_lens[b];
             total += proof_lens[b];
         }
+        const bool blake2b = v->transcript == ZG_TRANSCRIPT_BLAKE2B;
         std::vector<uint8_t> bytes(total ? total : 1);
+        // Blake2b: every proof's commitments side by side for the decompression kernel (a short proof: zeros, never read)
+        std::vector<uint8_t> enc(blake2b ? count * a.NP * 32 : 0);
         std::vector<Fe> inst(count * per_inst);
         std::vector<Fe> rb(count);
         uint32_t kw[8];
         std::memcpy(kw, key, 32);
         for (size_t b = 0; b < count; b++) {
             if (proof_lens[b]) std::memcpy(bytes.data() + off[b], proofs[b], proof_lens[b]);
+            if (blake2b && proof_lens[b] >= a.b2_len)
+                for (uint32_t pt = 0; pt < a.NP; pt++) std::memcpy(&enc[(b * a.NP + pt) * 32], proofs[b] + v->table->pt_off[pt], 32);
             for (size_t c = 0; c < circuits && per_inst; c++)
                 std::memcpy(inst.data() + b * per_inst + c * one_inst, instance[b * circuits + c], one_inst * sizeof(Fe));
             rb[b] = Fr::to_raw(rand_fr_host(kw, TAG_VERIFY_BATCH, b));
@@ -977,7 +1099,13 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
         ZG_HIP(hipMemcpyAsync((void*)a.len, len.data(), count * 8, hipMemcpyHostToDevice, st));
         if (per_inst) ZG_HIP(hipMemcpyAsync((void*)a.inst, inst.data(), inst.size() * sizeof(Fe), hipMemcpyHostToDevice, st));
         ZG_HIP(hipMemcpyAsync((void*)a.rb, rb.data(), count * sizeof(Fe), hipMemcpyHostToDevice, st));
-        ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay, dim3((uint32_t)count), dim3(64), 0, a);
+        if (blake2b) {
+            ZG_HIP(hipMemcpyAsync(a.enc, enc.data(), enc.size(), hipMemcpyHostToDevice, st));
+            ZG_TRY(g1_decompress_dev(ctx, a.enc, count * a.NP, a.pts, a.pvalid));
+            ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay_b2, dim3((uint32_t)count), dim3(64), 0, a);
+        } else {
+            ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay, dim3((uint32_t)count), dim3(64), 0, a);
+        }
         ZG_LAUNCH(ctx, "verify_scalars", (double)count * a.NE * 32, verify_scalars, dim3((uint32_t)count), dim3(64), 0, a);
         ZG_LAUNCH(ctx, "verify_terms", (double)count * a.NT * 96, verify_terms, dim3((uint32_t)count), dim3(TERMS_WG), 0, a);
         ZG_LAUNCH(ctx, "verify_fold", (double)count * 256, verify_fold, dim3(1), dim3(TERMS_WG), 0, a);

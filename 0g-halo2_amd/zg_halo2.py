@@ -60,6 +60,9 @@ def load() -> ctypes.CDLL:
     lib.zg_msm_var_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]
     lib.zg_g1_mul_each.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.zg_g1_mul_each_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.zg_g1_compress.argtypes = [c_void_p, c_size_t, c_void_p]
+    lib.zg_g1_decompress.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.zg_g1_decompress_dev.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     _lib = lib
     return lib
 
@@ -96,10 +99,24 @@ ABI_SYMBOLS = [
     "zg_g1_mul_each", "zg_g1_mul_each_dev", "zg_params_g2", "zg_g2_mul", "zg_params_update", "zg_params_update_dev",
     "zg_params_check_update",
     "zg_prover_set_multiopen", "zg_prover_multiopen", "zg_verifier_set_multiopen", "zg_verifier_multiopen",
+    "zg_prover_set_transcript", "zg_prover_transcript", "zg_verifier_set_transcript", "zg_verifier_transcript",
+    "zg_g1_compress", "zg_g1_decompress", "zg_g1_decompress_dev",
 ]
 
 # zg_prover_set_multiopen / zg_verifier_set_multiopen: the multi-open argument a proof ends with
 MULTIOPEN_GWC, MULTIOPEN_SHPLONK = 0, 1
+# zg_prover_set_transcript / zg_verifier_set_transcript: snark-verifier's EvmTranscript (Keccak-256, uncompressed points) or
+# halo2's own Blake2bWrite / Blake2bRead with Challenge255 (32-byte compressed points)
+TRANSCRIPT_EVM, TRANSCRIPT_BLAKE2B = 0, 1
+
+
+def g1_compress(points: np.ndarray) -> np.ndarray:
+    """zg_g1_compress (host, no device): uint64[n, 8] affine points in Montgomery form -> uint8[n, 32], the GroupEncoding
+    of each ((0,0) -> 32 zero bytes); no validation."""
+    points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    out = np.zeros((points.shape[0], 32), np.uint8)
+    _check(load().zg_g1_compress(_ptr(points), c_size_t(points.shape[0]), _ptr(out)))
+    return out
 
 # zg_params_check: bits of `failed`
 SRS_G1_MALFORMED, SRS_G1_IDENTITY, SRS_G2, SRS_POWERS, SRS_LAGRANGE = 1, 2, 4, 8, 16
@@ -424,6 +441,34 @@ class Ctx:
         out = np.zeros_like(points)
         _check(self.lib.zg_g1_mul_each(self.h, _ptr(points), _ptr(scalars), c_size_t(points.shape[0]), _ptr(out)))
         return out
+
+    def g1_decompress(self, encodings):
+        """zg_g1_decompress: GroupEncoding::from_bytes for n encodings -> (points, valid).  A host array uint8[n, 32] (or
+        n * 32 bytes) gives numpy arrays uint64[n, 8] / uint8[n]; a torch tensor of n * 32 uint8 on the device gives device
+        tensors int64[n, 8] / uint8[n] through zg_g1_decompress_dev (asynchronous on the context stream; the tensors are
+        fenced here on both sides).  An invalid encoding: (0,0) and valid 0."""
+        if hasattr(encodings, "data_ptr"):
+            import torch
+
+            enc = encodings.contiguous().view(torch.uint8).reshape(-1, 32)
+            n = enc.shape[0]
+            out = torch.zeros((n, 8), dtype=torch.int64, device=enc.device)
+            valid = torch.zeros((n,), dtype=torch.uint8, device=enc.device)
+            torch.cuda.synchronize()
+            _check(self.lib.zg_g1_decompress_dev(self.h, c_void_p(enc.data_ptr() if n else 0), c_size_t(n),
+                                                 c_void_p(out.data_ptr() if n else 0), c_void_p(valid.data_ptr() if n else 0)))
+            self.sync()
+            return out, valid
+        enc = np.ascontiguousarray(np.frombuffer(encodings, np.uint8) if isinstance(encodings, (bytes, bytearray)) else encodings,
+                                   dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((enc.shape[0], 8), np.uint64)
+        valid = np.zeros(enc.shape[0], np.uint8)
+        _check(self.lib.zg_g1_decompress(self.h, _ptr(enc), c_size_t(enc.shape[0]), _ptr(out), _ptr(valid)))
+        return out, valid
+
+    def g1_decompress_dev(self, d_in: int, n: int, d_out: int, d_valid: int):
+        """zg_g1_decompress_dev: device addresses (n * 32 B in, n * 64 B and n bytes out; no aliasing); asynchronous."""
+        _check(self.lib.zg_g1_decompress_dev(self.h, c_void_p(d_in), c_size_t(n), c_void_p(d_out), c_void_p(d_valid)))
 
     def g1_mul_each_dev(self, d_points: int, d_scalars: int, n: int, d_out: int):
         """zg_g1_mul_each_dev: device addresses (d_out may be d_points); asynchronous on the context stream."""
@@ -791,6 +836,17 @@ class Prover:
         self.ctx.lib.zg_prover_multiopen.argtypes = [c_void_p]
         return int(self.ctx.lib.zg_prover_multiopen(self.h))
 
+    def set_transcript(self, transcript: int):
+        """zg_prover_set_transcript: TRANSCRIPT_EVM (default) or TRANSCRIPT_BLAKE2B; the size bounds follow it."""
+        self.ctx.lib.zg_prover_set_transcript.argtypes = [c_void_p, ctypes.c_int]
+        _check(self.ctx.lib.zg_prover_set_transcript(self.h, ctypes.c_int(transcript)))
+        self.proof_cap = int(self.ctx.lib.zg_prover_proof_size(self.h))
+
+    @property
+    def transcript(self) -> int:
+        self.ctx.lib.zg_prover_transcript.argtypes = [c_void_p]
+        return int(self.ctx.lib.zg_prover_transcript(self.h))
+
     @property
     def batch(self) -> int:
         return int(self.ctx.lib.zg_prover_batch(self.h))
@@ -1157,6 +1213,16 @@ class Verifier:
     def multiopen(self) -> int:
         self.ctx.lib.zg_verifier_multiopen.argtypes = [c_void_p]
         return int(self.ctx.lib.zg_verifier_multiopen(self.h))
+
+    def set_transcript(self, transcript: int):
+        """zg_verifier_set_transcript: which transcript the proofs were written into (TRANSCRIPT_EVM / TRANSCRIPT_BLAKE2B)."""
+        self.ctx.lib.zg_verifier_set_transcript.argtypes = [c_void_p, ctypes.c_int]
+        _check(self.ctx.lib.zg_verifier_set_transcript(self.h, ctypes.c_int(transcript)))
+
+    @property
+    def transcript(self) -> int:
+        self.ctx.lib.zg_verifier_transcript.argtypes = [c_void_p]
+        return int(self.ctx.lib.zg_verifier_transcript(self.h))
 
     def verify(self, proofs, instances, key) -> list:
         """Verdict per proof: 1 accepted, 0 rejected, < 0 malformed.  instances[b]: uint64[n_instance, len, 4];

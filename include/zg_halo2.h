@@ -306,6 +306,26 @@ int zg_params_check(zg_ctx *ctx, uint32_t k, const zg_g1_affine *g,
 int zg_g1_mul_each(zg_ctx *ctx, const zg_g1_affine *points, const zg_fr *scalars, size_t n, zg_g1_affine *out);
 int zg_g1_mul_each_dev(zg_ctx *ctx, const void *d_points, const void *d_scalars, size_t n, void *d_out);
 
+/* The 32-byte GroupEncoding of G1 points (halo2curves 0.3.3 G1Affine::to_bytes / from_bytes; what halo2's own transcript
+ * writes into a proof, ZG_TRANSCRIPT_BLAKE2B below).  As known from the published sources -- the crates were not at hand;
+ * DESIGN.md section 17 lists what remains to be verified against them:
+ *   to_bytes    the identity is 32 zero bytes; otherwise x.to_repr() (32 little-endian bytes of the canonical integer)
+ *               with (y.to_repr()[0] & 1) << 7 OR-ed into byte 31; bit 6 of byte 31 is always 0.
+ *   from_bytes  bit 7 of byte 31 is the sign and is cleared; the remaining 32 bytes must be a canonical x < q (a set bit 6
+ *               therefore fails here); x = 0 with sign 0 is the identity; otherwise y = sqrt(x^3 + 3) -- the encoding is
+ *               invalid when there is none -- negated when its low bit differs from the sign.  q = 3 (mod 4): the root is
+ *               t^((q+1)/4), checked by squaring; 3 is a non-residue, so x = 0 with the sign set is invalid.
+ * zg_g1_compress is to_bytes for n points on the host (no device); it does not validate: a point off the curve gives bytes
+ * that do not decompress to it.  zg_g1_decompress is from_bytes for n encodings on the GPU, one lane per point: out[i] is
+ * the affine point in Montgomery form and valid[i] = 1 (the identity encoding: (0,0), valid 1); an invalid encoding gives
+ * (0,0) with valid[i] = 0, disturbs no neighbour and is not an error of the call.  n = 0 is ZG_OK and launches nothing; a
+ * null pointer with n > 0 is ZG_ERR_INVALID_ARG; n >= 2^28 is ZG_ERR_UNSUPPORTED.  The _dev form takes device pointers
+ * (d_in n * 32 B, d_out n * 64 B, d_valid n bytes; d_out may not alias d_in) and is asynchronous on the context stream. */
+typedef struct { uint8_t b[32]; } zg_g1_compressed;
+int zg_g1_compress(const zg_g1_affine *points, size_t n, zg_g1_compressed *out);
+int zg_g1_decompress(zg_ctx *ctx, const zg_g1_compressed *in, size_t n, zg_g1_affine *out, uint8_t *valid);
+int zg_g1_decompress_dev(zg_ctx *ctx, const void *d_in, size_t n, void *d_out, void *d_valid);
+
 /* The G2 half of ParamsKZG::new (ParamsKZG::setup: g2 = G2Affine::generator(), s_g2 = g2 * s), on the host: with
  * zg_params_new it makes a complete ParamsKZG, which zg_verifier_create and an SRS file need.  s: Montgomery, limbs
  * below r (else ZG_ERR_INVALID_ARG); s = 0 gives s_g2 = (0,0). */
@@ -638,6 +658,29 @@ int zg_prover_set_overlap(zg_prover *p, int enable);
 enum { ZG_MULTIOPEN_GWC = 0, ZG_MULTIOPEN_SHPLONK = 1 };
 int zg_prover_set_multiopen(zg_prover *p, int scheme);
 int zg_prover_multiopen(const zg_prover *p);
+/* The transcript a prover writes its proofs into.  ZG_TRANSCRIPT_EVM (default): snark-verifier's EvmTranscript, Keccak-256,
+ * a commitment as 64 uncompressed big-endian bytes.  ZG_TRANSCRIPT_BLAKE2B: halo2's own Blake2bWrite with Challenge255
+ * (halo2_proofs v2023_04_20 src/transcript/blake2b.rs), a commitment as its 32-byte GroupEncoding (zg_g1_compress): a
+ * proof is 32 bytes per commitment shorter.  As known from the published sources -- the crates were not at hand, and no
+ * interoperability is claimed beyond this description; DESIGN.md section 17 lists what remains to be verified:
+ *   hash state         BLAKE2b, 64-byte digest, no key, personalisation the 16 bytes "Halo2-Transcript"; never reset:
+ *                      everything since init is one running hash
+ *   common_scalar(s)   absorb the byte 0x02, then s.to_repr(): 32 bytes, little-endian, the canonical integer;
+ *                      write_scalar also appends those 32 bytes to the proof
+ *   common_point(P)    absorb 0x01, then x.to_repr() and y.to_repr(), 32 little-endian bytes each (the uncompressed
+ *                      pair); the identity is refused
+ *   write_point        appends the 32-byte compressed form P.to_bytes() to the proof
+ *   squeeze_challenge  absorb 0x00, finalise a clone of the state, take the 64-byte digest as a little-endian integer and
+ *                      reduce it modulo r (Challenge255::new, from_uniform_bytes); the live state keeps the 0x00 byte
+ * The order of writes and squeezes does not depend on the transcript: it is the one documented for GWC and SHPLONK, for
+ * one or several circuits.  A property of the prover object, like zg_prover_set_multiopen: it governs every prove entry
+ * (zg_prover_prove, _dev, _batch, _batch_dev, _images, _multi, _multi_dev, _images_multi) and the two proof-size bounds,
+ * which take 32 bytes per point under Blake2b; it combines with both multi-open schemes, both scheduling forms and
+ * point-range shards (host state on every rank); a fork starts with its parent's value.  It allocates nothing on the
+ * device.  With the default every byte and bound is what it was.  Any other value: ZG_ERR_INVALID_ARG, nothing changes. */
+enum { ZG_TRANSCRIPT_EVM = 0, ZG_TRANSCRIPT_BLAKE2B = 1 };
+int zg_prover_set_transcript(zg_prover *p, int transcript);
+int zg_prover_transcript(const zg_prover *p);
 /* Builds the digit tables (zg_bases_enable_digit_table) of the prover's three base sets -- ParamsKZG::g, ::g_lagrange and
  * the running sums of g_lagrange -- which a LONE proof (zg_prover_set_overlap(p, 1)) then uses instead of Pippenger buckets:
  * 2.9 -> 2.2 ms per create_proof at k = 14.  Footprint: 3 x ceil(255 / c) * 2^(c-1) * n * 64 B -- 78 GB at n = 2^14 (c = 11),
@@ -887,6 +930,16 @@ int zg_verifier_verify_multi(zg_verifier *v, size_t count, size_t circuits, cons
  * verification call.  Any other value: ZG_ERR_INVALID_ARG, nothing changes. */
 int zg_verifier_set_multiopen(zg_verifier *v, int scheme);
 int zg_verifier_multiopen(const zg_verifier *v);
+/* Which transcript the proofs handed to zg_verifier_verify_batch / _multi were written into (ZG_TRANSCRIPT_*, default EVM;
+ * the format: zg_prover_set_transcript).  Under ZG_TRANSCRIPT_BLAKE2B a proof is a fixed layout of 32-byte items, so a
+ * short proof is malformed before anything is read; every commitment is decompressed by the kernel of zg_g1_decompress
+ * (one lane per point) ahead of the replay, which absorbs and squeezes with BLAKE2b on the device.  Verdict classes stay:
+ * negative = short, an x not below q (bit 6 included), an x with no point, the identity encoding, a scalar not below r;
+ * 0 = a failing equation or trailing bytes; malformed wins over trailing; each verdict is the one a lone verification
+ * gives.  Query and offset tables are kept per (transcript, scheme, circuits).  Any other value: ZG_ERR_INVALID_ARG,
+ * nothing changes. */
+int zg_verifier_set_transcript(zg_verifier *v, int transcript);
+int zg_verifier_transcript(const zg_verifier *v);
 /* Host helper (no device): *result = 1 iff prod_i e(p[i], q[i]) = 1 in GT (BN254 optimal ate pairing); identity
  * points contribute 1.  The points are taken to be in G1 and G2.  bn256::multi_miller_loop + final_exponentiation. */
 int zg_pairing_check(const zg_g1_affine *p, const zg_g2_affine *q, size_t n, int *result);
