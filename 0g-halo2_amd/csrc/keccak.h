@@ -1,5 +1,6 @@
-// Keccak-f[1600], Keccak-256 and EvmTranscript's challenge rule, shared by the two sides of the transcript format: the
-// host writer (transcript.h, used by prove_batch.hip) and the device reader that replays a proof (verify.hip).
+// Keccak-f[1600], Keccak-256, EvmTranscript's challenge rule and its streaming sponge, shared by the two sides of the
+// transcript format: the host writer (transcript.h, used by prove_batch.hip) and the device reader that replays a proof
+// (verify.hip, which holds no hash code of its own).
 #pragma once
 
 #include <cstring>
@@ -91,6 +92,42 @@ __host__ __device__ inline Fe challenge_from_hash(const uint8_t h[32]) {
         for (int i = 0; i < 8; i++) v.l[i] = t[i];
     }
     return Fr::from_raw(v);
+}
+
+// EvmTranscript's hash state for a reader that streams: the bytes absorbed since the last squeeze go into the sponge as
+// they come (transcript.h's writer keeps them in a buffer and hashes it whole)
+struct Sponge {
+    uint64_t st[25];
+    uint32_t pos, len;
+};
+__host__ __device__ inline void sp_reset(Sponge& s) {
+    for (int i = 0; i < 25; i++) s.st[i] = 0;
+    s.pos = 0;
+    s.len = 0;
+}
+__host__ __device__ inline void sp_byte(Sponge& s, uint32_t b) {
+    s.st[s.pos >> 3] ^= (uint64_t)(b & 0xff) << (8 * (s.pos & 7));
+    s.len++;
+    if (++s.pos == KECCAK_RATE) {
+        keccak_f1600(s.st);
+        s.pos = 0;
+    }
+}
+// 32 big-endian bytes of a canonical integer (8 LE u32 limbs)
+__host__ __device__ inline void sp_int(Sponge& s, const Fe& raw) {
+    for (int k = 0; k < 32; k++) sp_byte(s, raw.l[(31 - k) >> 2] >> (8 * ((31 - k) & 3)));
+}
+// the squeeze of transcript.h's EvmTranscript, on the streamed sponge; the state becomes the hash
+__host__ __device__ inline Fe sp_squeeze(Sponge& s) {
+    if (squeeze_appends_one(s.len)) sp_byte(s, 1);
+    s.st[s.pos >> 3] ^= 0x01ull << (8 * (s.pos & 7));
+    s.st[KECCAK_RATE / 8 - 1] ^= 0x80ull << 56;
+    keccak_f1600(s.st);
+    uint8_t h[32];
+    for (int k = 0; k < 32; k++) h[k] = (uint8_t)(s.st[k >> 3] >> (8 * (k & 7)));
+    sp_reset(s);
+    for (int k = 0; k < 32; k++) sp_byte(s, h[k]);
+    return challenge_from_hash(h);
 }
 
 }  // namespace zg

@@ -192,9 +192,11 @@ struct TickLog {
 //   commit_advice      advice commitments                                   -> theta
 //   commit_permuted    lookup::commit_permuted (+ the random polynomial)    -> beta, gamma
 //   commit_products    permutation::commit, lookup::commit_product          -> y
+//   opening_plan       (no device work) which polynomial is evaluated and opened where: proof_layout.h's order of the
+//                      proof in this prover's list formats, made once per prover, argument and circuits in a proof
 //   quotient           evaluate_h, h(X) in pieces, their commitments        -> x
 //   evaluations        eval_polynomial at x omega^rot                       -> v
-//   openings           ProverGWC::create_proof
+//   openings           ProverGWC::create_proof, or ProverSHPLONK's (shplonk_*)
 //   finish             proof bytes and statuses out
 // A nonzero return leaves p->in_flight set: the next batch drains the streams before it reuses the slots.
 struct ProveBatch {
@@ -247,31 +249,14 @@ struct ProveBatch {
     Cols base_cols;
     std::vector<Jac> random_commit;
     bool have_random = false;
-    struct Q1 { uint32_t poly, slot; bool shared; uint32_t at; };  // (multi: taken once, from slot 0; `at`: its place in a slot's row of evaluations)
-    std::vector<int32_t> rots;  // distinct opening points, in any order (the powers table is indexed by slot)
-    std::vector<Q1> evq;
-    size_t e_fixed = 0, e_random = 0, e_sigma = 0, e_pz = 0, e_lk = 0, e_written = 0, e_h = 0;
-    uint32_t npoints = 0;
+    const OpenPlan* plan = nullptr;  // which polynomial is evaluated and opened where (opening_plan())
+    uint32_t npoints = 0;            // distinct opening points: ProofConst::points slots, GWC's point sets, SHPLONK's T
     uint32_t* d_hlist = nullptr;
     const Fe* ev_all = nullptr;
     uint32_t* h_err = nullptr;  // the lookups' error words on the host
     uint32_t prod_per = 0;      // commitments per proof of the products phase (the random polynomial rides there without lookups)
-    uint32_t nsets = 0;         // opening point sets: list of set s at lists[s * 512 ..], its evaluation indices in list order
-    std::vector<uint32_t> lists, counts, set_slot, firsts;  // (multi: the lists follow each other, set s from firsts[s])
-    struct EvRef { uint32_t circuit; size_t ev; };          // an evaluation of the proof: evq index `ev` of a circuit (multi)
-    std::vector<std::vector<EvRef>> set_evs;
-    uint32_t n_per = 0;  // multi: evaluations per circuit; the shared ones follow them in slot 0's row
-    // ---- SHPLONK (zg_prover_set_multiopen): construct_intermediate_sets' result for the circuit --
-    // commitments in first-appearance order, grouped by the set of points they are opened at -- and per proof what the
-    // second half needs of the first
+    // ---- SHPLONK (zg_prover_set_multiopen): per proof what the second half needs of the first
     const bool shplonk;
-    struct OQ { uint32_t poly, slot; size_t ev; uint32_t circuit; };  // an opening query: polynomial, point slot, its evaluation
-    struct SCom { uint32_t entry; std::vector<EvRef> evs; };           // a commitment (slot << 16 | polynomial); evs[i]: at set point i
-    struct SSet { uint32_t mask; std::vector<uint32_t> slots; std::vector<SCom> coms; };
-    std::vector<SSet> ssets;
-    std::vector<uint32_t> tslots;                 // T: every point slot a query names
-    std::vector<uint32_t> sh_first, sh_count;     // the numerators' lists, one per point of T; then L's (index tslots.size())
-    size_t sh_nlist = 0, sh_ncoef = 0;            // entries of all lists; coefficients per proof (both halves use [0, ..))
     struct SProof { Fe y, v; std::vector<std::vector<Fe>> R; };  // R[i]: sum_j y^j R_ij(X), coefficients
     std::vector<SProof> sproof;
     // ---- the gate (run())
@@ -417,11 +402,10 @@ struct ProveBatch {
             ZG_TRY(products_terms_queue());
             ZG_TRY(products_queue());
             ZG_TRY(products_absorb());
-            ZG_TRY(evaluation_lists());
+            ZG_TRY(opening_plan());
             ZG_TRY(quotient_queue());
             ZG_TRY(quotient_absorb());
             ZG_TRY(evaluations_queue());
-            ZG_TRY(openings_lists());
             ZG_TRY(evaluations_absorb());
             ZG_TRY(openings_queue());
         } else {
@@ -432,14 +416,13 @@ struct ProveBatch {
             ZG_TRY(products_terms_queue());  // behind beta, gamma
             ZG_TRY(permuted_absorb());
             ZG_TRY(products_queue());  // (starts with the host's share of the grand products: never queued ahead)
-            ZG_TRY(evaluation_lists());
+            ZG_TRY(opening_plan());
             ZG_TRY(arm());
             ZG_TRY(quotient_queue());    // behind y
             ZG_TRY(products_absorb());
             ZG_TRY(arm());
             ZG_TRY(evaluations_queue());  // behind x
             ZG_TRY(quotient_absorb());
-            ZG_TRY(openings_lists());
             ZG_TRY(arm());
             ZG_TRY(openings_queue());    // behind v
             ZG_TRY(evaluations_absorb());
@@ -823,7 +806,7 @@ struct ProveBatch {
         ZG_TICK("h: queued");
         return ZG_OK;
     }
-    // (h's commitments, then x and the opening points: needs evaluation_lists())
+    // (h's commitments, then x and the opening points: needs opening_plan())
     int quotient_absorb() {
         ZG_TRY(wait_points(p, (size_t)nq * Q, pts, W_QUOTIENT));
         ZG_TICK("h: points on the host");
@@ -834,7 +817,7 @@ struct ProveBatch {
             ProofConst& c = p->hpc[b];
             if (b < ntr) x = tr[b].squeeze();
             c.xn = Fr::pow_u64(x, n);
-            for (uint32_t i = 0; i < npoints; i++) c.points[i] = rotate_omega(pk, x, rots[i]);
+            for (uint32_t i = 0; i < npoints; i++) c.points[i] = rotate_omega(pk, x, (int32_t)plan->lay.rotations[i]);
         }
         ZG_TICK("x");
         ZG_TRY(publish());
@@ -843,54 +826,102 @@ struct ProveBatch {
         return ZG_OK;
     }
 
-    // ---- evaluations: which polynomial is evaluated at which opening point (circuit only)
-    int evaluation_lists() {
-        // distinct opening points, in any order (the powers table is indexed by slot)
-        rots = {0, 1, -1, -(int32_t)(bf + 1)};
-        auto rot_slot = [&](int32_t r) -> uint32_t {
-            for (size_t i = 0; i < rots.size(); i++)
-                if (rots[i] == r) return (uint32_t)i;
-            rots.push_back(r);
-            return (uint32_t)rots.size() - 1;
+    // ---- which polynomial is evaluated and opened where: proof_layout.h states it, the three functions below put it into
+    // the device list formats (OpenPlan), once per prover, argument and number of circuits in a proof
+    int opening_plan() {
+        ZG_REQUIRE(!shplonk || p->sh_h1 != nullptr, ZG_ERR_INVALID_ARG, "zg_prover_prove: no SHPLONK buffers (zg_prover_set_multiopen)");
+        const std::pair<int, uint32_t> key(p->multiopen, multi ? nb : 1u);
+        auto it = p->plans.find(key);
+        if (it == p->plans.end()) {
+            OpenPlan pl;
+            pl.lay = build_layout(proof_shape(pk), key.second, shplonk);
+            ZG_TRY(plan_evaluations(pl));
+            ZG_TRY(shplonk ? plan_shplonk(pl) : plan_gwc(pl));
+            it = p->plans.emplace(key, std::move(pl)).first;
+        }
+        plan = &it->second;
+        npoints = (uint32_t)plan->lay.rotations.size();
+        ZG_REQUIRE(!shplonk || (size_t)ntr * plan->sh_ncoef <= p->sh_terms + p->cap, ZG_ERR_UNSUPPORTED,
+                   "zg_prover_prove: %zu opening queries (room for %zu)", plan->lay.queries.size(), p->sh_terms);
+        return ZG_OK;
+    }
+    // the prover's handles: a commitment's polynomial (with its circuit's slot above it in a list entry)
+    uint32_t poly_of(Family fam, uint32_t index) const {
+        const uint32_t base[] = {p->ix_adv, p->ix_perm, p->ix_pz, p->ix_lz, p->ix_random, 0, 0, p->ix_fixed, p->ix_sigma, p->ix_hpoly};
+        return base[fam] + index;
+    }
+    uint32_t entry_of(Family fam, uint32_t circuit, uint32_t index) const { return circuit << 16 | poly_of(fam, index); }
+    int plan_evaluations(OpenPlan& pl) const {
+        const ProofLayout& l = pl.lay;
+        const uint32_t E = (uint32_t)l.evals.size();
+        auto once = [&](const ProofLayout::Query& q) { return l.N > 1 && (q.fam == FIXED || q.fam == RANDOM || q.fam == SIGMA || q.fam == H); };
+        uint32_t n_once = 0;
+        for (const ProofLayout::Query& q : l.evals) n_once += once(q) ? 1 : 0;
+        pl.n_per = (E - n_once) / l.N;
+        pl.n_row = pl.n_per + n_once;
+        ZG_REQUIRE(l.rotations.size() <= p->max_points, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u distinct rotations are queried (max %u)",
+                   (uint32_t)l.rotations.size(), p->max_points);
+        ZG_REQUIRE(pl.n_row <= p->max_evals, ZG_ERR_UNSUPPORTED, "zg_prover_prove: too many evaluations");
+        pl.idx.assign(2 * (size_t)pl.n_row, 0);
+        std::vector<uint32_t> at_per(l.N, 0);
+        uint32_t at_once = pl.n_per;
+        for (const ProofLayout::Query& q : l.evals) {  // (transcript order)
+            pl.ev_row.push_back(once(q) ? 0 : q.circuit);
+            pl.ev_at.push_back(once(q) ? at_once++ : at_per[q.circuit]++);
+            pl.idx[pl.ev_at.back()] = poly_of(q.fam, q.index);
+            pl.idx[pl.n_row + pl.ev_at.back()] = q.point;
+        }
+        std::vector<uint32_t> seen(pl.idx.begin(), pl.idx.begin() + pl.n_row);
+        std::sort(seen.begin(), seen.end());
+        pl.distinct_polys = (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+        for (uint32_t i = 0; i < l.rotations.size(); i++) pl.slots.push_back(i);
+        return ZG_OK;
+    }
+    // ProverGWC::create_proof's point sets: one per opening point, its queries in order.  A proof of several circuits
+    // lists (circuit, polynomial) pairs, each list as long as it has to be (N = 32 of the zero_g circuit puts about a
+    // thousand polynomials at x); a lone circuit's lists are 512 entries apart
+    int plan_gwc(OpenPlan& pl) const {
+        const ProofLayout& l = pl.lay;
+        const bool several = l.N > 1;
+        ZG_REQUIRE(!several || (l.queries.size() <= p->mlists_cap && p->nsh + p->npp <= 0x10000u), ZG_ERR_UNSUPPORTED,
+                   "zg_prover_prove_multi: %zu opening queries (room for %zu)", l.queries.size(), p->mlists_cap);
+        for (const std::vector<uint32_t>& set : l.at) {
+            ZG_REQUIRE(several || set.size() <= 512, ZG_ERR_UNSUPPORTED, "zg_prover_prove: more than 512 polynomials opened at one point");
+            pl.firsts.push_back(several ? (uint32_t)pl.lists.size() : 512 * (uint32_t)pl.counts.size());
+            pl.lists.resize(pl.firsts.back(), 0);
+            for (uint32_t qi : set) pl.lists.push_back(entry_of(l.queries[qi].fam, l.queries[qi].circuit, l.queries[qi].index));
+            pl.counts.push_back((uint32_t)set.size());
+        }
+        if (!several) pl.lists.resize(512 * l.at.size(), 0);
+        ZG_REQUIRE(l.at.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u opening points", (uint32_t)l.at.size());
+        return ZG_OK;
+    }
+    // ProverSHPLONK::create_proof (v2023_04_20 src/poly/kzg/multiopen/shplonk/prover.rs): the lists of
+    // both combinations from the layout's rotation sets -- per point r of T the commitments of every set that holds r,
+    // and for L every commitment once
+    int plan_shplonk(OpenPlan& pl) const {
+        const ProofLayout& l = pl.lay;
+        ZG_REQUIRE(p->nsh + p->npp <= 0x10000u, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u polynomials", p->nsh + p->npp);
+        ZG_REQUIRE(l.rsets.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu rotation sets (max %u)", l.rsets.size(), HC_MAX_SETS);
+        ZG_REQUIRE(l.rotations.size() <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu opening points", l.rotations.size());
+        for (const ProofLayout::Com& c : l.coms) pl.com_entry.push_back(entry_of(c.fam, c.circuit, c.index));
+        for (const ProofLayout::RotationSet& s : l.rsets) {
+            pl.set_mask.push_back(0);
+            for (uint32_t r : s.points) pl.set_mask.back() |= 1u << r;
+        }
+        auto list_sets = [&](uint32_t mask) {  // the commitments of the sets that hold one of `mask`'s points, as one list
+            pl.firsts.push_back((uint32_t)pl.lists.size());
+            for (size_t i = 0; i < l.rsets.size(); i++)
+                if (pl.set_mask[i] & mask)
+                    for (uint32_t c : l.rsets[i].coms) pl.lists.push_back(pl.com_entry[c]);
+            pl.counts.push_back((uint32_t)pl.lists.size() - pl.firsts.back());
         };
-        evq.clear();  // evaluations in transcript order, then h_poly at x
-        for (auto& q : pk.advice_queries) evq.push_back({p->ix_adv + q.column, rot_slot(q.rotation)});
-        e_fixed = evq.size();
-        for (auto& q : pk.fixed_queries) evq.push_back({p->ix_fixed + q.column, rot_slot(q.rotation), true});
-        e_random = evq.size();
-        evq.push_back({p->ix_random, 0, true});
-        e_sigma = evq.size();
-        for (uint32_t c = 0; c < P; c++) evq.push_back({p->ix_sigma + c, 0, true});
-        e_pz = evq.size();
-        for (uint32_t s = 0; s < S; s++) {
-            evq.push_back({p->ix_pz + s, 0});
-            evq.push_back({p->ix_pz + s, 1});
-            if (s + 1 < S) evq.push_back({p->ix_pz + s, 3});
-        }
-        e_lk = evq.size();
-        for (uint32_t l = 0; l < NL; l++) {
-            evq.push_back({p->ix_lz + l, 0});            // z(x)
-            evq.push_back({p->ix_lz + l, 1});            // z(omega x)
-            evq.push_back({p->ix_perm + 2 * l, 0});      // a'(x)
-            evq.push_back({p->ix_perm + 2 * l, 2});      // a'(omega^-1 x)
-            evq.push_back({p->ix_perm + 2 * l + 1, 0});  // s'(x)
-        }
-        e_written = evq.size();
-        evq.push_back({p->ix_hpoly, 0, true});
-        e_h = e_written;
-        // where an evaluation lands in a slot's row: in transcript order -- or, multi, the per-circuit ones first (every
-        // slot's row) and behind them, in slot 0's row only, what the proof holds once: fixed, random, sigma, h
-        n_per = 0;
-        for (Q1& q : evq) n_per += multi && q.shared ? 0 : 1;
-        {
-            uint32_t at_per = 0, at_once = n_per;
-            for (Q1& q : evq) q.at = multi && q.shared ? at_once++ : at_per++;
-        }
-        npoints = (uint32_t)rots.size();
-        ZG_REQUIRE(npoints <= p->max_points, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u distinct rotations are queried (max %u)", npoints,
-                   p->max_points);
-        ZG_REQUIRE(evq.size() <= p->max_evals, ZG_ERR_UNSUPPORTED, "zg_prover_prove: too many evaluations");
-
+        for (uint32_t r = 0; r < l.rotations.size(); r++) list_sets(1u << r);
+        pl.sh_ncoef = std::max(pl.lists.size(), l.coms.size() + 1);
+        list_sets(~0u);
+        pl.lists.push_back(0);  // (the place of h1's coefficient: it is no polynomial of the set)
+        ZG_REQUIRE(pl.lists.size() <= 2 * p->sh_terms + 16, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu opening queries (room for %zu)",
+                   l.queries.size(), p->sh_terms);
         return ZG_OK;
     }
     int evaluations_queue() {
@@ -903,74 +934,43 @@ struct ProveBatch {
             ZG_TRY(poly_horner_combine_xn(ctx, polys, p->d_pc, nq, d_hlist, Q, pp_at(p->ix_hpoly), pp_bs, n));
         }
         ZG_TRY(poly_powers(ctx, p->d_pc, nq, npoints, n, p->pw, pw_bs));  // (multi: one x, one table of powers)
-        std::vector<uint32_t> idx(2 * evq.size());
-        for (size_t i = 0; i < evq.size(); i++) {  // (by place in the row: polynomials [0, size), their points behind them)
-            idx[evq[i].at] = evq[i].poly;
-            idx[evq.size() + evq[i].at] = evq[i].slot;
-        }
-        ZG_TRY(h2d_list(p, p->d_idx, idx));
+        const uint32_t E = plan->n_row, n_per = plan->n_per;
+        ZG_TRY(h2d_list(p, p->d_idx, plan->idx));
         // (the evaluations too are written where the host reads them: no copy command behind the kernel)
-        uint32_t distinct_polys = 0;
-        {
-            std::vector<uint32_t> seen(idx.begin(), idx.begin() + evq.size());
-            std::sort(seen.begin(), seen.end());
-            distinct_polys = (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
-        }
         if (!multi) {
-            ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + evq.size(), p->pw, pw_bs, (uint32_t)evq.size(),
-                            p->pin.dev_view(p->pin.evals()), p->max_evals, distinct_polys, npoints));
+            ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + E, p->pw, pw_bs, E, p->pin.dev_view(p->pin.evals()), p->max_evals,
+                            plan->distinct_polys, npoints));
         } else {
             // every circuit's own evaluations, then -- once, slot 0 -- the shared ones: all against the one table of powers
-            const uint32_t n_once = (uint32_t)evq.size() - n_per;
-            ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + evq.size(), p->pw, 0, n_per, p->pin.dev_view(p->pin.evals()),
+            ZG_TRY(poly_dot(ctx, polys, nb, n, p->d_idx, p->d_idx + E, p->pw, 0, n_per, p->pin.dev_view(p->pin.evals()), p->max_evals, 0, npoints));
+            ZG_TRY(poly_dot(ctx, polys, 1, n, p->d_idx + n_per, p->d_idx + E + n_per, p->pw, 0, E - n_per, p->pin.dev_view(p->pin.evals()) + n_per,
                             p->max_evals, 0, npoints));
-            ZG_TRY(poly_dot(ctx, polys, 1, n, p->d_idx + n_per, p->d_idx + evq.size() + n_per, p->pw, 0, n_once,
-                            p->pin.dev_view(p->pin.evals()) + n_per, p->max_evals, 0, npoints));
         }
         ev_all = p->pin.evals();
         ZG_HIP(hipEventRecord(p->evs[W_EVALS], st));
         ZG_TICK("evals: queued");
         return ZG_OK;
     }
-    // evaluation `e` (evq index) of circuit c of a multi proof: a shared one lives in slot 0's row
-    const Fe& ev_of(uint32_t c, size_t e) const { return ev_all[(size_t)(evq[e].shared ? 0 : c) * p->max_evals + evq[e].at]; }
-    // (the evaluations into the transcripts, then v and each point set's v-weighted evaluation: needs openings_lists())
+    // evaluation e of the layout, of the proof whose (first) slot is b
+    const Fe& ev(uint32_t b, uint32_t e) const { return ev_all[(size_t)(b + plan->ev_row[e]) * p->max_evals + plan->ev_at[e]]; }
+    // (the evaluations into the transcripts in the layout's order, then v and each point set's v-weighted evaluation)
     int evaluations_absorb() {
         ZG_HIP(hipEventSynchronize(p->evs[W_EVALS]));
         ZG_TICK("evals on the host");
-        if (multi) {
-            // every circuit's advice evaluations | fixed, random, sigma once | every circuit's permutation evaluations |
-            // every circuit's lookup evaluations
-            Transcript& t = tr[0];
-            for (uint32_t c = 0; c < nb; c++)
-                for (size_t i = 0; i < e_fixed; i++) t.write_scalar(ev_of(c, i));
-            for (size_t i = e_fixed; i < e_pz; i++) t.write_scalar(ev_of(0, i));
-            for (uint32_t c = 0; c < nb; c++)
-                for (size_t i = e_pz; i < e_lk; i++) t.write_scalar(ev_of(c, i));
-            for (uint32_t c = 0; c < nb; c++)
-                for (size_t i = e_lk; i < e_written; i++) t.write_scalar(ev_of(c, i));
-            if (shplonk) return shplonk_numerator_tables();
-            const Fe v = t.squeeze();
-            for (uint32_t b = 0; b < nb; b++) p->hpc[b].v = v;
-            for (uint32_t s = 0; s < nsets; s++) {  // eval_batch of a set: Horner in v over all circuits' evaluations, list order
-                Fe eval_batch = fe_zero();
-                for (const EvRef& r : set_evs[s]) eval_batch = Fr::add(Fr::mul(eval_batch, v), ev_of(r.circuit, r.ev));
-                p->hpc[0].subs[s] = eval_batch;
-            }
-        }
-        for (uint32_t b = 0; b < nb && !multi; b++) {
-            const Fe* ev = ev_all + (size_t)b * p->max_evals;
-            for (size_t i = 0; i < e_written; i++) tr[b].write_scalar(ev[i]);
-            if (shplonk) continue;
-            ProofConst& c = p->hpc[b];
-            c.v = tr[b].squeeze();
-            for (uint32_t s = 0; s < nsets; s++) {
-                Fe eval_batch = fe_zero();
-                for (const EvRef& r : set_evs[s]) eval_batch = Fr::add(Fr::mul(eval_batch, c.v), ev[r.ev]);
-                c.subs[s] = eval_batch;
-            }
-        }
+        const ProofLayout& l = plan->lay;
+        for (uint32_t b = 0; b < ntr; b++)
+            for (uint32_t e = 0; e < l.n_scalars(); e++) tr[b].write_scalar(ev(b, e));
         if (shplonk) return shplonk_numerator_tables();
+        for (uint32_t b = 0; b < ntr; b++) {
+            const Fe v = tr[b].squeeze();
+            for (uint32_t s = 0; s < nb; s++)
+                if (multi || s == b) p->hpc[s].v = v;
+            for (uint32_t s = 0; s < npoints; s++) {  // eval_batch of a set: Horner in v over its queries' evaluations, in order
+                Fe eval_batch = fe_zero();
+                for (uint32_t qi : l.at[s]) eval_batch = Fr::add(Fr::mul(eval_batch, v), ev(b, l.queries[qi].eval));
+                p->hpc[b].subs[s] = eval_batch;
+            }
+        }
         ZG_TICK("v");
         ZG_TRY(publish());
         ZG_TICK("v uploaded");
@@ -978,104 +978,19 @@ struct ProveBatch {
         return ZG_OK;
     }
 
-    int openings_lists() {
-        // ---- opening queries in create_proof's order: (poly, point slot, index of the evaluation)
-        // (multi: circuit after circuit its advice, permutation and lookup queries, then once what all circuits share)
-        std::vector<OQ> oq;
-        for (uint32_t circ = 0; circ < (multi ? nb : 1u); circ++) {
-            for (size_t i = 0; i < e_fixed; i++) oq.push_back({evq[i].poly, evq[i].slot, i, circ});
-            {
-                size_t e = e_pz;
-                std::vector<size_t> e_last(S, 0), e_cur(S, 0), e_next(S, 0);
-                for (uint32_t s = 0; s < S; s++) {
-                    e_cur[s] = e++;
-                    e_next[s] = e++;
-                    if (s + 1 < S) e_last[s] = e++;
-                }
-                for (uint32_t s = 0; s < S; s++) {
-                    oq.push_back({p->ix_pz + s, 0, e_cur[s], circ});
-                    oq.push_back({p->ix_pz + s, 1, e_next[s], circ});
-                }
-                for (uint32_t s = S; s-- > 0;) {
-                    if (s + 1 == S) continue;
-                    oq.push_back({p->ix_pz + s, 3, e_last[s], circ});
-                }
-            }
-            for (uint32_t l = 0; l < NL; l++) {
-                const size_t e5 = e_lk + 5 * l;
-                oq.push_back({p->ix_lz + l, 0, e5 + 0, circ});
-                oq.push_back({p->ix_perm + 2 * l, 0, e5 + 2, circ});
-                oq.push_back({p->ix_perm + 2 * l + 1, 0, e5 + 4, circ});
-                oq.push_back({p->ix_perm + 2 * l, 2, e5 + 3, circ});
-                oq.push_back({p->ix_lz + l, 1, e5 + 1, circ});
-            }
-        }
-        for (size_t i = e_fixed; i < e_random; i++) oq.push_back({evq[i].poly, evq[i].slot, i, 0});
-        for (uint32_t c = 0; c < P; c++) oq.push_back({p->ix_sigma + c, 0, e_sigma + c, 0});
-        oq.push_back({p->ix_hpoly, 0, e_h, 0});
-        oq.push_back({p->ix_random, 0, e_random, 0});
-
-        if (shplonk) return shplonk_sets(oq);
-        // ---- ProverGWC::create_proof: the point sets (circuit only), then per proof its v-weighted evaluation batches
-        nsets = 0;
-        lists.clear(); counts.clear(); set_slot.clear(); set_evs.clear(); firsts.clear();
-        if (multi) {
-            // the same sets -- a point appears first in circuit 0's queries -- over (circuit, polynomial) pairs, each list as
-            // long as it has to be (N = 32 of the zero_g circuit puts about a thousand polynomials at x)
-            ZG_REQUIRE(oq.size() <= p->mlists_cap && p->nsh + p->npp <= 0x10000u, ZG_ERR_UNSUPPORTED,
-                       "zg_prover_prove_multi: %zu opening queries (room for %zu)", oq.size(), p->mlists_cap);
-            std::vector<char> done(oq.size(), 0);
-            for (size_t first = 0; first < oq.size(); first++) {
-                if (done[first]) continue;
-                const uint32_t slot = oq[first].slot;
-                firsts.push_back((uint32_t)lists.size());
-                set_evs.emplace_back();
-                for (size_t j = first; j < oq.size(); j++) {
-                    if (done[j] || oq[j].slot != slot) continue;
-                    done[j] = 1;
-                    lists.push_back(oq[j].circuit << 16 | oq[j].poly);
-                    set_evs.back().push_back({oq[j].circuit, oq[j].ev});
-                }
-                counts.push_back((uint32_t)lists.size() - firsts.back());
-                set_slot.push_back(slot);
-                nsets++;
-            }
-        } else {
-            std::vector<char> done(oq.size(), 0);
-            for (size_t first = 0; first < oq.size(); first++) {
-                if (done[first]) continue;
-                const uint32_t slot = oq[first].slot;
-                lists.resize((size_t)(nsets + 1) * 512, 0);
-                set_evs.emplace_back();
-                uint32_t cnt = 0;
-                for (size_t j = first; j < oq.size(); j++) {
-                    if (done[j] || oq[j].slot != slot) continue;
-                    done[j] = 1;
-                    ZG_REQUIRE(cnt < 512, ZG_ERR_UNSUPPORTED, "zg_prover_prove: more than 512 polynomials opened at one point");
-                    lists[(size_t)nsets * 512 + cnt++] = oq[j].poly;
-                    set_evs.back().push_back({0, oq[j].ev});
-                }
-                counts.push_back(cnt);
-                set_slot.push_back(slot);
-                nsets++;
-            }
-        }
-        ZG_REQUIRE(nsets <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u opening points", nsets);
-        ZG_TICK("opening sets listed");
-        return ZG_OK;
-    }
     int openings_queue() {
         if (shplonk) return shplonk_h1_queue();
         // poly_batch of every point set in one launch: set s -> wpoly[2s]
         // (their own region of d_idx, behind the evaluation lists: nothing else writes there between proofs)
         uint32_t* d_lists = multi ? p->d_mlists : d_hlist + 64;
-        ZG_TRY(h2d_list(p, d_lists, lists));
+        const uint32_t nsets = npoints;
+        ZG_TRY(h2d_list(p, d_lists, plan->lists));
         if (multi)
-            ZG_TRY(poly_combine_pairs(ctx, polys, p->d_pc, d_lists, firsts.data(), counts.data(), nsets, p->wpoly, (size_t)2 * n, n));
+            ZG_TRY(poly_combine_pairs(ctx, polys, p->d_pc, d_lists, plan->firsts.data(), plan->counts.data(), nsets, p->wpoly, (size_t)2 * n, n));
         else
-        ZG_TRY(poly_horner_combine_sets(ctx, polys, p->d_pc, nb, d_lists, 512, counts.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, n));
+            ZG_TRY(poly_horner_combine_sets(ctx, polys, p->d_pc, nb, d_lists, 512, plan->counts.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, n));
         // one batched kate_division: poly s at wpoly[2s], quotient at wpoly[2s+1]
-        ZG_TRY(poly_kate_division(ctx, p->d_pc, nq, set_slot.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n,
+        ZG_TRY(poly_kate_division(ctx, p->d_pc, nq, plan->slots.data(), nsets, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n,
                                   wp_bs, p->ktmp, n));
         // the witness polynomials sit at odd slots: stride 2n
         ctx->msm_dense_hint = true;  // (so are the opening quotients)
@@ -1087,6 +1002,7 @@ struct ProveBatch {
     }
     int openings_absorb() {
         if (shplonk) return shplonk_finish();
+        const uint32_t nsets = npoints;
         ZG_TRY(wait_points(p, (size_t)nq * nsets, pts, W_GWC));
         ZG_TICK("gwc: points on the host");
         for (uint32_t b = 0; b < nq; b++)
@@ -1094,71 +1010,6 @@ struct ProveBatch {
         return ZG_OK;
     }
 
-
-    // ---- SHPLONK (ProverSHPLONK::create_proof, v2023_04_20 src/poly/kzg/multiopen/shplonk/prover.rs)
-    // construct_intermediate_sets: commitments by first appearance, rotation sets by equal point sets, in the order of
-    // their first commitment (circuit only).  The lists of both combinations follow from it: per point r of T the
-    // commitments of every set that holds r, and for L every commitment once.
-    int shplonk_sets(const std::vector<OQ>& oq) {
-        ZG_REQUIRE(p->sh_h1 != nullptr, ZG_ERR_INVALID_ARG, "zg_prover_prove: no SHPLONK buffers (zg_prover_set_multiopen)");
-        ZG_REQUIRE(p->nsh + p->npp <= 0x10000u, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %u polynomials", p->nsh + p->npp);
-        struct Com { uint32_t entry, mask; std::vector<std::pair<uint32_t, EvRef>> at; };
-        std::vector<Com> coms;
-        std::map<uint32_t, size_t> com_of;
-        uint32_t tmask = 0;
-        for (const OQ& q : oq) {
-            const uint32_t entry = (multi ? q.circuit << 16 : 0u) | q.poly;
-            auto it = com_of.find(entry);
-            if (it == com_of.end()) {
-                it = com_of.emplace(entry, coms.size()).first;
-                coms.push_back({entry, 0u, {}});
-            }
-            Com& c = coms[it->second];
-            if (c.mask >> q.slot & 1u) continue;  // (a point set: the same query twice counts once)
-            c.mask |= 1u << q.slot;
-            c.at.push_back({q.slot, {q.circuit, q.ev}});
-            tmask |= 1u << q.slot;
-        }
-        ssets.clear(); tslots.clear();
-        for (uint32_t sl = 0; sl < PC_MAX_POINTS; sl++)
-            if (tmask >> sl & 1u) tslots.push_back(sl);
-        for (const Com& c : coms) {
-            size_t i = 0;
-            while (i < ssets.size() && ssets[i].mask != c.mask) i++;
-            if (i == ssets.size()) {
-                ssets.push_back({c.mask, {}, {}});
-                for (uint32_t sl = 0; sl < PC_MAX_POINTS; sl++)
-                    if (c.mask >> sl & 1u) ssets[i].slots.push_back(sl);
-            }
-            SCom sc{c.entry, {}};
-            for (uint32_t sl : ssets[i].slots)
-                for (const auto& a : c.at)
-                    if (a.first == sl) sc.evs.push_back(a.second);
-            ssets[i].coms.push_back(std::move(sc));
-        }
-        ZG_REQUIRE(ssets.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu rotation sets (max %u)", ssets.size(), HC_MAX_SETS);
-        ZG_REQUIRE(tslots.size() <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "zg_prover_prove: %zu opening points", tslots.size());
-        lists.clear(); sh_first.clear(); sh_count.clear();
-        for (uint32_t r : tslots) {
-            sh_first.push_back((uint32_t)lists.size());
-            for (const SSet& s : ssets)
-                if (s.mask >> r & 1u)
-                    for (const SCom& c : s.coms) lists.push_back(c.entry);
-            sh_count.push_back((uint32_t)lists.size() - sh_first.back());
-        }
-        sh_ncoef = lists.size() > coms.size() + 1 ? lists.size() : coms.size() + 1;
-        sh_first.push_back((uint32_t)lists.size());
-        for (const SSet& s : ssets)
-            for (const SCom& c : s.coms) lists.push_back(c.entry);
-        sh_count.push_back((uint32_t)coms.size());
-        lists.push_back(0);  // (the place of h1's coefficient: it is no polynomial of the set)
-        sh_nlist = lists.size();
-        ZG_REQUIRE(sh_nlist <= 2 * p->sh_terms + 16 && (size_t)(multi ? 1 : nb) * sh_ncoef <= p->sh_terms + p->cap, ZG_ERR_UNSUPPORTED,
-                   "zg_prover_prove: %zu opening queries (room for %zu)", oq.size(), p->sh_terms);
-        ZG_TICK("rotation sets listed");
-        return ZG_OK;
-    }
-    const Fe& sh_ev(uint32_t b, const EvRef& r) const { return multi ? ev_of(r.circuit, r.ev) : ev_all[(size_t)b * p->max_evals + evq[r.ev].at]; }
     // x[i] <- 1 / x[i] with ONE field inversion (Montgomery's trick; no entry is zero: differences of distinct points)
     static void invert_all(std::vector<Fe>& x) {
         std::vector<Fe> pre(x.size());
@@ -1186,7 +1037,10 @@ struct ProveBatch {
     // c_(i,r) = 1 / prod_(p in S_i, p != r) (r - p), and the low coefficients of sum_(i: r in S_i) v^i c_(i,r) R_i(X),
     // R_i = sum_j y^j R_ij the interpolant of the y-combined evaluations on S_i (the host holds them: eval_batch's place)
     int shplonk_numerator_tables() {
-        const uint32_t np = multi ? 1u : nb, nT = (uint32_t)tslots.size();
+        const uint32_t np = ntr, nT = npoints;
+        const ProofLayout& l = plan->lay;
+        const std::vector<ProofLayout::RotationSet>& ssets = l.rsets;
+        const size_t sh_ncoef = plan->sh_ncoef;
         sproof.assign(np, SProof{});
         std::vector<F9> coef((size_t)np * sh_ncoef, F9{});
         std::vector<Fe> corr((size_t)np * nT * PC_MAX_POINTS, fe_zero());
@@ -1199,29 +1053,29 @@ struct ProveBatch {
             std::vector<std::vector<Fe>> cinv(ssets.size());
             {  // every c_(i,a) of the proof under one inversion
                 std::vector<Fe> den;
-                for (const SSet& s : ssets)
-                    for (size_t a = 0; a < s.slots.size(); a++) {
+                for (const ProofLayout::RotationSet& s : ssets)
+                    for (size_t a = 0; a < s.points.size(); a++) {
                         Fe d = Fr::one();
-                        for (size_t c = 0; c < s.slots.size(); c++)
-                            if (c != a) d = Fr::mul(d, Fr::sub(pt[s.slots[a]], pt[s.slots[c]]));
+                        for (size_t c = 0; c < s.points.size(); c++)
+                            if (c != a) d = Fr::mul(d, Fr::sub(pt[s.points[a]], pt[s.points[c]]));
                         den.push_back(d);
                     }
                 invert_all(den);
                 size_t at = 0;
                 for (size_t i = 0; i < ssets.size(); i++) {
-                    cinv[i].assign(den.begin() + at, den.begin() + at + ssets[i].slots.size());
-                    at += ssets[i].slots.size();
+                    cinv[i].assign(den.begin() + at, den.begin() + at + ssets[i].points.size());
+                    at += ssets[i].points.size();
                 }
             }
             Fe vi = Fr::one();
             for (size_t i = 0; i < ssets.size(); i++, vi = Fr::mul(vi, sp.v)) {
-                const SSet& s = ssets[i];
-                const size_t m = s.slots.size();
+                const ProofLayout::RotationSet& s = ssets[i];
+                const size_t m = s.points.size();
                 sp.R[i].assign(m, fe_zero());
                 for (size_t a = 0; a < m; a++) {
                     Fe e = fe_zero(), yj = Fr::one();  // the y-combined evaluation at this point
-                    for (const SCom& c : s.coms) {
-                        e = Fr::add(e, Fr::mul(yj, sh_ev(b, c.evs[a])));
+                    for (uint32_t c : s.coms) {
+                        e = Fr::add(e, Fr::mul(yj, ev(b, l.queries[l.coms[c].queries[a]].eval)));
                         yj = Fr::mul(yj, sp.y);
                     }
                     // e c_(i,a) prod_(c != a) (X - p_c) into R_i
@@ -1229,22 +1083,22 @@ struct ProveBatch {
                     for (size_t c = 0; c < m; c++) {
                         if (c == a) continue;
                         num.push_back(fe_zero());
-                        for (size_t d2 = num.size() - 1; d2 > 0; d2--) num[d2] = Fr::sub(num[d2 - 1], Fr::mul(num[d2], pt[s.slots[c]]));
-                        num[0] = Fr::neg(Fr::mul(num[0], pt[s.slots[c]]));
+                        for (size_t d2 = num.size() - 1; d2 > 0; d2--) num[d2] = Fr::sub(num[d2 - 1], Fr::mul(num[d2], pt[s.points[c]]));
+                        num[0] = Fr::neg(Fr::mul(num[0], pt[s.points[c]]));
                     }
                     for (size_t d2 = 0; d2 < m; d2++) sp.R[i][d2] = Fr::add(sp.R[i][d2], num[d2]);
                 }
             }
             for (uint32_t o = 0; o < nT; o++) {
-                F9* cf = &coef[(size_t)b * sh_ncoef + sh_first[o]];
+                F9* cf = &coef[(size_t)b * sh_ncoef + plan->firsts[o]];
                 Fe* cr = &corr[((size_t)b * nT + o) * PC_MAX_POINTS];
                 size_t at = 0;
                 vi = Fr::one();
                 for (size_t i = 0; i < ssets.size(); i++, vi = Fr::mul(vi, sp.v)) {
-                    const SSet& s = ssets[i];
-                    if (!(s.mask >> tslots[o] & 1u)) continue;
+                    const ProofLayout::RotationSet& s = ssets[i];
+                    if (!(plan->set_mask[i] >> o & 1u)) continue;
                     size_t a = 0;
-                    while (s.slots[a] != tslots[o]) a++;
+                    while (s.points[a] != o) a++;
                     const Fe w = Fr::mul(vi, cinv[i][a]);
                     Fe wy = w;
                     for (size_t j = 0; j < s.coms.size(); j++, wy = Fr::mul(wy, sp.y)) cf[at++] = coef9(wy);
@@ -1260,11 +1114,11 @@ struct ProveBatch {
     // h1 = sum_i v^i N_i / Z_(S_i) as |T| first-order divisions: per point r the combination sum_(i: r in S_i) v^i c_(i,r) N_i
     // (one launch for all of them), the batched Kate division by (X - r), and the sum of the quotients
     int shplonk_h1_queue() {
-        const uint32_t np = multi ? 1u : nb, nT = (uint32_t)tslots.size();
-        ZG_TRY(h2d_list(p, p->sh_lists, lists));
-        ZG_TRY(poly_combine_weighted(ctx, polys, np, p->sh_lists, sh_first.data(), sh_count.data(), nT, p->sh_coef, sh_ncoef, p->sh_corr,
+        const uint32_t np = ntr, nT = npoints;
+        ZG_TRY(h2d_list(p, p->sh_lists, plan->lists));
+        ZG_TRY(poly_combine_weighted(ctx, polys, np, p->sh_lists, plan->firsts.data(), plan->counts.data(), nT, p->sh_coef, plan->sh_ncoef, p->sh_corr,
                                      PC_MAX_POINTS, (size_t)nT * PC_MAX_POINTS, nullptr, 0, p->wpoly, (size_t)2 * n, wp_bs, n));
-        ZG_TRY(poly_kate_division(ctx, p->d_pc, np, tslots.data(), nT, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n, wp_bs,
+        ZG_TRY(poly_kate_division(ctx, p->d_pc, np, plan->slots.data(), nT, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n, wp_bs,
                                   p->ktmp, n));
         ZG_TRY(poly_sum_rows(ctx, np, p->wpoly + n, (size_t)2 * n, wp_bs, nT, p->sh_h1, n, n));
         ctx->msm_dense_hint = true;
@@ -1276,7 +1130,9 @@ struct ProveBatch {
     }
     // h1 -> u; L = sum_i v^i z_i sum_j y^j (P_ij - R_ij(u)) - Z_T(u) h1 with every coefficient already over z_0; h2 = L / (X - u)
     int shplonk_finish() {
-        const uint32_t np = multi ? 1u : nb, nT = (uint32_t)tslots.size(), oL = nT;
+        const uint32_t np = ntr, nT = npoints, oL = nT;
+        const std::vector<ProofLayout::RotationSet>& ssets = plan->lay.rsets;
+        const size_t sh_ncoef = plan->sh_ncoef;
         ZG_TRY(wait_points(p, np, pts, W_GWC));
         ZG_TICK("h1 on the host");
         std::vector<F9> coef((size_t)np * sh_ncoef, F9{});
@@ -1293,8 +1149,8 @@ struct ProveBatch {
         for (uint32_t b = 0; b < np; b++) {
             const Fe* pt = p->hpc[b].points;
             Fe z0 = Fr::one();
-            for (uint32_t r : tslots)
-                if (!(ssets[0].mask >> r & 1u)) z0 = Fr::mul(z0, Fr::sub(pt[PC_U_SLOT], pt[r]));
+            for (uint32_t r = 0; r < nT; r++)
+                if (!(plan->set_mask[0] >> r & 1u)) z0 = Fr::mul(z0, Fr::sub(pt[PC_U_SLOT], pt[r]));
             z0inv_all[b] = z0;
         }
         invert_all(z0inv_all);
@@ -1303,11 +1159,11 @@ struct ProveBatch {
             const Fe* pt = p->hpc[b].points;
             const Fe ub = pt[PC_U_SLOT];
             Fe zT = Fr::one();
-            for (uint32_t r : tslots) zT = Fr::mul(zT, Fr::sub(ub, pt[r]));
+            for (uint32_t r = 0; r < nT; r++) zT = Fr::mul(zT, Fr::sub(ub, pt[r]));
             std::vector<Fe> z(ssets.size(), Fr::one());
             for (size_t i = 0; i < ssets.size(); i++)
-                for (uint32_t r : tslots)
-                    if (!(ssets[i].mask >> r & 1u)) z[i] = Fr::mul(z[i], Fr::sub(ub, pt[r]));
+                for (uint32_t r = 0; r < nT; r++)
+                    if (!(plan->set_mask[i] >> r & 1u)) z[i] = Fr::mul(z[i], Fr::sub(ub, pt[r]));
             const Fe z0inv = z0inv_all[b];
             F9* cf = &coef[(size_t)b * sh_ncoef];
             size_t at = 0;
@@ -1327,7 +1183,7 @@ struct ProveBatch {
         ZG_TRY(publish());
         ZG_TRY(shplonk_upload(coef, corr));
         const uint32_t firstL = 0;  // (L's coefficients start the table of this half; its list is the last one)
-        ZG_TRY(poly_combine_weighted(ctx, polys, np, p->sh_lists + sh_first[oL], &firstL, &sh_count[oL], 1, p->sh_coef, sh_ncoef, p->sh_corr, 1,
+        ZG_TRY(poly_combine_weighted(ctx, polys, np, p->sh_lists + plan->firsts[oL], &firstL, &plan->counts[oL], 1, p->sh_coef, sh_ncoef, p->sh_corr, 1,
                                      1, p->sh_h1, n, p->wpoly, (size_t)2 * n, wp_bs, n));
         const uint32_t uslot = PC_U_SLOT;
         ZG_TRY(poly_kate_division(ctx, p->d_pc, np, &uslot, 1, p->wpoly, (size_t)2 * n, wp_bs, p->wpoly + n, (size_t)2 * n, wp_bs, p->ktmp, n));
@@ -1420,12 +1276,7 @@ static int prove_multi_impl(zg_prover* p, size_t circuits, const zg_fr* const* a
 
 size_t zg_prover_proof_size_multi(const zg_prover* p, size_t circuits) {
     if (!p || !circuits) return 0;
-    const PkDev& k = *p->pk;
-    const size_t per_points = k.A + 3 * k.NL + k.sets;
-    const size_t per_scalars = k.advice_queries.size() + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
-    const size_t max_open = p->multiopen == ZG_MULTIOPEN_SHPLONK ? 2 : 2 + k.advice_queries.size() + k.fixed_queries.size();
-    const size_t point_bytes = p->transcript == ZG_TRANSCRIPT_BLAKE2B ? 32 : 64;
-    return point_bytes * (circuits * per_points + 1 + k.qpd + max_open) + 32 * (circuits * per_scalars + k.fixed_queries.size() + 1 + k.P);
+    return proof_size_bound(proof_shape(*p->pk), (uint32_t)circuits, p->multiopen == ZG_MULTIOPEN_SHPLONK, p->transcript == ZG_TRANSCRIPT_BLAKE2B);
 }
 
 int zg_prover_prove_multi(zg_prover* p, size_t circuits, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,

@@ -6,8 +6,29 @@
 
 #include "poly.h"
 #include "check.h"
+#include "proof_layout.h"
 
 namespace zg {
+
+// The layout of a proof of N circuits under one multi-open argument (proof_layout.h) in the prover's device list
+// formats.  The prover's handle of a commitment is its polynomial index (zg_prover::ix_*; `circuit << 16 | index` in a
+// proof of several circuits), of a layout point its number as the ProofConst::points slot.  Made at the first proof that
+// needs it (ProveBatch::opening_plan) and kept as long as the slots.
+struct OpenPlan {
+    ProofLayout lay;
+    // evaluation e of the layout lands in row ev_row[e] of the slots' evaluations (its circuit's; the proof's own slot when
+    // N = 1) at place ev_at[e]: transcript order, or (N > 1) a circuit's n_per own evaluations in every row and behind
+    // them, in row 0 only, what the proof holds once: fixed, random, sigma, h
+    std::vector<uint32_t> ev_row, ev_at;
+    uint32_t n_per = 0, n_row = 0, distinct_polys = 0;
+    std::vector<uint32_t> idx;  // poly_dot's lists: the polynomials of a row's n_row places, their point slots behind them
+    std::vector<uint32_t> slots;  // 0 .. points: the slot of every opening point, for the Kate divisions
+    // GWC: point set s opens the entries lists[firsts[s] .. + counts[s]) (N = 1: 512 entries apart)
+    // SHPLONK: per point r of T the commitments of every set that holds r, then (list T) every commitment once for L,
+    // then the place of h1's coefficient; set_mask[i]: the points of rotation set i
+    std::vector<uint32_t> lists, firsts, counts, com_entry, set_mask;
+    size_t sh_ncoef = 0;  // coefficients per proof (both halves use [0, ..))
+};
 
 // ------------------------------------------------------------------ proving key on the device
 // What keygen_pk derives, resident in HBM, shared (read-only) by every prover forked from the one that built it.
@@ -73,6 +94,14 @@ struct PkDev {
         for (void* q : owned) (void)hipFree(q);
     }
 };
+
+inline ProofShape proof_shape(const PkDev& k) {
+    ProofShape s;
+    s.A = k.A; s.F = k.F; s.P = k.P; s.NL = k.NL; s.sets = k.sets; s.qpd = k.qpd; s.bf = k.bf; s.log_n = k.k;
+    for (const zg_query& q : k.advice_queries) s.advice_queries.push_back({q.column, q.rotation});
+    for (const zg_query& q : k.fixed_queries) s.fixed_queries.push_back({q.column, q.rotation});
+    return s;
+}
 
 // ------------------------------------------------------------------ the prover's pinned arena
 // ONE block of coherent, mapped host memory that kernels write and the host reads right after an event (alloc_slots), in
@@ -179,6 +208,7 @@ struct zg_prover {
     zg::Fe* sh_corr = nullptr;
     size_t sh_terms = 0;  // opening queries of `cap` circuits: sh_lists holds 2 * sh_terms + 16 entries, sh_coef sh_terms + cap + 16
     std::map<uint32_t*, std::vector<uint32_t>> uploaded_lists;  // what h2d_list left at each destination
+    std::map<std::pair<int, uint32_t>, zg::OpenPlan> plans;     // by (multi-open argument, circuits in a proof)
     std::vector<size_t> inst_filled;  // per slot: rows of inst_val that may be non-zero
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_err = nullptr;
     // One event per WAIT of a proof (the five commitment phases and the evaluations): with the gate (below) the next phase's

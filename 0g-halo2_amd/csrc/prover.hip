@@ -173,6 +173,7 @@ void free_slots(zg_prover* p) {
     p->gate_seq = 0;  // (the gate word goes with the arena: a new one starts at zero, and a gate opens at its number or later)
     p->cap = 0;
     p->uploaded_lists.clear();
+    p->plans.clear();  // (their limits were the slots')
     p->warm_sig = 0;  // (new buffers: the next proof is a first proof again -- ProveBatch::gate_wanted)
 }
 
@@ -927,14 +928,7 @@ int zg_prover_set_transcript(zg_prover* p, int transcript) {
 
 int zg_prover_transcript(const zg_prover* p) { return p ? p->transcript : ZG_TRANSCRIPT_EVM; }
 
-size_t zg_prover_proof_size(const zg_prover* p) {
-    if (!p) return 0;
-    const PkDev& k = *p->pk;
-    size_t points = k.A + 2 * k.NL + k.sets + k.NL + 1 + k.qpd;
-    size_t scalars = k.advice_queries.size() + k.fixed_queries.size() + 1 + k.P + (k.sets ? 3 * k.sets - 1 : 0) + 5 * k.NL;
-    size_t max_open = p->multiopen == ZG_MULTIOPEN_SHPLONK ? 2 : 2 + k.advice_queries.size() + k.fixed_queries.size();
-    return (p->transcript == ZG_TRANSCRIPT_BLAKE2B ? 32 : 64) * (points + max_open) + 32 * scalars;
-}
+size_t zg_prover_proof_size(const zg_prover* p) { return zg_prover_proof_size_multi(p, 1); }
 
 void zg_prover_destroy(zg_prover* p) {
     if (!p) return;

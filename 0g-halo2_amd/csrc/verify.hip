@@ -4,15 +4,18 @@
 // instances of it (verify_proof's `instances: &[&[&[F]]]`; NC = 1: zg_verifier_verify_batch).  A proof of NC instances
 // holds the per-circuit commitments and evaluations NC times, circuit-major within each family, and once what the
 // circuits share: the random polynomial, h, the fixed and sigma evaluations, one W per point set.
+// That order -- families, evaluations, opening queries, point sets, SHPLONK's rotation sets, lengths -- is stated in
+// proof_layout.h, for the prover too; set_circuits() maps it to term indices and device tables and derives none of it.
 //
 // Per proof b the GWC equation is  e(L_b, [s]_2) = e(R_b, [1]_2)  with  L_b = sum_j u^j W_j  and
 // R_b = sum_j u^j (z_j W_j + sum_k v^(m_j-1-k) C_jk - e_j G),  j over the opening point sets in first-appearance order,
 // k over a set's queries in query order.  Four launches and one host step:
-//   verify_replay   one wave per proof: the EvmTranscript read back (Keccak-f[1600]), every point and
-//                   scalar validated as it is read, the challenges theta, beta, gamma, y, x, v, u squeezed;
-//                   (zg_verifier_set_transcript(ZG_TRANSCRIPT_BLAKE2B), DESIGN.md section 17: g1_decompress_kernel of
-//                   g1_compress.hip first -- one lane per commitment of the batch, y from x -- then verify_replay_b2,
-//                   the same walk over the decompressed points with BLAKE2b and little-endian scalars)
+//   verify_replay   one wave per proof: the transcript read back in ONE walk (replay_one) over a format policy, every
+//                   point and scalar validated as it is read, the challenges theta, beta, gamma, y, x, v, u squeezed.
+//                   KeccakWalk: EvmTranscript, the sponge of keccak.h.  Blake2bWalk (zg_verifier_set_transcript(
+//                   ZG_TRANSCRIPT_BLAKE2B)): g1_decompress_kernel of g1_compress.hip first -- one
+//                   lane per commitment of the batch, y from x -- then the walk over the decompressed points with
+//                   BLAKE2b and little-endian scalars.  No hash code lives in this file.
 //   verify_scalars  one wave per proof: x^n, l_0 / l_last / l_blind and the instance evaluations (Lagrange form,
 //                   O(instance_len) per query) with one batched inversion, the expected h(x) from the gates, the
 //                   permutation and the lookups folded with y, then every term's scalar of L_b and R_b;
@@ -28,6 +31,7 @@
 #include "blake2b.h"
 #include "keccak.h"
 #include "poly.h"
+#include "proof_layout.h"
 
 namespace zg {
 
@@ -79,16 +83,15 @@ struct VArgs {
     // the multi-open argument: nW points end a proof (GWC: one W per point set; SHPLONK: h1, h2), the last nL of them are
     // the left side's terms (every W; h2).  SHPLONK: nS rotation sets over the nT points of T;
     // set i holds the points f_pt[s_first[i] .. s_first[i + 1]) (indices into T, nF pairs in all) and s_mask[i] says
-    // which points of T are its own; t_wr[t] = omega^rotation of point t
+    // which points of T are its own; T is GWC's point sets, so set_wr[t] = omega^rotation of point t
     uint32_t scheme, nW, nL, nS, nT, nF, nwork;
     const uint32_t* s_first;
     const uint32_t* s_mask;
     const uint32_t* f_pt;
-    const Fe* t_wr;
-    // proofs of NC circuit instances: where the families start among a proof's points (circuit c's share of a family
-    // follows circuit c-1's: A advice, 2 NL permuted, `sets` permutation z, NL lookup z) and among its evaluations (nAQ
-    // advice, npz permutation, 5 NL lookup evaluations per circuit)
-    uint32_t NC, PT_LK, PT_PZ, PT_LZ, PT_RAND, EV_FIX, EV_SIG, EV_PZ, EV_LK, npz;
+    // proofs of NC circuit instances, from proof_layout.h (set_circuits): the points the walk reads between two squeezes,
+    // where the random polynomial's commitment stands among a proof's points, and where the families start among its
+    // evaluations (circuit c's share follows circuit c-1's: nAQ advice, npz permutation, 5 NL lookup evaluations each)
+    uint32_t NC, walk[4], PT_RAND, EV_FIX, EV_SIG, EV_PZ, EV_LK, npz;
     uint32_t log_n;
     Fe omega, ifft_div, delta, vk_repr;
     // batch
@@ -114,42 +117,6 @@ struct VArgs {
     XYZZ* out;       // [2]
 };
 
-// ------------------------------------------------------------------ Keccak-256 sponge
-// EvmTranscript's hash state: the bytes absorbed since the last squeeze, streamed into the sponge
-struct Sponge {
-    uint64_t st[25];
-    uint32_t pos, len;
-};
-__host__ __device__ void sp_reset(Sponge& s) {
-    for (int i = 0; i < 25; i++) s.st[i] = 0;
-    s.pos = 0;
-    s.len = 0;
-}
-__host__ __device__ void sp_byte(Sponge& s, uint32_t b) {
-    s.st[s.pos >> 3] ^= (uint64_t)(b & 0xff) << (8 * (s.pos & 7));
-    s.len++;
-    if (++s.pos == KECCAK_RATE) {
-        keccak_f1600(s.st);
-        s.pos = 0;
-    }
-}
-// 32 big-endian bytes of a canonical integer (8 LE u32 limbs)
-__host__ __device__ void sp_int(Sponge& s, const Fe& raw) {
-    for (int k = 0; k < 32; k++) sp_byte(s, raw.l[(31 - k) >> 2] >> (8 * ((31 - k) & 3)));
-}
-// the squeeze of transcript.h's EvmTranscript, on the streamed sponge; the state becomes the hash
-__host__ __device__ Fe sp_squeeze(Sponge& s) {
-    if (squeeze_appends_one(s.len)) sp_byte(s, 1);
-    s.st[s.pos >> 3] ^= 0x01ull << (8 * (s.pos & 7));
-    s.st[KECCAK_RATE / 8 - 1] ^= 0x80ull << 56;
-    keccak_f1600(s.st);
-    uint8_t h[32];
-    for (int k = 0; k < 32; k++) h[k] = (uint8_t)(s.st[k >> 3] >> (8 * (k & 7)));
-    sp_reset(s);
-    for (int k = 0; k < 32; k++) sp_byte(s, h[k]);
-    return challenge_from_hash(h);
-}
-
 template <class P>
 __host__ __device__ bool below_modulus(const Fe& v) {
     for (int i = 7; i >= 0; i--) {
@@ -166,166 +133,147 @@ __host__ __device__ Fe be_int(const uint8_t* b) {
     return v;
 }
 
-struct Reader {
-    const uint8_t* p;
-    uint64_t pos, len;
+// A proof as the transcript walk sees it: its bytes, where its points go and -- Blake2b -- whether g1_decompress_kernel
+// found them valid.  The pointers live here and not in the policies below: next to a hash state, which is indexed
+// dynamically and so kept in scratch, a pointer comes back without its address space and every byte of the proof is
+// read with a flat load (measured: the Keccak walk of a tiny-model proof 1.62 ms instead of 1.43).
+struct ProofIn {
+    const uint8_t* bytes;
+    uint64_t len;
+    Affine* pts;
+    const uint8_t* valid;
 };
-__host__ __device__ bool read_point(Reader& r, Sponge& s, Affine& out) {
-    if (r.pos + 64 > r.len) return false;
-    const uint8_t* b = r.p + r.pos;
-    r.pos += 64;
-    const Fe x = be_int(b), y = be_int(b + 32);
-    if (!below_modulus<FqParams>(x) || !below_modulus<FqParams>(y)) return false;
-    out.x = Fq::from_raw(x);
-    out.y = Fq::from_raw(y);
-    if (affine_is_identity(out) || !affine_on_curve(out)) return false;  // (the transcript refuses the identity)
-    for (int k = 0; k < 64; k++) sp_byte(s, b[k]);
-    return true;
-}
-__host__ __device__ bool read_scalar(Reader& r, Sponge& s, Fe& out) {
-    if (r.pos + 32 > r.len) return false;
-    const uint8_t* b = r.p + r.pos;
-    r.pos += 32;
-    const Fe v = be_int(b);
-    if (!below_modulus<FrParams>(v)) return false;
-    out = Fr::from_raw(v);
-    for (int k = 0; k < 32; k++) sp_byte(s, b[k]);
-    return true;
-}
-
-// Read order (NC = 1; with more circuits every per-circuit family is read for circuit 0, 1, ... in turn, and the
-// permutation z of all circuits come before the lookup z of all circuits): advice commitments | theta | per lookup (permuted input, permuted table) | beta, gamma | permutation z
-// per set | lookup z | random | y | h pieces | x | advice, fixed evals, random eval, sigma evals, permutation evals
-// (z, z(wx), and z(w^last x) except for the last set), lookup evals (z, z(wx), a', a'(w^-1 x), s') | v | one W per
-// point set | u.  Points land in pts in that order (W last), evaluations in ev.
-__host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
+// What the walk asks of a transcript format: begin (false: the proof cannot be read at all), absorb a common scalar,
+// read and absorb the proof's next point into / from pts[i], read and absorb its next scalar, squeeze, and whether the
+// proof ended where the walk did.
+// EvmTranscript (keccak.h): 64-byte big-endian points, each coordinate below q, on the curve and not the identity (the
+// transcript refuses it); 32-byte big-endian scalars below r.
+struct KeccakWalk {
     Sponge s;
-    sp_reset(s);
-    Reader r{a.bytes + a.off[b], 0, a.len[b]};
-    Affine* pts = a.pts + (size_t)b * a.NP;
-    Fe* ev = a.ev + (size_t)b * a.NE;
-    Fe* ch = a.ch + (size_t)b * CH_N;
-    sp_int(s, Fr::to_raw(a.vk_repr));
-    const Fe* inst = a.inst + (size_t)b * a.NC * a.I * a.ilen;
-    for (uint32_t i = 0; i < a.NC * a.I * a.ilen; i++) sp_int(s, Fr::to_raw(inst[i]));
-    bool ok = true;
-    uint32_t pi = 0, ei = 0;
-    for (uint32_t c = 0; c < a.NC * a.A && ok; c++) ok = read_point(r, s, pts[pi++]);
-    if (ok) ch[CH_THETA] = sp_squeeze(s);
-    for (uint32_t l = 0; l < a.NC * 2 * a.NL && ok; l++) ok = read_point(r, s, pts[pi++]);
-    if (ok) {
-        ch[CH_BETA] = sp_squeeze(s);
-        ch[CH_GAMMA] = sp_squeeze(s);
+    uint64_t pos;
+    __host__ __device__ bool begin(const ProofIn&, uint64_t) {
+        sp_reset(s);
+        pos = 0;
+        return true;
     }
-    for (uint32_t c = 0; c < a.NC * (a.sets + a.NL) + 1 && ok; c++) ok = read_point(r, s, pts[pi++]);
-    if (ok) ch[CH_Y] = sp_squeeze(s);
-    for (uint32_t c = 0; c < a.qpd && ok; c++) ok = read_point(r, s, pts[pi++]);
-    if (ok) ch[CH_X] = sp_squeeze(s);
-    for (uint32_t c = 0; c < a.ev_h && ok; c++) ok = read_scalar(r, s, ev[ei++]);
-    if (a.scheme == ZG_MULTIOPEN_SHPLONK) {  // y, v | h1 | u | h2
-        if (ok) {
-            ch[CH_SY] = sp_squeeze(s);
-            ch[CH_V] = sp_squeeze(s);
-            ok = read_point(r, s, pts[pi++]);
-        }
-        if (ok) {
-            ch[CH_U] = sp_squeeze(s);
-            ok = read_point(r, s, pts[pi++]);
-        }
-    } else {
-        if (ok) ch[CH_V] = sp_squeeze(s);
-        for (uint32_t c = 0; c < a.nsets && ok; c++) ok = read_point(r, s, pts[pi++]);
-        if (ok) ch[CH_U] = sp_squeeze(s);
+    __host__ __device__ void common_scalar(const Fe& raw) { sp_int(s, raw); }
+    __host__ __device__ bool point(const ProofIn& in, uint32_t i) {
+        if (pos + 64 > in.len) return false;
+        const uint8_t* b = in.bytes + pos;
+        pos += 64;
+        const Fe x = be_int(b), y = be_int(b + 32);
+        if (!below_modulus<FqParams>(x) || !below_modulus<FqParams>(y)) return false;
+        Affine& out = in.pts[i];
+        out.x = Fq::from_raw(x);
+        out.y = Fq::from_raw(y);
+        if (affine_is_identity(out) || !affine_on_curve(out)) return false;
+        for (int k = 0; k < 64; k++) sp_byte(s, b[k]);
+        return true;
     }
-    a.status[b] = !ok ? ST_MALFORMED : r.pos != r.len ? ST_TRAILING : ST_OK;
-}
-// The same walk for halo2's Blake2b transcript (blake2b.h; the format: include/zg_halo2.h, zg_prover_set_transcript).  A
-// proof is a fixed layout of 32-byte items, so a short one is malformed before anything is read; the commitments are in
-// pts already, decompressed by g1_decompress_kernel with their flags in pvalid (an invalid encoding and the identity are
-// refused here, where the transcript would refuse them); scalars are little-endian canonical integers below r.
-__host__ __device__ bool b2_point(Blake2b& s, const Affine& p, uint8_t valid, uint64_t& pos) {
-    pos += 32;
-    if (!valid || affine_is_identity(p)) return false;
-    b2_byte(s, 1);
-    b2_int(s, Fq::to_raw(p.x));
-    b2_int(s, Fq::to_raw(p.y));
-    return true;
-}
-__host__ __device__ bool b2_scalar(Blake2b& s, const uint8_t* b, uint64_t& pos, Fe& out) {
-    Fe v;
-    for (int i = 0; i < 8; i++)
-        v.l[i] = (uint32_t)b[pos + 4 * i] | ((uint32_t)b[pos + 4 * i + 1] << 8) | ((uint32_t)b[pos + 4 * i + 2] << 16) |
-                 ((uint32_t)b[pos + 4 * i + 3] << 24);
-    pos += 32;
-    if (!below_modulus<FrParams>(v)) return false;
-    out = Fr::from_raw(v);
-    b2_byte(s, 2);
-    b2_int(s, v);
-    return true;
-}
-__host__ __device__ void replay_one_b2(const VArgs& a, uint32_t b) {
-    if (a.len[b] < a.b2_len) {
+    __host__ __device__ bool scalar(const ProofIn& in, Fe& out) {
+        if (pos + 32 > in.len) return false;
+        const uint8_t* b = in.bytes + pos;
+        pos += 32;
+        const Fe v = be_int(b);
+        if (!below_modulus<FrParams>(v)) return false;
+        out = Fr::from_raw(v);
+        for (int k = 0; k < 32; k++) sp_byte(s, b[k]);
+        return true;
+    }
+    __host__ __device__ Fe squeeze() { return sp_squeeze(s); }
+    __host__ __device__ bool at_end(const ProofIn& in) const { return pos == in.len; }
+};
+// halo2's Blake2b transcript (blake2b.h; the format: include/zg_halo2.h, zg_prover_set_transcript).  A proof is a fixed
+// layout of 32-byte items, `fixed_len` bytes, so a short one is malformed before anything is read; the commitments are in
+// pts already, decompressed by g1_decompress_kernel with their flags (an invalid encoding and the identity are refused
+// here, where the transcript would refuse them); scalars are little-endian canonical integers below r.
+struct Blake2bWalk {
+    Blake2b s;
+    uint64_t pos, fixed_len;
+    __host__ __device__ bool begin(const ProofIn& in, uint64_t fixed_len_) {
+        if (in.len < fixed_len_) return false;
+        b2_init_halo2(s);
+        pos = 0;
+        fixed_len = fixed_len_;
+        return true;
+    }
+    __host__ __device__ void common_scalar(const Fe& raw) {
+        b2_byte(s, 2);
+        b2_int(s, raw);
+    }
+    __host__ __device__ bool point(const ProofIn& in, uint32_t i) {
+        pos += 32;
+        if (!in.valid[i] || affine_is_identity(in.pts[i])) return false;
+        b2_byte(s, 1);
+        b2_int(s, Fq::to_raw(in.pts[i].x));
+        b2_int(s, Fq::to_raw(in.pts[i].y));
+        return true;
+    }
+    __host__ __device__ bool scalar(const ProofIn& in, Fe& out) {
+        const uint8_t* b = in.bytes + pos;
+        Fe v;
+        for (int i = 0; i < 8; i++)
+            v.l[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
+        pos += 32;
+        if (!below_modulus<FrParams>(v)) return false;
+        out = Fr::from_raw(v);
+        common_scalar(v);
+        return true;
+    }
+    __host__ __device__ Fe squeeze() { return b2_squeeze(s); }
+    __host__ __device__ bool at_end(const ProofIn& in) const { return fixed_len == in.len; }
+};
+
+// The walk, in the order of proof_layout.h's families: the vk and the instances | walk[0] points (advice) | theta | walk[1]
+// (permuted) | beta, gamma | walk[2] (permutation z, lookup z, random) | y | walk[3] (h pieces) | x | the evaluations |
+// GWC: v, one W per point set, u; SHPLONK: y, v, h1, u, h2.  Points land in pts in that order, evaluations in ev.
+template <class Walk>
+__host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
+    const ProofIn in{a.bytes + a.off[b], a.len[b], a.pts + (size_t)b * a.NP, a.pvalid + (size_t)b * a.NP};
+    Walk w;
+    if (!w.begin(in, a.b2_len)) {
         a.status[b] = ST_MALFORMED;
         return;
     }
-    Blake2b s;
-    b2_init_halo2(s);
-    const uint8_t* bytes = a.bytes + a.off[b];
-    const Affine* pts = a.pts + (size_t)b * a.NP;
-    const uint8_t* pv = a.pvalid + (size_t)b * a.NP;
     Fe* ev = a.ev + (size_t)b * a.NE;
     Fe* ch = a.ch + (size_t)b * CH_N;
-    b2_byte(s, 2);
-    b2_int(s, Fr::to_raw(a.vk_repr));
+    w.common_scalar(Fr::to_raw(a.vk_repr));
     const Fe* inst = a.inst + (size_t)b * a.NC * a.I * a.ilen;
-    for (uint32_t i = 0; i < a.NC * a.I * a.ilen; i++) {
-        b2_byte(s, 2);
-        b2_int(s, Fr::to_raw(inst[i]));
-    }
+    for (uint32_t i = 0; i < a.NC * a.I * a.ilen; i++) w.common_scalar(Fr::to_raw(inst[i]));
     bool ok = true;
-    uint32_t pi = 0, ei = 0;
-    uint64_t pos = 0;
-#define B2_POINTS(count)                                                 \
-    for (uint32_t c = 0; c < (count) && ok; c++, pi++) ok = b2_point(s, pts[pi], pv[pi], pos)
-    B2_POINTS(a.NC * a.A);
-    if (ok) ch[CH_THETA] = b2_squeeze(s);
-    B2_POINTS(a.NC * 2 * a.NL);
-    if (ok) {
-        ch[CH_BETA] = b2_squeeze(s);
-        ch[CH_GAMMA] = b2_squeeze(s);
-    }
-    B2_POINTS(a.NC * (a.sets + a.NL) + 1);
-    if (ok) ch[CH_Y] = b2_squeeze(s);
-    B2_POINTS(a.qpd);
-    if (ok) ch[CH_X] = b2_squeeze(s);
-    for (uint32_t c = 0; c < a.ev_h && ok; c++) ok = b2_scalar(s, bytes, pos, ev[ei++]);
-    if (a.scheme == ZG_MULTIOPEN_SHPLONK) {  // y, v | h1 | u | h2
-        if (ok) {
-            ch[CH_SY] = b2_squeeze(s);
-            ch[CH_V] = b2_squeeze(s);
-        }
-        B2_POINTS(1);
-        if (ok) ch[CH_U] = b2_squeeze(s);
-        B2_POINTS(1);
-    } else {
-        if (ok) ch[CH_V] = b2_squeeze(s);
-        B2_POINTS(a.nsets);
-        if (ok) ch[CH_U] = b2_squeeze(s);
-    }
-#undef B2_POINTS
-    a.status[b] = !ok ? ST_MALFORMED : a.b2_len != a.len[b] ? ST_TRAILING : ST_OK;
+    uint32_t pi = 0;
+    auto points = [&](uint32_t count) {
+        for (uint32_t c = 0; c < count && ok; c++) ok = w.point(in, pi++);
+    };
+    auto squeeze = [&](uint32_t c) {
+        if (ok) ch[c] = w.squeeze();
+    };
+    points(a.walk[0]);
+    squeeze(CH_THETA);
+    points(a.walk[1]);
+    squeeze(CH_BETA);
+    squeeze(CH_GAMMA);
+    points(a.walk[2]);
+    squeeze(CH_Y);
+    points(a.walk[3]);
+    squeeze(CH_X);
+    for (uint32_t c = 0; c < a.ev_h && ok; c++) ok = w.scalar(in, ev[c]);
+    const bool shplonk = a.scheme == ZG_MULTIOPEN_SHPLONK;
+    if (shplonk) squeeze(CH_SY);
+    squeeze(CH_V);
+    points(shplonk ? 1 : a.nW);
+    squeeze(CH_U);
+    if (shplonk) points(1);
+    a.status[b] = !ok ? ST_MALFORMED : !w.at_end(in) ? ST_TRAILING : ST_OK;
 }
 // One wave per proof, every lane running the same code on the same data (identical stores), so the per-proof work runs
 // in uniform control flow.  63 of the 64 lanes are redundant; the layout is kept because the one-lane-per-proof form of
-// these two kernels gave wrong field products on the device (the same bodies are right on the host), for a reason not
-// found yet.  The two kernels are a small share of a batch's time.
+// this kernel and verify_scalars gave wrong field products on the device (the same bodies are right on the host), for a
+// reason not found yet.  The two kernels are a small share of a batch's time.
+template <class Walk>
 __global__ __launch_bounds__(64) void verify_replay(VArgs a) {
     const uint32_t b = blockIdx.x;
-    if (b < a.count) replay_one(a, b);
-}
-__global__ __launch_bounds__(64) void verify_replay_b2(VArgs a) {
-    const uint32_t b = blockIdx.x;
-    if (b < a.count) replay_one_b2(a, b);
+    if (b < a.count) replay_one<Walk>(a, b);
 }
 
 // in-place inversion of x[0..m) (zeros stay zero) with one field inversion; pre = m scratch elements
@@ -397,7 +345,7 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
     const uint32_t d_sh = 1 + nl + a.n_iev * a.ilen;
     const bool shplonk = a.scheme == ZG_MULTIOPEN_SHPLONK;
     if (shplonk) {
-        for (uint32_t t = 0; t < a.nT; t++) tp[t] = Fr::mul(x, a.t_wr[t]);
+        for (uint32_t t = 0; t < a.nT; t++) tp[t] = Fr::mul(x, a.set_wr[t]);
         for (uint32_t i = 0; i < a.nS; i++)
             for (uint32_t f = a.s_first[i]; f < a.s_first[i + 1]; f++) {
                 Fe d = one;
@@ -625,22 +573,18 @@ struct zg_verifier {
     VArgs a{};
     zg_g2_affine g2{}, s_g2{};
     std::vector<void*> owned;  // circuit arrays
-    // what the query table of a proof of NC circuits is built from, and the tables made so far (by NC)
-    std::vector<zg_query> advice_queries, fixed_queries;
-    int scheme = ZG_MULTIOPEN_GWC;  // zg_verifier_set_multiopen
+    ProofShape shape;                    // what the layout of a proof of NC circuits is built from
+    int scheme = ZG_MULTIOPEN_GWC;       // zg_verifier_set_multiopen
     int transcript = ZG_TRANSCRIPT_EVM;  // zg_verifier_set_transcript
     struct Table {
-        const VQuery* oq = nullptr;
+        ProofLayout lay;
+        const VQuery* oq = nullptr;  // the layout's queries under this verifier's handles, on the device
         uint32_t n_oq = 0;
         // SHPLONK: the rotation sets (VArgs)
-        uint32_t nS = 0, nT = 0, nF = 0;
+        uint32_t nF = 0;
         const uint32_t *s_first = nullptr, *s_mask = nullptr, *f_pt = nullptr;
-        const Fe* t_wr = nullptr;
-        // Blake2b transcript: the byte offset of every point of a proof (a fixed layout of 32-byte items), its length
-        std::vector<uint32_t> pt_off;
-        uint64_t b2_len = 0;
     };
-    std::map<std::array<int, 3>, Table> tables;  // by (transcript, scheme, circuits)
+    std::map<std::array<int, 2>, Table> tables;  // the layouts made so far, by (scheme, circuits)
     const Table* table = nullptr;                // the one in use (set_circuits)
     // batch buffers, grown on demand (cap: proofs; pts / ev / sc: elements, their size per proof follows NC)
     size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0, pts_cap = 0, ev_cap = 0, sc_cap = 0;
@@ -715,160 +659,88 @@ Fe omega_pow(const Fe& omega, const Fe& omega_inv, int64_t r) {
     return Fr::pow_u64(r >= 0 ? omega : omega_inv, (uint64_t)(r >= 0 ? r : -r));
 }
 
-// The layout of a proof of NC circuit instances and its table of opening queries into v->a; tables are built once per NC.
-// Points in read order: every circuit's advice | every circuit's (permuted input, permuted table) per lookup | every
-// circuit's permutation z | every circuit's lookup z | random | h pieces | W per point set.  Evaluations in read order:
-// every circuit's advice | fixed, random, sigma | every circuit's permutation (3 per set, 2 for the last) | every circuit's
-// lookups (5 each) | (the expected h(x)).
+// The layout of a proof of NC circuit instances (proof_layout.h, built once per scheme and NC) into v->a, with its opening
+// queries as a VQuery table.  The verifier's handle of a commitment is its term index: a proof's own points stand first,
+// in the layout's order, the key's fixed and sigma commitments are SHARED, h is HREF; a layout point is a point set.
 int set_circuits(zg_verifier* v, uint32_t NC) {
     VArgs& a = v->a;
-    a.NC = NC;
-    a.PT_LK = NC * a.A; a.PT_PZ = a.PT_LK + NC * 2 * a.NL; a.PT_LZ = a.PT_PZ + NC * a.sets; a.PT_RAND = a.PT_LZ + NC * a.NL;
-    a.EV_FIX = NC * a.nAQ;
-    const uint32_t EV_RAND = a.EV_FIX + a.nFQ;
-    a.EV_SIG = EV_RAND + 1; a.EV_PZ = a.EV_SIG + a.P; a.EV_LK = a.EV_PZ + NC * a.npz;
-    a.ev_h = a.EV_LK + NC * 5 * a.NL;
-    a.NE = a.ev_h + 1;
-    // opening queries in the prover's order -- circuit after circuit its advice, permutation and lookup queries, then what
-    // the circuits share; point sets by first appearance of their rotation (circuit 0's order: the same sets for every NC)
-    std::vector<VQuery> oq;
-    std::vector<int64_t> set_rot;
-    std::vector<uint32_t> set_size;
-    const int64_t nn = (int64_t)1 << a.log_n, last = -(int64_t)(a.bf + 1);
-    auto add = [&](int64_t rot, uint32_t term, uint32_t eval) {
-        const int64_t key = ((rot % nn) + nn) % nn;
-        uint32_t j = 0;
-        while (j < set_rot.size() && set_rot[j] != key) j++;
-        if (j == set_rot.size()) {
-            set_rot.push_back(key);
-            set_size.push_back(0);
-        }
-        oq.push_back({term, eval, j, set_size[j]++, 0});
-    };
-    for (uint32_t c = 0; c < NC; c++) {
-        const uint32_t pt_adv = c * a.A, pt_lk = a.PT_LK + c * 2 * a.NL, pt_pz = a.PT_PZ + c * a.sets, pt_lz = a.PT_LZ + c * a.NL;
-        const uint32_t ev_adv = c * a.nAQ, ev_pz = a.EV_PZ + c * a.npz, ev_lk = a.EV_LK + c * 5 * a.NL;
-        for (uint32_t i = 0; i < a.nAQ; i++) add(v->advice_queries[i].rotation, pt_adv + v->advice_queries[i].column, ev_adv + i);
-        for (uint32_t s = 0; s < a.sets; s++) {
-            add(0, pt_pz + s, ev_pz + 3 * s);
-            add(1, pt_pz + s, ev_pz + 3 * s + 1);
-        }
-        for (uint32_t s = a.sets; s-- > 0;)
-            if (s + 1 != a.sets) add(last, pt_pz + s, ev_pz + 3 * s + 2);
-        for (uint32_t l = 0; l < a.NL; l++) {
-            add(0, pt_lz + l, ev_lk + 5 * l);
-            add(0, pt_lk + 2 * l, ev_lk + 5 * l + 2);
-            add(0, pt_lk + 2 * l + 1, ev_lk + 5 * l + 4);
-            add(-1, pt_lk + 2 * l, ev_lk + 5 * l + 3);
-            add(1, pt_lz + l, ev_lk + 5 * l + 1);
-        }
-    }
-    for (uint32_t i = 0; i < a.nFQ; i++) add(v->fixed_queries[i].rotation, SHARED | v->fixed_queries[i].column, a.EV_FIX + i);
-    for (uint32_t c = 0; c < a.P; c++) add(0, SHARED | (a.F + c), a.EV_SIG + c);
-    add(0, HREF, a.ev_h);
-    add(0, a.PT_RAND, EV_RAND);
-    a.nsets = (uint32_t)set_rot.size();
-    a.n_oq = (uint32_t)oq.size();
-    a.scheme = (uint32_t)v->scheme;
     const bool shplonk = v->scheme == ZG_MULTIOPEN_SHPLONK;
-    a.nW = shplonk ? 2 : a.nsets;
-    a.nL = shplonk ? 1 : a.nsets;
-    a.NP = a.PT_RAND + 1 + a.qpd + a.nW;
-    a.NT = a.NP + a.nL + a.F + a.P + 1;
-    const std::array<int, 3> table_key = {v->transcript, v->scheme, (int)NC};
+    const std::array<int, 2> table_key = {v->scheme, (int)NC};
     auto it = v->tables.find(table_key);
     if (it == v->tables.end()) {
         zg_verifier::Table t;
-        if (v->transcript == ZG_TRANSCRIPT_BLAKE2B) {
-            // items in read order: the points up to and including the h pieces | ev_h evaluations | the multi-open's points
-            const uint32_t before = a.PT_RAND + 1 + a.qpd;
-            for (uint32_t pt = 0; pt < a.NP; pt++) t.pt_off.push_back(32 * (pt + (pt >= before ? a.ev_h : 0)));
-            t.b2_len = 32 * ((uint64_t)a.NP + a.ev_h);
-        }
+        t.lay = build_layout(v->shape, NC, shplonk);
+        const ProofLayout& l = t.lay;
+        auto term = [&](const ProofLayout::Query& q) {
+            return q.fam == FIXED ? SHARED | q.index : q.fam == SIGMA ? SHARED | (a.F + q.index) : q.fam == H ? HREF : l.point_index(q.fam, q.circuit, q.index);
+        };
+        std::vector<VQuery> oq;
         if (shplonk) {
-            // construct_intermediate_sets over the same queries (`set` is the query's point so far): commitments by first
-            // appearance -- a term index names one -- with the points they are opened at; rotation sets by equal point
-            // sets, in the order of their first commitment; T = the points, numbered as GWC numbers its sets
-            ZG_REQUIRE(set_rot.size() <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "zg_verifier: %zu opening points (max %u)", set_rot.size(),
+            ZG_REQUIRE(l.rotations.size() <= PC_MAX_POINTS, ZG_ERR_UNSUPPORTED, "zg_verifier: %zu opening points (max %u)", l.rotations.size(),
                        PC_MAX_POINTS);
-            std::vector<uint32_t> com_term, com_mask, set_mask, set_count;
-            {  // a commitment's points are a SET: a (commitment, point) pair queried twice counts once, as in the prover
-                std::vector<VQuery> once;
-                for (const VQuery& q : oq) {
-                    bool dup = false;
-                    for (const VQuery& o : once) dup = dup || (o.term == q.term && o.set == q.set);
-                    if (!dup) once.push_back(q);
-                }
-                oq.swap(once);
-                a.n_oq = (uint32_t)oq.size();
-            }
-            for (const VQuery& q : oq) {
-                size_t c = 0;
-                while (c < com_term.size() && com_term[c] != q.term) c++;
-                if (c == com_term.size()) {
-                    com_term.push_back(q.term);
-                    com_mask.push_back(0);
-                }
-                com_mask[c] |= 1u << q.set;
-            }
-            std::vector<uint32_t> com_set(com_term.size()), com_j(com_term.size());
-            for (size_t c = 0; c < com_term.size(); c++) {
-                size_t i = 0;
-                while (i < set_mask.size() && set_mask[i] != com_mask[c]) i++;
-                if (i == set_mask.size()) {
-                    set_mask.push_back(com_mask[c]);
-                    set_count.push_back(0);
-                }
-                com_set[c] = (uint32_t)i;
-                com_j[c] = set_count[i]++;
-            }
-            ZG_REQUIRE(set_mask.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_verifier: %zu rotation sets (max %u)", set_mask.size(),
-                       HC_MAX_SETS);
-            std::vector<uint32_t> s_first(1, 0), f_pt;
-            for (uint32_t m : set_mask) {
-                for (uint32_t t = 0; t < set_rot.size(); t++)
-                    if (m >> t & 1u) f_pt.push_back(t);
+            ZG_REQUIRE(l.rsets.size() <= HC_MAX_SETS, ZG_ERR_UNSUPPORTED, "zg_verifier: %zu rotation sets (max %u)", l.rsets.size(), HC_MAX_SETS);
+            std::vector<uint32_t> s_first(1, 0), s_mask, f_pt;
+            for (const ProofLayout::RotationSet& s : l.rsets) {
+                s_mask.push_back(0);
+                for (uint32_t p : s.points) s_mask.back() |= 1u << p;
+                f_pt.insert(f_pt.end(), s.points.begin(), s.points.end());
                 s_first.push_back((uint32_t)f_pt.size());
             }
-            std::vector<char> seen(com_term.size(), 0);
-            for (VQuery& q : oq) {
-                size_t c = 0;
-                while (com_term[c] != q.term) c++;
-                const uint32_t i = com_set[c];
-                uint32_t f = s_first[i];
-                while (f_pt[f] != q.set) f++;
-                q.pt = f | (seen[c] ? 0u : FIRST_PT);
-                seen[c] = 1;
-                q.set = i;
-                q.vpow = com_j[c];
+            // a repeated (commitment, point) pair counts once; the commitment's own scalar goes with its first query
+            std::vector<char> seen(l.coms.size(), 0);
+            for (const ProofLayout::Query& q : l.queries) {
+                if (q.com == ProofLayout::NONE) continue;
+                const ProofLayout::Com& c = l.coms[q.com];
+                uint32_t f = s_first[c.set];
+                while (f_pt[f] != q.point) f++;
+                oq.push_back({term(q), q.eval, c.set, c.place, f | (seen[q.com] ? 0u : FIRST_PT)});
+                seen[q.com] = 1;
             }
-            std::vector<Fe> t_wr;
-            for (int64_t r : set_rot) t_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
-            t.nS = (uint32_t)set_mask.size(); t.nT = (uint32_t)set_rot.size(); t.nF = (uint32_t)f_pt.size();
+            t.nF = (uint32_t)f_pt.size();
             ZG_TRY(upload(v, &t.s_first, s_first));
-            ZG_TRY(upload(v, &t.s_mask, set_mask));
+            ZG_TRY(upload(v, &t.s_mask, s_mask));
             ZG_TRY(upload(v, &t.f_pt, f_pt));
-            ZG_TRY(upload(v, &t.t_wr, t_wr));
         } else {
             // v-powers run down within a set: the first query of a set of m gets v^(m-1)
-            for (VQuery& q : oq) q.vpow = set_size[q.set] - 1 - q.vpow;
+            for (const ProofLayout::Query& q : l.queries) oq.push_back({term(q), q.eval, q.point, 0, 0});
+            for (const std::vector<uint32_t>& set : l.at)
+                for (size_t k = 0; k < set.size(); k++) oq[set[k]].vpow = (uint32_t)(set.size() - 1 - k);
         }
         ZG_TRY(upload(v, &t.oq, oq));
-        t.n_oq = a.n_oq;
-        if (!a.set_wr) {  // (the point sets do not depend on NC)
+        t.n_oq = (uint32_t)oq.size();
+        if (!a.set_wr) {  // (the points do not depend on NC or the scheme)
             std::vector<Fe> set_wr;
-            for (int64_t r : set_rot) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)r));
+            const int64_t n = (int64_t)1 << a.log_n;
+            for (int64_t r : l.rotations) set_wr.push_back(Fr::pow_u64(a.omega, (uint64_t)(((r % n) + n) % n)));
             ZG_TRY(upload(v, &a.set_wr, set_wr));
         }
-        it = v->tables.emplace(table_key, t).first;
+        it = v->tables.emplace(table_key, std::move(t)).first;
     }
     const zg_verifier::Table& t = it->second;
+    const ProofLayout& l = t.lay;
     v->table = &t;
-    a.b2_len = t.b2_len;
+    a.NC = NC;
+    a.scheme = (uint32_t)v->scheme;
+    a.walk[0] = l.pt[ADVICE].count;
+    a.walk[1] = l.pt[PERMUTED].count;
+    a.walk[2] = l.pt[PERM_Z].count + l.pt[LOOKUP_Z].count + l.pt[RANDOM].count;
+    a.walk[3] = l.pt[H_PIECE].count;
+    a.PT_RAND = l.pt[RANDOM].first;
+    a.EV_FIX = l.ev[EV_FIXED].first; a.EV_SIG = l.ev[EV_SIGMA].first; a.EV_PZ = l.ev[EV_PERM].first; a.EV_LK = l.ev[EV_LOOKUP].first;
+    a.npz = l.ev[EV_PERM].count / NC;
+    a.ev_h = l.ev[EV_H].first;
+    a.NE = a.ev_h + 1;
+    a.nsets = (uint32_t)l.rotations.size();
+    a.nT = shplonk ? a.nsets : 0;
+    a.nW = l.pt[OPENING].count;
+    a.nL = shplonk ? 1 : a.nW;  // (the left side's terms: every W; h2)
+    a.NP = l.n_points();
+    a.NT = a.NP + a.nL + a.F + a.P + 1;
+    a.b2_len = l.bytes(true);
     a.oq = t.oq;
     a.n_oq = t.n_oq;  // (SHPLONK's table holds a repeated (commitment, point) pair once)
-    a.nS = t.nS; a.nT = t.nT; a.nF = t.nF; a.nwork = t.nT + t.nS;
-    a.s_first = t.s_first; a.s_mask = t.s_mask; a.f_pt = t.f_pt; a.t_wr = t.t_wr;
+    a.nS = (uint32_t)l.rsets.size(); a.nF = t.nF; a.nwork = a.nT + a.nS;
+    a.s_first = t.s_first; a.s_mask = t.s_mask; a.f_pt = t.f_pt;
     return ZG_OK;
 }
 
@@ -890,9 +762,10 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
     a.ifft_div = Fr::inv(Fr::from_u64(n));
     a.delta = fr_delta();
     a.vk_repr = fe_of(*vk_repr);
-    a.npz = a.sets ? 3 * a.sets - 1 : 0;
-    v->advice_queries.assign(cs->advice_queries, cs->advice_queries + a.nAQ);
-    v->fixed_queries.assign(cs->fixed_queries, cs->fixed_queries + a.nFQ);
+    ProofShape& sh = v->shape;
+    sh.A = a.A; sh.F = a.F; sh.P = a.P; sh.NL = a.NL; sh.sets = a.sets; sh.qpd = a.qpd; sh.bf = a.bf; sh.log_n = a.log_n;
+    for (uint32_t i = 0; i < a.nAQ; i++) sh.advice_queries.push_back({cs->advice_queries[i].column, cs->advice_queries[i].rotation});
+    for (uint32_t i = 0; i < a.nFQ; i++) sh.fixed_queries.push_back({cs->fixed_queries[i].column, cs->fixed_queries[i].rotation});
 
     // where each circuit query's evaluation comes from
     std::vector<uint32_t> iev_col;
@@ -1081,7 +954,7 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
         for (size_t b = 0; b < count; b++) {
             if (proof_lens[b]) std::memcpy(bytes.data() + off[b], proofs[b], proof_lens[b]);
             if (blake2b && proof_lens[b] >= a.b2_len)
-                for (uint32_t pt = 0; pt < a.NP; pt++) std::memcpy(&enc[(b * a.NP + pt) * 32], proofs[b] + v->table->pt_off[pt], 32);
+                for (uint32_t pt = 0; pt < a.NP; pt++) std::memcpy(&enc[(b * a.NP + pt) * 32], proofs[b] + 32 * (size_t)v->table->lay.item_of_point(pt), 32);
             for (size_t c = 0; c < circuits && per_inst; c++)
                 std::memcpy(inst.data() + b * per_inst + c * one_inst, instance[b * circuits + c], one_inst * sizeof(Fe));
             rb[b] = Fr::to_raw(rand_fr_host(kw, TAG_VERIFY_BATCH, b));
@@ -1102,9 +975,9 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
         if (blake2b) {
             ZG_HIP(hipMemcpyAsync(a.enc, enc.data(), enc.size(), hipMemcpyHostToDevice, st));
             ZG_TRY(g1_decompress_dev(ctx, a.enc, count * a.NP, a.pts, a.pvalid));
-            ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay_b2, dim3((uint32_t)count), dim3(64), 0, a);
+            ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay<Blake2bWalk>, dim3((uint32_t)count), dim3(64), 0, a);
         } else {
-            ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay, dim3((uint32_t)count), dim3(64), 0, a);
+            ZG_LAUNCH(ctx, "verify_replay", (double)total, verify_replay<KeccakWalk>, dim3((uint32_t)count), dim3(64), 0, a);
         }
         ZG_LAUNCH(ctx, "verify_scalars", (double)count * a.NE * 32, verify_scalars, dim3((uint32_t)count), dim3(64), 0, a);
         ZG_LAUNCH(ctx, "verify_terms", (double)count * a.NT * 96, verify_terms, dim3((uint32_t)count), dim3(TERMS_WG), 0, a);
