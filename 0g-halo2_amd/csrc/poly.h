@@ -260,6 +260,25 @@ int poly_l_cosets_init(zg_ctx* ctx, Fe* l0, Fe* llast, Fe* lblind, uint32_t n, u
 int poly_lactive(zg_ctx* ctx, Fe* lactive, const Fe* llast, const Fe* lblind, uint32_t en, bool hat);
 int poly_scale(zg_ctx* ctx, const Fe* in, Fe* out, size_t count, const Fe& factor);  // out[i] = in[i] * factor
 
+// Challenges as columns (zg_prover_set_phases): what challenge_fill_kernel writes for one phase of a batch -- the constant
+// into all n rows of each challenge's value row (the blinding rows included: the polynomial IS the constant), (c, 0, ..)
+// into its coefficient row and the constant into its slab on every part of the extended domain in use, there in the form
+// that part's readers expect (vals[..][1]: x 2^5 for the nine-limb evaluate_h).  No transform is spent on a constant.
+struct ChalFill {
+    uint32_t count = 0;                    // challenges of the phase that have a pseudo-column
+    uint32_t chal[ZG_MAX_CHALLENGES] = {};  // their indices
+    uint32_t col0 = 0;                     // pseudo-column of challenge 0 among the value rows (IU) ...
+    Fe* val = nullptr; size_t val_bs = 0;  // value rows [nb][I][n]
+    Fe* coef = nullptr; size_t coef_bs = 0;  // coefficient row of challenge 0, proof 0; proof b's coef_bs further
+    uint32_t n = 0, nparts = 0;
+    Fe* cos[2] = {nullptr, nullptr};       // slab of challenge 0, proof 0, per part in use
+    size_t cos_bs[2] = {0, 0};
+    uint32_t en[2] = {0, 0};
+    const Fe* vals = nullptr;              // [nb][stride][2]
+    uint32_t stride = 0;
+};
+int poly_challenge_fill(zg_ctx* ctx, const ChalFill& f, uint32_t nb);
+
 // from sort.hip: lookup::prover::permute_expression_pair on the device
 int poly_sort_pad(zg_ctx* ctx, Fe* keys, uint32_t n, uint32_t usable, uint32_t batch);
 int poly_sort_keys(zg_ctx* ctx, Fe* keys, uint32_t n, uint32_t batch);

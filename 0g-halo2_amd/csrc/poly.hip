@@ -2008,6 +2008,41 @@ int poly_split_combine(zg_ctx* ctx, uint32_t nb, Fe* h, size_t h_bs, const Fe* b
     return ZG_OK;
 }
 
+// ---- challenges as columns: grid (row blocks, challenges of the phase, proofs).  A challenge's rows are, one behind the
+// other, its n values, its n coefficients and its slab on each part in use; a thread stores one element (32 bytes).
+__global__ void challenge_fill_kernel(ChalFill f) {
+    const uint32_t j = f.chal[blockIdx.y], b = blockIdx.z;
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const Fe* v = f.vals + ((size_t)b * f.stride + j) * 2;
+    if (i < f.n) {
+        stg(f.val + (size_t)b * f.val_bs + (size_t)(f.col0 + j) * f.n + i, ldg(v));
+        return;
+    }
+    i -= f.n;
+    if (i < f.n) {
+        stg(f.coef + (size_t)b * f.coef_bs + (size_t)j * f.n + i, i == 0 ? ldg(v) : fe_zero());
+        return;
+    }
+    i -= f.n;
+    for (uint32_t d = 0; d < f.nparts; d++) {
+        if (i < f.en[d]) {
+            stg(f.cos[d] + (size_t)b * f.cos_bs[d] + (size_t)j * f.en[d] + i, ldg(v + 1));
+            return;
+        }
+        i -= f.en[d];
+    }
+}
+int poly_challenge_fill(zg_ctx* ctx, const ChalFill& f, uint32_t nb) {
+    if (!nb || !f.count) return ZG_OK;
+    size_t rows = (size_t)2 * f.n;
+    for (uint32_t d = 0; d < f.nparts; d++) rows += f.en[d];
+    ZG_REQUIRE(f.count <= ZG_MAX_CHALLENGES && f.nparts <= 2 && nb <= 65535 && rows < (1ull << 31), ZG_ERR_INVALID_ARG, "challenge_fill: %u challenges, %zu rows", f.count, rows);
+    ZG_LAUNCH(ctx, "challenge_fill", (double)nb * f.count * rows * 32, challenge_fill_kernel, dim3((unsigned)((rows + 255) / 256), f.count, nb),
+              dim3(256), 0, f);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
 }  // namespace zg
 
 using namespace zg;

@@ -16,6 +16,9 @@ struct ProofShape {
     uint32_t A = 0, F = 0, P = 0, NL = 0, sets = 0;  // advice, fixed, permutation columns; lookups; permutation z polynomials
     uint32_t qpd = 0, bf = 0, log_n = 0;             // h pieces, blinding factors
     std::vector<std::pair<uint32_t, int32_t>> advice_queries, fixed_queries;  // (column, rotation)
+    // create_proof's phases (ConstraintSystem::advice_column_phase / challenge_phase): the phase each advice column is
+    // committed in (empty: all in the first) and the phase after whose commitments each challenge is squeezed
+    std::vector<uint8_t> advice_phase, challenge_phase;
 };
 
 // A proof's commitments by family, in transcript order; behind them what an opening query may also name: the key's fixed
@@ -25,6 +28,11 @@ enum Family : uint32_t { ADVICE, PERMUTED, PERM_Z, LOOKUP_Z, RANDOM, H_PIECE, OP
 // A proof's evaluations by family, in transcript order: every circuit's advice | fixed, random, sigma once | every
 // circuit's permutation evaluations (set s: z, z(wx), z(w^last x) at 3s .., the last set without the third) | every
 // circuit's lookup evaluations (z, z(wx), a', a'(w^-1 x), s') | the expected h(x), which no proof holds.
+//
+// With advice phases the ADVICE family alone changes its order, for any N: phase-major, within a phase circuit-major,
+// within a circuit ascending column -- create_proof commits every circuit's columns of a phase, then squeezes that
+// phase's challenges (ascending index), then goes on to the next phase.  Evaluations and opening queries keep
+// cs.advice_queries' order; point_index() is where a column's commitment stands.
 enum EvalFamily : uint32_t { EV_ADVICE, EV_FIXED, EV_RANDOM, EV_SIGMA, EV_PERM, EV_LOOKUP, EV_H, N_EVAL_FAMILIES };
 
 struct ProofLayout {
@@ -37,8 +45,16 @@ struct ProofLayout {
     struct Com { Family fam; uint32_t circuit, index, set, place; std::vector<uint32_t> queries; };
     struct RotationSet { std::vector<uint32_t> points, coms; };
 
+    // a phase of the advice commitments: where its points end among the proof's (every circuit's share), its columns in
+    // ascending order and the challenges squeezed behind its last point, in squeeze order
+    struct Phase { uint32_t end = 0; std::vector<uint32_t> columns, challenges; };
+
     uint32_t N = 1;
     bool shplonk = false;
+    std::vector<Phase> phases;  // at least one; theta follows the last
+    // more than one phase: per advice column where its phase starts among the ADVICE points, the columns of that phase
+    // and the column's place among them (empty: the one phase holds the columns in their order)
+    std::vector<uint32_t> adv_first, adv_per, adv_place;
     Range pt[N_POINT_FAMILIES], ev[N_EVAL_FAMILIES];
     std::vector<Query> queries;             // create_proof's order
     std::vector<Query> evals;               // the same queries by evaluation index: transcript order, the expected h(x) last
@@ -52,7 +68,10 @@ struct ProofLayout {
     uint32_t n_scalars() const { return ev[EV_H].first; }
     size_t bytes(bool blake2b) const { return (size_t)(blake2b ? 32 : 64) * n_points() + (size_t)32 * n_scalars(); }
     // where commitment (fam, circuit, index) stands among the proof's points
-    uint32_t point_index(Family fam, uint32_t circuit, uint32_t index) const { return pt[fam].first + circuit * (pt[fam].count / N) + index; }
+    uint32_t point_index(Family fam, uint32_t circuit, uint32_t index) const {
+        if (fam == ADVICE && !adv_first.empty()) return pt[ADVICE].first + adv_first[index] + circuit * adv_per[index] + adv_place[index];
+        return pt[fam].first + circuit * (pt[fam].count / N) + index;
+    }
     // Blake2b transcript, a fixed layout of 32-byte items: the evaluations stand between the h pieces and the argument's points
     uint32_t item_of_point(uint32_t point) const { return point + (point >= pt[OPENING].first ? n_scalars() : 0); }
     size_t n_shplonk_pairs() const {
@@ -70,7 +89,50 @@ inline void families(const ProofShape& s, uint32_t N, uint32_t n_open, ProofLayo
     for (uint32_t f = 0, at = 0; f < N_POINT_FAMILIES; at += pc[f++]) pt[f] = {at, pc[f]};
     for (uint32_t f = 0, at = 0; f < N_EVAL_FAMILIES; at += ec[f++]) ev[f] = {at, ec[f]};
 }
+// the phases of the ADVICE family (ProofLayout::phases, adv_*)
+inline void phases(const ProofShape& s, ProofLayout& l) {
+    uint32_t last = 0;
+    for (uint32_t c = 0; c < s.A && c < s.advice_phase.size(); c++) last = s.advice_phase[c] > last ? s.advice_phase[c] : last;
+    l.phases.assign(last + 1, ProofLayout::Phase{});
+    for (uint32_t c = 0; c < s.A; c++) l.phases[c < s.advice_phase.size() ? s.advice_phase[c] : 0].columns.push_back(c);
+    for (uint32_t j = 0; j < s.challenge_phase.size(); j++) l.phases[s.challenge_phase[j] <= last ? s.challenge_phase[j] : last].challenges.push_back(j);
+    uint32_t at = l.pt[ADVICE].first;
+    for (ProofLayout::Phase& ph : l.phases) ph.end = at += l.N * (uint32_t)ph.columns.size();
+    if (last == 0) return;
+    l.adv_first.assign(s.A, 0); l.adv_per.assign(s.A, 0); l.adv_place.assign(s.A, 0);
+    uint32_t first = 0;
+    for (const ProofLayout::Phase& ph : l.phases) {
+        for (uint32_t i = 0; i < ph.columns.size(); i++) {
+            l.adv_first[ph.columns[i]] = first;
+            l.adv_per[ph.columns[i]] = (uint32_t)ph.columns.size();
+            l.adv_place[ph.columns[i]] = i;
+        }
+        first += l.N * (uint32_t)ph.columns.size();
+    }
+}
 }  // namespace layout_detail
+
+// What zg_prover_set_phases / zg_verifier_set_phases ask of a setting (upstream: advice_column_in and
+// challenge_usable_after assert that the phase before has a column): nullptr when it is legal, else what is wrong.
+// `used`: the challenges the circuit's expressions name.
+inline const char* phases_error(uint32_t A, const uint8_t* advice_phase, uint32_t used, uint32_t n_challenges, const uint8_t* challenge_phase,
+                                uint32_t max_phases, uint32_t max_challenges) {
+    if ((A && !advice_phase) || (n_challenges && !challenge_phase)) return "a phase array is null";
+    uint32_t last = 0, seen = 1;  // (phase 0 always exists)
+    for (uint32_t c = 0; c < A; c++) {
+        if (advice_phase[c] >= max_phases) return "an advice column's phase is out of range";
+        last = advice_phase[c] > last ? advice_phase[c] : last;
+        seen |= 1u << advice_phase[c];
+    }
+    if (seen != (2u << last) - 1u) return "a phase has no advice column (phases are contiguous from 0)";
+    if (n_challenges < used) return "fewer challenges than the circuit uses";
+    if (n_challenges > max_challenges) return "too many challenges";
+    for (uint32_t j = 0; j < n_challenges; j++) {
+        if (challenge_phase[j] >= max_phases) return "a challenge's phase is out of range";
+        if (challenge_phase[j] > last) return "a challenge is squeezed after a phase that has no advice column";
+    }
+    return nullptr;
+}
 
 // The bound zg_prover_proof_size{,_multi} return: the proof's length with as many W as GWC could need, one per
 // possible opening point (2 + every advice and fixed query), or SHPLONK's 2.
@@ -85,6 +147,7 @@ inline ProofLayout build_layout(const ProofShape& s, uint32_t N, bool shplonk) {
     l.N = N;
     l.shplonk = shplonk;
     layout_detail::families(s, N, 0, l.pt, l.ev);
+    layout_detail::phases(s, l);
     // ---- the opening queries; points by first appearance, rotations compared mod n as upstream compares field points
     const int64_t n = (int64_t)1 << s.log_n, last = -(int64_t)(s.bf + 1);
     std::vector<int64_t> keys;

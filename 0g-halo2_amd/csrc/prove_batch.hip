@@ -116,19 +116,22 @@ static const zg_bases* dense_g(const zg_prover* p) { return naf_of(p, p->g); }
 
 // Commitments of a phase: one MSM launch sequence over m.batch = groups x per scalar vectors (msm_dev), against this
 // prover's point range of the base sets; the XYZZ results go to the host behind it.
-int commit(zg_prover* p, MsmJob m, int wait_ix) {
-    ZG_REQUIRE(m.batch <= p->maxv * (size_t)p->cap, ZG_ERR_INVALID_ARG, "zg_prover: %zu commitments in one phase", m.batch);
+// (out_at, last: a phase made of several launch sequences -- the runs of an advice phase's columns -- leaves sequence
+//  after sequence in the results and records the event behind the last)
+int commit(zg_prover* p, MsmJob m, int wait_ix, size_t out_at = 0, bool last = true) {
+    ZG_REQUIRE(out_at + m.batch <= p->maxv * (size_t)p->cap, ZG_ERR_INVALID_ARG, "zg_prover: %zu commitments in one phase", out_at + m.batch);
+    ZG_REQUIRE(out_at == 0 || !p->rccl_comm, ZG_ERR_UNSUPPORTED, "zg_prover: advice phases on a point-range shard");
     // The last kernel of the MSM writes its sums straight into the pinned host buffer the transcript reads (the memory is
     // mapped into the device's address space): no copy command between the MSM and the host -- a command costs a lone
     // proof its dispatch latency on top of its run time, ~9 us per commitment phase.  Only the in-library RCCL exchange
     // keeps the sums on the device (all-gather and the additions follow on this stream) and copies the result out.
-    XYZZ* h_out = p->pin.dev_view(p->pin.results());
+    XYZZ* h_out = p->pin.dev_view(p->pin.results()) + out_at;
     m.scalars += p->shard_lo;
     m.n = p->shard_n;
     m.out = p->rccl_comm ? p->xyzz : h_out;
     ZG_TRY(msm_dev(p->ctx, m));
     if (p->rccl_comm) ZG_TRY(shard_gather_sum(p, m.batch, h_out));  // (over xGMI, on this stream)
-    ZG_HIP(hipEventRecord(p->evs[wait_ix], p->ctx->stream));
+    if (last) ZG_HIP(hipEventRecord(p->evs[wait_ix], p->ctx->stream));
     return ZG_OK;
 }
 // ... and waits for ONLY that launch sequence; with a sharded SRS the partial commitments of all ranks are exchanged
@@ -189,7 +192,8 @@ struct TickLog {
 // EvmTranscript and leaves the next challenges in p->hpc[] / on the device (upload_consts).  Order and contents of the phases
 // are upstream's:
 //   load_inputs        instance + advice columns in place, blinding rows, the vanishing argument's random polynomial
-//   commit_advice      advice commitments                                   -> theta
+//   commit_advice      advice commitments, phase by phase with the phase's challenges behind each (zg_prover_set_phases;
+//                      one phase and no challenge unless the circuit says otherwise)   -> theta
 //   commit_permuted    lookup::commit_permuted (+ the random polynomial)    -> beta, gamma
 //   commit_products    permutation::commit, lookup::commit_product          -> y
 //   opening_plan       (no device work) which polynomial is evaluated and opened where: proof_layout.h's order of the
@@ -212,11 +216,19 @@ struct ProveBatch {
     size_t proof_cap;
     size_t* proof_lens;
     int* statuses;
+    // zg_prover_prove_phased: the caller's witness synthesis, called at the head of every advice phase
+    zg_phase_fn phase_fn = nullptr;
+    void* phase_user = nullptr;
     // ---- shapes
     const PkDev& pk;
     zg_ctx* ctx;
     hipStream_t st;
     uint32_t nb, n, k, ek, bf, usable, A, I, P, NL, S, Q;
+    uint32_t IU, NC;  // (I = IU + NC: the caller's instance columns, then the challenges' constant columns -- PkDev::NC)
+    // the challenges squeezed so far, [nb][nch] (zero where not yet squeezed): what a phase's callback is handed
+    uint32_t nch;
+    std::vector<zg_fr> chal;
+    std::vector<Fe> chal_vals;
     // A proof of SEVERAL circuit instances (create_proof's `circuits` slice, zg_prover_prove_multi): the nb slots are the
     // circuits and there is ONE transcript, tr[0]; after every squeeze the same challenges go into every slot's scalars.
     // The slots meet in three places: the transcript's order (the absorb halves), the quotient (fold_quotients: one h,
@@ -281,6 +293,9 @@ struct ProveBatch {
           status(count, ZG_OK), shplonk(p_->multiopen == ZG_MULTIOPEN_SHPLONK) {
         n = pk.n; k = pk.k; ek = pk.ext_k; bf = pk.bf; usable = pk.usable;
         A = pk.A; I = pk.I; P = pk.P; NL = pk.NL; S = pk.sets; Q = pk.qpd;
+        IU = pk.IU; NC = pk.NC;
+        nch = (uint32_t)p->challenge_phase.size();
+        chal.assign((size_t)nb * nch, zg_fr{});
         for (Transcript& t : tr) t.blake2b = p->transcript == ZG_TRANSCRIPT_BLAKE2B;
         hat = pk.hat;
         split = pk.nparts == 3 && (!p->use_side || p->lat_split);
@@ -394,6 +409,7 @@ struct ProveBatch {
         begin();
         ZG_TRY(load_inputs());
         gated = gate_wanted();
+        if (p->phased()) ZG_TRY(opening_plan());  // (no device work: the layout states the phases)
         ZG_TRY(advice_queue());
         if (!gated) {
             ZG_TRY(advice_absorb());
@@ -444,6 +460,7 @@ struct ProveBatch {
     bool gate_wanted() {
         const int v = knob(K_LAT_GATE);
         if (shplonk) return false;  // (its second half starts from h1 on the host: the plain order)
+        if (p->phased() || phase_fn) return false;  // (a phase's witness starts from the challenges on the host)
         if (no_gate || (v < 0 ? LAT_GATE_DEFAULT : v) == 0 || !p->use_side || nb != 1 || p->world > 1 || p->rccl_comm) return false;
         if (p->warm_sig != form_sig()) return false;  // (first-use allocations and their synchronisations are behind us)
         // (a runtime that completes every launch before it submits the next one would never reach publish())
@@ -526,7 +543,7 @@ struct ProveBatch {
                 Fe* iv = p->inst_val + b * inst_bs;
                 if (p->inst_filled[b] > instance_len) ZG_HIP(hipMemsetAsync(iv, 0, inst_bs * 32, st));  // (zeroed at create)
                 p->inst_filled[b] = instance_len;
-                for (uint32_t c = 0; c < I; c++) {
+                for (uint32_t c = 0; c < IU; c++) {
                     const zg_fr* src = instance_len ? instance[b] + (size_t)c * instance_len : nullptr;
                     for (size_t i = 0; i < instance_len; i++) T(b).common_scalar(to_fe(&src[i]));
                     if (instance_len) ZG_TRY(h2d(p, iv + (size_t)c * n, src, instance_len * 32));
@@ -539,29 +556,112 @@ struct ProveBatch {
         return ZG_OK;
     }
 
-    int advice_queue() {
-        // ---- advice: commit (Lagrange basis)
-        ZG_TRY(fork());
-        if (I) {
-            const Grouping g = grouping(I, inst_bs, pp_bs);
-            ZG_TRY(ntt_batch_to_dev(sx, p->inst_val, pp_at(p->ix_inst), n, (size_t)nb * I, k, pk.omega_inv, &pk.ifft_div, &g));
-            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_inst, I));
+    // ---- the advice phases.  One phase, no challenge, no callback: the launches and waits are what they were.
+    // the columns of phase `ph` in runs of neighbours: (first column, count)
+    std::vector<std::pair<uint32_t, uint32_t>> phase_runs(uint32_t ph) const {
+        std::vector<std::pair<uint32_t, uint32_t>> runs;
+        if (!p->phased()) {
+            if (A) runs.push_back({0u, A});
+            return runs;
         }
-        if (A) {
-            ZG_TRY(commit(p, phase_msm(p->gl, adv, n, A, adv_bs), W_ADVICE));
-            const Grouping g = grouping(A, adv_bs, pp_bs);
-            ZG_TRY(ntt_batch_to_dev(sx, adv, pp_at(p->ix_adv), n, (size_t)nb * A, k, pk.omega_inv, &pk.ifft_div, &g));
-            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_adv, A));
+        for (uint32_t c : plan->lay.phases[ph].columns) {
+            if (!runs.empty() && runs.back().first + runs.back().second == c) runs.back().second++;
+            else runs.push_back({c, 1u});
+        }
+        return runs;
+    }
+    // the caller's witness of a phase (zg_prover_prove_phased): usable rows of the phase's columns, written on this stream
+    // or before the callback returns
+    int phase_witness(uint32_t ph) {
+        if (!phase_fn) return ZG_OK;
+        std::vector<void*> slots(nb);
+        for (uint32_t b = 0; b < nb; b++) slots[b] = p->adv_val + b * adv_bs;
+        const int st_fn = phase_fn(phase_user, ph, nb, chal.data(), slots.data());
+        if (st_fn != 0) {
+            (void)prover_drain(p);
+            p->in_flight = false;
+            for (uint32_t b = 0; b < nb; b++) proof_lens[b] = 0;
+            ZG_REQUIRE(false, ZG_ERR_INVALID_ARG, "zg_prover_prove_phased: the callback returned %d in phase %u", st_fn, ph);
+        }
+        return ZG_OK;
+    }
+    int advice_phase_queue(uint32_t ph) {
+        ZG_TRY(phase_witness(ph));
+        ZG_TRY(fork());
+        if (ph == 0 && IU) {
+            const Grouping g = grouping(IU, inst_bs, pp_bs);
+            ZG_TRY(ntt_batch_to_dev(sx, p->inst_val, pp_at(p->ix_inst), n, (size_t)nb * IU, k, pk.omega_inv, &pk.ifft_div, &g));
+            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_inst, IU));
+        }
+        // ---- advice: commit (Lagrange basis), one launch sequence per run of neighbouring columns, one event for the phase
+        const auto runs = phase_runs(ph);
+        size_t at = 0;
+        for (size_t r = 0; r < runs.size(); r++) {
+            const uint32_t c0 = runs[r].first, cnt = runs[r].second;
+            ZG_TRY(commit(p, phase_msm(p->gl, adv + (size_t)c0 * n, n, cnt, adv_bs), W_ADVICE, at, r + 1 == runs.size()));
+            at += (size_t)nb * cnt;
+            const Grouping g = grouping(cnt, adv_bs, pp_bs);
+            ZG_TRY(ntt_batch_to_dev(sx, adv + (size_t)c0 * n, pp_at(p->ix_adv + c0), n, (size_t)nb * cnt, k, pk.omega_inv, &pk.ifft_div, &g));
+            if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_adv + c0, cnt));
         }
         ZG_TICK("advice: queued");
         return ZG_OK;
     }
-    int advice_absorb() {
-        if (A) {
-            ZG_TRY(wait_points(p, (size_t)nb * A, pts, W_ADVICE));
+    // the phase's points into the transcripts (run r of proof b behind run r of proof b - 1, as the MSMs left them), then
+    // its challenges: squeezed, recorded for the next callback and written into their pseudo-columns
+    int advice_phase_absorb(uint32_t ph) {
+        const auto runs = phase_runs(ph);
+        size_t total = 0;
+        for (const auto& r : runs) total += (size_t)nb * r.second;
+        if (total) {
+            ZG_TRY(wait_points(p, total, pts, W_ADVICE));
             ZG_TICK("advice: points on the host");
-            for (uint32_t b = 0; b < nb; b++)
-                for (uint32_t c = 0; c < A; c++) T(b).write_point(pts[(size_t)b * A + c]);
+            for (uint32_t b = 0; b < nb; b++) {
+                size_t at = 0;
+                for (const auto& r : runs) {
+                    for (uint32_t c = 0; c < r.second; c++) T(b).write_point(pts[at + (size_t)b * r.second + c]);
+                    at += (size_t)nb * r.second;
+                }
+            }
+        }
+        if (!p->phased()) return ZG_OK;
+        const std::vector<uint32_t>& squeezed = plan->lay.phases[ph].challenges;
+        if (squeezed.empty()) return ZG_OK;
+        ChalFill f;
+        std::vector<Fe>& vals = chal_vals;  // [nb][NC][2]: the value as the rows hold it, and as the coset slabs do
+        vals.resize((size_t)nb * (NC ? NC : 1) * 2, fe_zero());
+        for (uint32_t j : squeezed) {
+            for (uint32_t b = 0; b < nb; b++) {
+                const Fe c = tr[b].squeeze();
+                memcpy(&chal[(size_t)b * nch + j], &c, 32);
+                if (j < NC) {
+                    vals[((size_t)b * NC + j) * 2] = c;
+                    vals[((size_t)b * NC + j) * 2 + 1] = hat ? Fr::mul(c, Fr9Params::c261_fe()) : c;
+                }
+            }
+            if (j < NC) f.chal[f.count++] = j;
+        }
+        if (!f.count) return ZG_OK;
+        // (every phase stages and uploads the array as it stands, behind the fills of the phase before on this stream)
+        ZG_TRY(h2d(p, p->d_chal, vals.data(), vals.size() * sizeof(Fe)));
+        f.col0 = IU;
+        f.val = p->inst_val; f.val_bs = inst_bs;
+        f.coef = pp_at(p->ix_inst + IU); f.coef_bs = pp_bs;
+        f.n = n;
+        for (uint32_t di = dlo; di < dhi; di++) {
+            f.cos[f.nparts] = p->dbuf[di].cos + (size_t)(A + IU) * pk.dom[di].en;
+            f.cos_bs[f.nparts] = (size_t)p->ncos * pk.dom[di].en;
+            f.en[f.nparts++] = pk.dom[di].en;
+        }
+        f.vals = p->d_chal; f.stride = NC;
+        return poly_challenge_fill(ctx, f, nb);
+    }
+    int advice_queue() { return advice_phase_queue(0); }
+    int advice_absorb() {
+        ZG_TRY(advice_phase_absorb(0));
+        for (uint32_t ph = 1; ph < p->n_phases; ph++) {
+            ZG_TRY(advice_phase_queue(ph));
+            ZG_TRY(advice_phase_absorb(ph));
         }
         squeeze_into(&ProofConst::theta);
         ZG_TICK("theta");
@@ -744,7 +844,11 @@ struct ProveBatch {
         ZG_TRY(join());  // evaluate_h reads every coset the side stream produced
         // (throughput configuration: nothing overlaps, so every witness polynomial goes to its cosets here, in one batch per
         //  coset, instead of phase by phase)
-        if (!phase_cosets) ZG_TRY(to_cosets(ctx, p->ix_adv, p->ncos));
+        if (!phase_cosets && !NC) ZG_TRY(to_cosets(ctx, p->ix_adv, p->ncos));
+        if (!phase_cosets && NC) {  // (the challenges' slabs are filled, not transformed: the columns on either side of them)
+            ZG_TRY(to_cosets(ctx, p->ix_adv, A + IU));
+            ZG_TRY(to_cosets(ctx, p->ix_pz, p->ncos - (A + I)));
+        }
         // ---- evaluate_h (+ division by X^n - 1) on every part of the extended domain, back to coefficients, h pieces
         for (uint32_t di = dlo; di < dhi; di++) {
             const EvalHArgs a = evalh_args(p, di);
@@ -834,7 +938,10 @@ struct ProveBatch {
         auto it = p->plans.find(key);
         if (it == p->plans.end()) {
             OpenPlan pl;
-            pl.lay = build_layout(proof_shape(pk), key.second, shplonk);
+            ProofShape shape = proof_shape(pk);
+            shape.advice_phase = p->advice_phase;
+            shape.challenge_phase = p->challenge_phase;
+            pl.lay = build_layout(shape, key.second, shplonk);
             ZG_TRY(plan_evaluations(pl));
             ZG_TRY(shplonk ? plan_shplonk(pl) : plan_gwc(pl));
             it = p->plans.emplace(key, std::move(pl)).first;
@@ -1234,9 +1341,15 @@ struct ProveBatch {
 
 static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advice_host, void* const* advice_dev,
                             const zg_fr* const* instance, size_t instance_len, const uint8_t* keys /* [count][32] */,
-                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, int* statuses) {
+                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, int* statuses, zg_phase_fn phase_fn = nullptr,
+                            void* phase_user = nullptr) {
     ZG_REQUIRE(p && proofs && proof_lens && keys, ZG_ERR_INVALID_ARG, "zg_prover_prove: null argument");
     ZG_TRY(batch_args_ok("zg_prover_prove", "proofs", p, count, instance, instance_len));
+    ZG_REQUIRE(phase_fn || p->n_phases == 1, ZG_ERR_INVALID_ARG,
+               "zg_prover_prove: the circuit has advice columns in %u phases, whose witness depends on challenges: use zg_prover_prove_phased",
+               p->n_phases);
+    ZG_REQUIRE(!p->phased() || (p->world <= 1 && !p->rccl_comm), ZG_ERR_UNSUPPORTED,
+               "zg_prover_prove: advice phases and challenges are not made on a point-range shard of the SRS");
     ZG_REQUIRE(p->multiopen != ZG_MULTIOPEN_SHPLONK || (p->world <= 1 && !p->rccl_comm), ZG_ERR_UNSUPPORTED,
                "zg_prover_prove: the SHPLONK multi-open is not made on a point-range shard of the SRS");
     ZG_REQUIRE(p->world > 1 || p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG,
@@ -1244,6 +1357,8 @@ static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
     ZG_ENTER(p->ctx);
     {
         ProveBatch job(p, count, advice_host, advice_dev, instance, instance_len, keys, proofs, proof_cap, proof_lens, statuses);
+        job.phase_fn = phase_fn;
+        job.phase_user = phase_user;
         const int st = job.run();
         if (!job.gate_gave_up) return st;
     }
@@ -1263,6 +1378,7 @@ static int prove_multi_impl(zg_prover* p, size_t circuits, const zg_fr* const* a
     ZG_REQUIRE(p && proof && proof_len && keys, ZG_ERR_INVALID_ARG, "zg_prover_prove_multi: null argument");
     *proof_len = 0;
     ZG_TRY(batch_args_ok("zg_prover_prove_multi", "circuits", p, circuits, instance, instance_len));
+    ZG_REQUIRE(!p->phased(), ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not for a circuit with challenges or advice phases");
     uint8_t* out[1] = {proof};
     if (circuits == 1) return prove_batch_impl(p, 1, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr);
     ZG_REQUIRE(p->world <= 1 && !p->rccl_comm, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not on a point-range shard of the SRS");
@@ -1299,6 +1415,14 @@ int zg_prover_prove_batch_dev(zg_prover* p, size_t count, void* const* d_advice,
                               size_t instance_len, const uint8_t* rng_keys, uint8_t* const* proofs, size_t proof_cap,
                               size_t* proof_lens, int* statuses) {
     return prove_batch_impl(p, count, nullptr, d_advice, instance, instance_len, rng_keys, proofs, proof_cap, proof_lens, statuses);
+}
+
+int zg_prover_prove_phased(zg_prover* p, size_t count, zg_phase_fn fn, void* user, const zg_fr* const* instance, size_t instance_len,
+                           const uint8_t* rng_keys, uint8_t* const* proofs, size_t* proof_lens) {
+    ZG_REQUIRE(p && fn, ZG_ERR_INVALID_ARG, "zg_prover_prove_phased: null argument");
+    // (the slots hold the columns: the callback writes them, phase by phase)
+    return prove_batch_impl(p, count, nullptr, nullptr, instance, instance_len, rng_keys, proofs, zg_prover_proof_size(p), proof_lens, nullptr, fn,
+                            user);
 }
 
 int zg_prover_prove_dev(zg_prover* p, void* d_advice, const zg_fr* instance, size_t instance_len, const uint8_t rng_key[32],

@@ -37,6 +37,12 @@ struct PkDev {
     uint32_t k = 0, ext_k = 0, cs_degree = 0, bf = 0, qpd = 0;
     uint32_t n = 0, en = 0, usable = 0;
     uint32_t F = 0, A = 0, I = 0, P = 0, NL = 0, sets = 0, chunk = 0;
+    // Challenges (Expression::Challenge, ZG_CHALLENGE queries): challenge j is the instance-like column IU + j of a proof,
+    // the constant polynomial -- I = IU + NC counts them, IU is the caller's n_instance: what is hashed and uploaded.  The
+    // circuit image on the device names that column in the query's place; q_chal says which queries were challenges
+    // (ConstraintSystem::degree counts them as degree 0: classify_terms).
+    uint32_t IU = 0, NC = 0;
+    std::vector<uint8_t> q_chal;
     std::vector<zg_query> advice_queries, fixed_queries;
     DevCircuit dc{};
     std::vector<void*> owned;  // device allocations freed with the key
@@ -102,6 +108,7 @@ inline ProofShape proof_shape(const PkDev& k) {
     for (const zg_query& q : k.fixed_queries) s.fixed_queries.push_back({q.column, q.rotation});
     return s;
 }
+
 
 // ------------------------------------------------------------------ the prover's pinned arena
 // ONE block of coherent, mapped host memory that kernels write and the host reads right after an event (alloc_slots), in
@@ -202,6 +209,12 @@ struct zg_prover {
     // the interpolants' low coefficients
     int multiopen = 0;
     int transcript = 0;  // zg_prover_set_transcript: ZG_TRANSCRIPT_EVM, or halo2's Blake2b transcript with compressed points
+    // zg_prover_set_phases: the phase of every advice column (empty: one phase) and of every challenge squeezed (at least
+    // pk->NC of them; only the first pk->NC have a pseudo-column)
+    std::vector<uint8_t> advice_phase, challenge_phase;
+    uint32_t n_phases = 1;
+    zg::Fe* d_chal = nullptr;  // [cap][NC][2]: a challenge as its value / coefficient rows hold it, and as its coset slabs do
+    bool phased() const { return n_phases > 1 || !challenge_phase.empty(); }
     zg::Fe* sh_h1 = nullptr;
     uint32_t* sh_lists = nullptr;
     zg::F9* sh_coef = nullptr;

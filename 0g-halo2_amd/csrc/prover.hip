@@ -239,6 +239,8 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
     ZG_TRY(dalloc_into(own, &p->d_mlists, p->mlists_cap));
     ZG_TRY(dalloc_into(own, &p->ktmp, poly_kate_tmp_elems(n, cap * p->max_points)));
     ZG_TRY(dalloc_into(own, &p->d_pc, c));
+    p->d_chal = nullptr;
+    if (k.NC) ZG_TRY(dalloc_into(own, &p->d_chal, c * k.NC * 2));
     p->hpc.assign(cap, ProofConst{});
     // SHPLONK's buffers, while the prover is set to it: per slot h1 and PC_MAX_POINTS + 1 rows of low
     // coefficients; the lists and coefficients for the opening queries of `cap` single proofs, or of one proof of `cap`
@@ -425,6 +427,32 @@ int key_shape(PkDev* pk, const zg_ctx* ctx, const zg_circuit* cs, const zg_fr* v
     return ZG_OK;
 }
 
+// Challenges become columns: every ZG_CHALLENGE query is rewritten to the instance-like column IU + its index (`queries`
+// keeps the rewritten list alive, *out is the circuit with that list and I = IU + NC instance columns), and the key learns
+// how many there are.  A circuit without challenges comes back as it is.
+int challenge_columns(PkDev* pk, const zg_circuit* cs, std::vector<zg_query>& queries, zg_circuit* out) {
+    *out = *cs;
+    pk->IU = cs->n_instance;
+    pk->NC = 0;
+    pk->q_chal.assign(cs->n_queries, 0);
+    for (uint32_t q = 0; q < cs->n_queries; q++) {
+        if (cs->queries[q].kind != ZG_CHALLENGE) continue;
+        ZG_REQUIRE(cs->queries[q].column < ZG_MAX_CHALLENGES, ZG_ERR_INVALID_ARG, "zg_prover_create: query %u names challenge %u (max %u)", q,
+                   cs->queries[q].column, (uint32_t)ZG_MAX_CHALLENGES);
+        pk->q_chal[q] = 1;
+        pk->NC = std::max(pk->NC, cs->queries[q].column + 1);
+    }
+    for (uint32_t c = 0; c < cs->n_perm_columns; c++)
+        ZG_REQUIRE(cs->perm_columns[c].kind != ZG_CHALLENGE, ZG_ERR_INVALID_ARG, "zg_prover_create: permutation column %u is a challenge", c);
+    if (!pk->NC) return ZG_OK;
+    queries.assign(cs->queries, cs->queries + cs->n_queries);
+    for (uint32_t q = 0; q < cs->n_queries; q++)
+        if (pk->q_chal[q]) queries[q].kind = ZG_INSTANCE, queries[q].column += pk->IU;
+    out->queries = queries.data();
+    out->n_instance = pk->I = pk->IU + pk->NC;
+    return ZG_OK;
+}
+
 // the circuit image, validated; its monomials and lookups in the layout the kernels read
 int validate_circuit(const PkDev* pk, const zg_circuit* cs, std::vector<DMono>& monos, std::vector<DLookup>& lks) {
     for (uint32_t q = 0; q < cs->n_queries; q++) {
@@ -432,6 +460,10 @@ int validate_circuit(const PkDev* pk, const zg_circuit* cs, std::vector<DMono>& 
         uint32_t lim = qq.kind == ZG_FIXED ? pk->F : qq.kind == ZG_ADVICE ? pk->A : qq.kind == ZG_INSTANCE ? pk->I : 0;
         ZG_REQUIRE(qq.column < lim, ZG_ERR_INVALID_ARG, "zg_prover_create: query %u names column %u of kind %u", q,
                    qq.column, qq.kind);
+        // (a ZG_CHALLENGE query arrives here as its pseudo-column, rewritten by challenge_columns: a rotation would leave
+        //  the constant polynomial what it is, but upstream has none)
+        ZG_REQUIRE(!(q < pk->q_chal.size() && pk->q_chal[q]) || qq.rotation == 0, ZG_ERR_INVALID_ARG,
+                   "zg_prover_create: query %u rotates a challenge", q);
     }
     monos.assign(cs->n_monomials, DMono{});
     Fe one = Fr::one();
@@ -687,7 +719,11 @@ int classify_terms(PkDev* pk, const zg_circuit* cs) {
     const uint32_t low_max = m1 + 1;
     auto degree = [&](const zg_poly& q) {
         uint32_t d = 0;
-        for (uint32_t m = q.first; m < q.first + q.count; m++) d = std::max<uint32_t>(d, cs->monomials[m].n_factors);
+        for (uint32_t m = q.first; m < q.first + q.count; m++) {
+            uint32_t f = 0;  // (a challenge has degree 0, as ConstraintSystem::degree counts it)
+            for (uint32_t i = 0; i < cs->monomials[m].n_factors; i++) f += pk->q_chal[cs->monomials[m].factors[i]] ? 0u : 1u;
+            d = std::max(d, f);
+        }
         return d;
     };
     qt.gate_hi.assign(NG, 0);
@@ -872,7 +908,7 @@ int prover_drain(zg_prover* p) {
 int batch_args_ok(const char* who, const char* what, const zg_prover* p, size_t count, const zg_fr* const* instance, size_t instance_len) {
     const PkDev& pk = *p->pk;
     ZG_REQUIRE(count >= 1 && count <= p->cap, ZG_ERR_INVALID_ARG, "%s: %zu %s for %u slots (zg_prover_set_batch)", who, count, what, p->cap);
-    ZG_REQUIRE(pk.I == 0 || instance || instance_len == 0, ZG_ERR_INVALID_ARG, "%s: instance is null", who);
+    ZG_REQUIRE(pk.IU == 0 || instance || instance_len == 0, ZG_ERR_INVALID_ARG, "%s: instance is null", who);
     ZG_REQUIRE(instance_len <= pk.usable, ZG_ERR_INVALID_ARG, "%s: instance too large (Error::InstanceTooLarge)", who);
     return ZG_OK;
 }
@@ -928,6 +964,30 @@ int zg_prover_set_transcript(zg_prover* p, int transcript) {
 
 int zg_prover_transcript(const zg_prover* p) { return p ? p->transcript : ZG_TRANSCRIPT_EVM; }
 
+int zg_prover_set_phases(zg_prover* p, const uint8_t* advice_phase, uint32_t n_challenges, const uint8_t* challenge_phase) {
+    ZG_REQUIRE(p, ZG_ERR_INVALID_ARG, "zg_prover_set_phases: null prover");
+    const PkDev& pk = *p->pk;
+    const char* why = phases_error(pk.A, advice_phase, pk.NC, n_challenges, challenge_phase, ZG_MAX_PHASES, ZG_MAX_CHALLENGES);
+    ZG_REQUIRE(!why, ZG_ERR_INVALID_ARG, "zg_prover_set_phases: %s", why);
+    ZG_ENTER(p->ctx);
+    ZG_TRY(prover_drain(p));
+    p->advice_phase.assign(advice_phase, advice_phase + pk.A);
+    p->challenge_phase.assign(challenge_phase, challenge_phase + n_challenges);
+    p->n_phases = 1;
+    for (uint8_t ph : p->advice_phase) p->n_phases = std::max<uint32_t>(p->n_phases, ph + 1u);
+    p->plans.clear();  // (the layouts they hold state the phases)
+    p->warm_sig = 0;
+    return ZG_OK;
+}
+
+int zg_prover_phases(const zg_prover* p, uint8_t* advice_phase, uint32_t* n_challenges, uint8_t* challenge_phase) {
+    if (!p) return 0;
+    for (uint32_t c = 0; advice_phase && c < p->pk->A; c++) advice_phase[c] = c < p->advice_phase.size() ? p->advice_phase[c] : 0;
+    if (n_challenges) *n_challenges = (uint32_t)p->challenge_phase.size();
+    for (size_t j = 0; challenge_phase && j < p->challenge_phase.size(); j++) challenge_phase[j] = p->challenge_phase[j];
+    return (int)p->n_phases;
+}
+
 size_t zg_prover_proof_size(const zg_prover* p) { return zg_prover_proof_size_multi(p, 1); }
 
 void zg_prover_destroy(zg_prover* p) {
@@ -969,6 +1029,11 @@ static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fi
     if (p->use_side && !ctx->side) ZG_TRY(zg_ctx_create(ctx->device, &ctx->side));
     std::vector<DMono> monos;
     std::vector<DLookup> lks;
+    std::vector<zg_query> rewritten;
+    zg_circuit with_columns;
+    ZG_TRY(challenge_columns(pk, cs, rewritten, &with_columns));
+    cs = &with_columns;  // (from here on a challenge is a column)
+    p->challenge_phase.assign(pk->NC, 0);  // (the default: every challenge behind phase 0's commitments)
     ZG_TRY(validate_circuit(pk, cs, monos, lks));
     check_info(pk, cs, monos, lks);
     ZG_TRY(upload_circuit(pk, cs, monos, lks, ctx->stream));
@@ -1045,6 +1110,7 @@ int zg_prover_fork(const zg_prover* parent, zg_ctx* ctx, zg_prover** out) {
     p->qterms = parent->qterms;
     p->multiopen = parent->multiopen;
     p->transcript = parent->transcript;
+    p->advice_phase = parent->advice_phase; p->challenge_phase = parent->challenge_phase; p->n_phases = parent->n_phases;
     p->shard_lo = parent->shard_lo; p->shard_n = parent->shard_n; p->world = parent->world; p->rank = parent->rank;
     p->exchange = parent->exchange; p->exchange_user = parent->exchange_user;
     // (a communicator serialises its collectives on ONE stream: a fork does not inherit it)
@@ -1156,6 +1222,16 @@ int zg_prover_fetch_slot(zg_prover* p, size_t slot, uint32_t what, uint32_t inde
         case 4: ZG_REQUIRE(index < pk.NL, ZG_ERR_INVALID_ARG, "zg_prover_fetch: lookup %u", index);
                 src = perm + (size_t)(2 * index + 1) * n; count = n; break;
         case 5: src = hp; count = (size_t)pk.qpd * n; break;
+        case 6: case 7: case 8: case 9: case 10: {  // challenge `index` as a column: value row, coefficient row, slabs
+            ZG_REQUIRE(index < pk.NC, ZG_ERR_INVALID_ARG, "zg_prover_fetch: challenge %u of %u", index, pk.NC);
+            const uint32_t di = what - 8;
+            ZG_REQUIRE(what < 8 || (di < pk.nparts && (di == 0) == !p->last_split), ZG_ERR_INVALID_ARG,
+                       "zg_prover_fetch: the last proof did not use that part of the extended domain");
+            if (what == 6) src = p->inst_val + (slot * pk.I + pk.IU + index) * n, count = n;
+            else if (what == 7) src = p->pp + slot * (size_t)p->npp * n + (size_t)(p->ix_inst + pk.IU + index - p->nsh) * n, count = n;
+            else src = p->dbuf[di].cos + (slot * p->ncos + pk.A + pk.IU + index) * (size_t)pk.dom[di].en, count = pk.dom[di].en;
+            break;
+        }
         default: ZG_REQUIRE(false, ZG_ERR_INVALID_ARG, "zg_prover_fetch: unknown item %u", what);
     }
     ZG_REQUIRE(cap_elems >= count, ZG_ERR_INVALID_ARG, "zg_prover_fetch: need %zu elements", count);
@@ -1168,7 +1244,7 @@ int zg_prover_fetch_slot(zg_prover* p, size_t slot, uint32_t what, uint32_t inde
         ZG_HIP(hipMemcpy(out, tmp, count * 32, hipMemcpyDeviceToHost));
         return ZG_OK;
     }
-    if (what == 0 && pk.hat) {  // h on the coset is kept as x * 2^261: hand back the library form
+    if ((what == 0 || what >= 8) && pk.hat) {  // h and the slabs on a coset are kept as x * 2^261: hand back the library form
         WsScope ws(p->ctx);
         Fe* tmp = ws.get<Fe>(count);
         if (!tmp) return ZG_ERR_OOM;

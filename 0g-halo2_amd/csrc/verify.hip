@@ -44,6 +44,7 @@ constexpr uint32_t SHARED = 0x80000000u;  // query table: commitment shared by a
 constexpr uint32_t HREF = 0x7fffffffu;    // query table: the h commitment sum_i xn^i H_i
 constexpr uint32_t IEVAL = 0x80000000u;   // evaluation source: an instance evaluation slot (of the circuit at hand)
 constexpr uint32_t FIXEV = 0x40000000u;   // evaluation source: a fixed-query evaluation (shared); else: an advice query's, per circuit
+constexpr uint32_t CHALEV = 0x20000000u;  // evaluation source: a challenge of the proof's scalar record (Expression::Challenge)
 
 struct alignas(16) VMono {
     Fe coeff;
@@ -61,7 +62,8 @@ struct VQuery {
 };
 constexpr uint32_t FIRST_PT = 0x80000000u;
 
-enum { CH_THETA, CH_BETA, CH_GAMMA, CH_Y, CH_X, CH_V, CH_U, CH_SY, CH_N };  // (CH_SY: SHPLONK's y, squeezed where GWC squeezes v)
+// (CH_SY: SHPLONK's y, squeezed where GWC squeezes v; CH_CHAL + j: the circuit's challenge j, squeezed behind its phase's advice commitments)
+enum { CH_THETA, CH_BETA, CH_GAMMA, CH_Y, CH_X, CH_V, CH_U, CH_SY, CH_CHAL, CH_N = CH_CHAL + ZG_MAX_CHALLENGES };
 enum { ST_OK = 1, ST_TRAILING = 0, ST_MALFORMED = -1 };
 
 struct VArgs {
@@ -92,6 +94,9 @@ struct VArgs {
     // where the random polynomial's commitment stands among a proof's points, and where the families start among its
     // evaluations (circuit c's share follows circuit c-1's: nAQ advice, npz permutation, 5 NL lookup evaluations each)
     uint32_t NC, walk[4], PT_RAND, EV_FIX, EV_SIG, EV_PZ, EV_LK, npz;
+    // the advice phases (the layout's): walk[0] is read as ph_points[ph] points per phase, each followed by the squeezes of
+    // that phase's ph_nchal[ph] challenges, whose indices stand one phase behind the other in ph_chal
+    uint32_t n_ph, ph_points[ZG_MAX_PHASES], ph_nchal[ZG_MAX_PHASES], ph_chal[ZG_MAX_CHALLENGES];
     uint32_t log_n;
     Fe omega, ifft_div, delta, vk_repr;
     // batch
@@ -224,7 +229,8 @@ struct Blake2bWalk {
     __host__ __device__ bool at_end(const ProofIn& in) const { return fixed_len == in.len; }
 };
 
-// The walk, in the order of proof_layout.h's families: the vk and the instances | walk[0] points (advice) | theta | walk[1]
+// The walk, in the order of proof_layout.h's families: the vk and the instances | walk[0] points (advice), phase by phase
+// with the phase's challenges squeezed behind each | theta | walk[1]
 // (permuted) | beta, gamma | walk[2] (permutation z, lookup z, random) | y | walk[3] (h pieces) | x | the evaluations |
 // GWC: v, one W per point set, u; SHPLONK: y, v, h1, u, h2.  Points land in pts in that order, evaluations in ev.
 template <class Walk>
@@ -248,7 +254,10 @@ __host__ __device__ void replay_one(const VArgs& a, uint32_t b) {
     auto squeeze = [&](uint32_t c) {
         if (ok) ch[c] = w.squeeze();
     };
-    points(a.walk[0]);
+    for (uint32_t ph = 0, cj = 0; ph < a.n_ph; ph++) {
+        points(a.ph_points[ph]);
+        for (uint32_t e = 0; e < a.ph_nchal[ph]; e++) squeeze(CH_CHAL + a.ph_chal[cj++]);
+    }
     squeeze(CH_THETA);
     points(a.walk[1]);
     squeeze(CH_BETA);
@@ -308,9 +317,10 @@ __host__ __device__ Fe eval_poly(const VArgs& a, const zg_poly& p, const Fe* qe)
     return acc;
 }
 
-// (ev: the proof's evaluations; adv: circuit c's advice evaluations among them; iev: its instance evaluations)
-__host__ __device__ __forceinline__ Fe src_eval(uint32_t src, const Fe* ev, const Fe* adv, const Fe* iev, uint32_t ev_fix) {
-    return (src & IEVAL) ? iev[src & ~IEVAL] : (src & FIXEV) ? ev[ev_fix + (src & ~FIXEV)] : adv[src];
+// (ev: the proof's evaluations; adv: circuit c's advice evaluations among them; iev: its instance evaluations; ch: the
+//  proof's challenges)
+__host__ __device__ __forceinline__ Fe src_eval(uint32_t src, const Fe* ev, const Fe* adv, const Fe* iev, uint32_t ev_fix, const Fe* ch) {
+    return (src & IEVAL) ? iev[src & ~IEVAL] : (src & FIXEV) ? ev[ev_fix + (src & ~FIXEV)] : (src & CHALEV) ? ch[CH_CHAL + (src & ~CHALEV)] : adv[src];
 }
 
 __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
@@ -386,7 +396,7 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
             }
             iev[e] = Fr::mul(sum, num);
         }
-        for (uint32_t q = 0; q < a.n_queries; q++) qe[q] = src_eval(a.qsrc[q], ev, adv, iev, a.EV_FIX);
+        for (uint32_t q = 0; q < a.n_queries; q++) qe[q] = src_eval(a.qsrc[q], ev, adv, iev, a.EV_FIX, ch);
         for (uint32_t g = 0; g < a.n_gates; g++) FOLD(eval_poly(a, a.gates[g], qe));
         if (a.sets > 0) {
             const Fe* pz = ev + a.EV_PZ + circ * a.npz;  // set s: z at 3s, z(wx) at 3s + 1, z(w^last x) at 3s + 2
@@ -399,7 +409,7 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
                 Fe left = pz[3 * s + 1], right = pz[3 * s], cd = cd0;
                 const uint32_t c0 = s * a.chunk, c1 = c0 + a.chunk > a.P ? a.P : c0 + a.chunk;
                 for (uint32_t c = c0; c < c1; c++) {
-                    const Fe ce = src_eval(a.psrc[c], ev, adv, iev, a.EV_FIX);
+                    const Fe ce = src_eval(a.psrc[c], ev, adv, iev, a.EV_FIX, ch);
                     const Fe sig = ev[a.EV_SIG + c];
                     left = Fr::mul(left, Fr::add(Fr::add(Fr::mul(beta, sig), ce), gamma));
                     right = Fr::mul(right, Fr::add(Fr::add(ce, cd), gamma));
@@ -576,6 +586,16 @@ struct zg_verifier {
     ProofShape shape;                    // what the layout of a proof of NC circuits is built from
     int scheme = ZG_MULTIOPEN_GWC;       // zg_verifier_set_multiopen
     int transcript = ZG_TRANSCRIPT_EVM;  // zg_verifier_set_transcript
+    // zg_verifier_set_phases (shape.advice_phase / challenge_phase hold the setting): the challenges the circuit's
+    // expressions name, and the setting's number, which the cached tables are keyed by
+    uint32_t n_used = 0;
+    int phase_gen = 0;
+    bool phased() const { return !shape.challenge_phase.empty() || build_phases() > 1; }
+    uint32_t build_phases() const {
+        uint32_t last = 0;
+        for (uint8_t ph : shape.advice_phase) last = ph > last ? ph : last;
+        return last + 1;
+    }
     struct Table {
         ProofLayout lay;
         const VQuery* oq = nullptr;  // the layout's queries under this verifier's handles, on the device
@@ -584,7 +604,7 @@ struct zg_verifier {
         uint32_t nF = 0;
         const uint32_t *s_first = nullptr, *s_mask = nullptr, *f_pt = nullptr;
     };
-    std::map<std::array<int, 2>, Table> tables;  // the layouts made so far, by (scheme, circuits)
+    std::map<std::array<int, 3>, Table> tables;  // the layouts made so far, by (scheme, circuits, phase setting)
     const Table* table = nullptr;                // the one in use (set_circuits)
     // batch buffers, grown on demand (cap: proofs; pts / ev / sc: elements, their size per proof follows NC)
     size_t cap = 0, bytes_cap = 0, inst_cap = 0, tmp_cap = 0, pts_cap = 0, ev_cap = 0, sc_cap = 0;
@@ -665,7 +685,7 @@ Fe omega_pow(const Fe& omega, const Fe& omega_inv, int64_t r) {
 int set_circuits(zg_verifier* v, uint32_t NC) {
     VArgs& a = v->a;
     const bool shplonk = v->scheme == ZG_MULTIOPEN_SHPLONK;
-    const std::array<int, 2> table_key = {v->scheme, (int)NC};
+    const std::array<int, 3> table_key = {v->scheme, (int)NC, v->phase_gen};
     auto it = v->tables.find(table_key);
     if (it == v->tables.end()) {
         zg_verifier::Table t;
@@ -722,6 +742,12 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
     a.NC = NC;
     a.scheme = (uint32_t)v->scheme;
     a.walk[0] = l.pt[ADVICE].count;
+    a.n_ph = (uint32_t)l.phases.size();
+    for (uint32_t ph = 0, cj = 0, at = l.pt[ADVICE].first; ph < a.n_ph; at = l.phases[ph++].end) {
+        a.ph_points[ph] = l.phases[ph].end - at;
+        a.ph_nchal[ph] = (uint32_t)l.phases[ph].challenges.size();
+        for (uint32_t j : l.phases[ph].challenges) a.ph_chal[cj++] = j;
+    }
     a.walk[1] = l.pt[PERMUTED].count;
     a.walk[2] = l.pt[PERM_Z].count + l.pt[LOOKUP_Z].count + l.pt[RANDOM].count;
     a.walk[3] = l.pt[H_PIECE].count;
@@ -780,6 +806,12 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
         return (uint32_t)(iev_key.size() - 1) | IEVAL;
     };
     auto source = [&](uint32_t kind, uint32_t col, int32_t rot, uint32_t* out) {
+        if (kind == ZG_CHALLENGE) {
+            if (col >= ZG_MAX_CHALLENGES || rot != 0) return false;
+            v->n_used = std::max(v->n_used, col + 1);
+            *out = CHALEV | col;
+            return true;
+        }
         if (kind == ZG_INSTANCE) {
             *out = inst_slot(col, rot);
             return true;
@@ -798,8 +830,9 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
     for (uint32_t q = 0; q < a.n_queries; q++)
         ZG_REQUIRE(source(cs->queries[q].kind, cs->queries[q].column, cs->queries[q].rotation, &qsrc[q]),
                    ZG_ERR_INVALID_ARG, "zg_verifier_create: query %u is not among the circuit's column queries", q);
+    sh.challenge_phase.assign(v->n_used, 0);  // (the default: every challenge behind phase 0's commitments)
     for (uint32_t c = 0; c < a.P; c++)
-        ZG_REQUIRE(source(cs->perm_columns[c].kind, cs->perm_columns[c].column, 0, &psrc[c]), ZG_ERR_INVALID_ARG,
+        ZG_REQUIRE(cs->perm_columns[c].kind != ZG_CHALLENGE && source(cs->perm_columns[c].kind, cs->perm_columns[c].column, 0, &psrc[c]), ZG_ERR_INVALID_ARG,
                    "zg_verifier_create: permutation column %u has no query at the current row", c);
     a.n_iev = (uint32_t)iev_col.size();
 
@@ -909,6 +942,25 @@ int zg_verifier_set_transcript(zg_verifier* v, int transcript) {
 
 int zg_verifier_transcript(const zg_verifier* v) { return v ? v->transcript : ZG_TRANSCRIPT_EVM; }
 
+int zg_verifier_set_phases(zg_verifier* v, const uint8_t* advice_phase, uint32_t n_challenges, const uint8_t* challenge_phase) {
+    ZG_REQUIRE(v, ZG_ERR_INVALID_ARG, "zg_verifier_set_phases: null verifier");
+    const char* why = phases_error(v->a.A, advice_phase, v->n_used, n_challenges, challenge_phase, ZG_MAX_PHASES, ZG_MAX_CHALLENGES);
+    ZG_REQUIRE(!why, ZG_ERR_INVALID_ARG, "zg_verifier_set_phases: %s", why);
+    ZG_ENTER(v->ctx);
+    v->shape.advice_phase.assign(advice_phase, advice_phase + v->a.A);
+    v->shape.challenge_phase.assign(challenge_phase, challenge_phase + n_challenges);
+    v->phase_gen++;  // (the tables made so far state another order: new ones at the next verification)
+    return ZG_OK;
+}
+
+int zg_verifier_phases(const zg_verifier* v, uint8_t* advice_phase, uint32_t* n_challenges, uint8_t* challenge_phase) {
+    if (!v) return 0;
+    for (uint32_t c = 0; advice_phase && c < v->a.A; c++) advice_phase[c] = c < v->shape.advice_phase.size() ? v->shape.advice_phase[c] : 0;
+    if (n_challenges) *n_challenges = (uint32_t)v->shape.challenge_phase.size();
+    for (size_t j = 0; challenge_phase && j < v->shape.challenge_phase.size(); j++) challenge_phase[j] = v->shape.challenge_phase[j];
+    return (int)v->build_phases();
+}
+
 int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const* proofs, const size_t* proof_lens,
                              const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
     return zg_verifier_verify_multi(v, count, 1, proofs, proof_lens, instance, instance_len, key, verdicts);
@@ -919,6 +971,8 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
     ZG_REQUIRE(v && key && (count == 0 || (proofs && proof_lens && verdicts && (instance || v->a.I == 0))),
                ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: null argument");
     ZG_REQUIRE(circuits >= 1 && circuits <= 1024, ZG_ERR_INVALID_ARG, "zg_verifier_verify_multi: proofs of %zu circuits", circuits);
+    ZG_REQUIRE(circuits == 1 || !v->phased(), ZG_ERR_UNSUPPORTED,
+               "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with challenges or advice phases");
     ZG_REQUIRE(count < (1u << 24) && instance_len < (1u << 24), ZG_ERR_UNSUPPORTED,
                "zg_verifier_verify_batch: %zu proofs of %zu instance rows", count, instance_len);
     if (count == 0) return ZG_OK;

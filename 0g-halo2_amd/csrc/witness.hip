@@ -883,10 +883,18 @@ int zg_witness_run_dev(zg_witness_plan* p, const uint8_t* images, size_t count, 
     return ZG_OK;
 }
 
+// (the witness program has no field operand: a witness that depends on a challenge is not its to make -- said before
+//  anything else is asked of the call, a plan included)
+static int images_unphased(const char* who, const zg_prover* p) {
+    ZG_REQUIRE(!p || !p->phased(), ZG_ERR_UNSUPPORTED, "%s: not for a circuit with challenges or advice phases", who);
+    return ZG_OK;
+}
+
 // What zg_prover_prove_images and zg_prover_check_images share: the plan's program into the prover's slots 0..count-1.
 // slots / inst: [64]; inst[b] = the program's instance values of image b, inside `outputs`.
 static int images_into_slots(const char* who, zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, zg_fr* outputs,
                              void** slots, const zg_fr** inst) {
+    ZG_TRY(images_unphased(who, p));
     ZG_REQUIRE(count >= 1 && count <= zg_prover_batch(p) && count <= 64, ZG_ERR_INVALID_ARG,
                "%s: %zu images for a prover of %zu slots (64 at most per call)", who, count, zg_prover_batch(p));
     for (size_t b = 0; b < count; b++) {
@@ -913,6 +921,7 @@ static int images_into_slots(const char* who, zg_prover* p, zg_witness_plan* pla
 
 int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, const uint8_t* rng_keys,
                            uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses) {
+    ZG_TRY(images_unphased("zg_prover_prove_images", p));
     ZG_REQUIRE(p && plan && images && rng_keys && proofs && proof_lens && (outputs || !plan->n_instance), ZG_ERR_INVALID_ARG,
                "zg_prover_prove_images: null argument");
     void* slots[64];

@@ -101,7 +101,41 @@ ABI_SYMBOLS = [
     "zg_prover_set_multiopen", "zg_prover_multiopen", "zg_verifier_set_multiopen", "zg_verifier_multiopen",
     "zg_prover_set_transcript", "zg_prover_transcript", "zg_verifier_set_transcript", "zg_verifier_transcript",
     "zg_g1_compress", "zg_g1_decompress", "zg_g1_decompress_dev",
+    "zg_prover_set_phases", "zg_prover_phases", "zg_prover_prove_phased", "zg_verifier_set_phases", "zg_verifier_phases",
 ]
+
+# zg_query.kind of an Expression::Challenge, and the limits of zg_prover_set_phases
+CHALLENGE, MAX_CHALLENGES, MAX_PHASES = 3, 16, 3
+# zg_phase_fn: int fn(void *user, uint32_t phase, size_t count, const zg_fr *challenges, void *const *d_advice)
+PHASE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_uint32, c_size_t, c_void_p, ctypes.POINTER(c_void_p))
+_hip = None
+
+
+def _hip_runtime():
+    """The HIP runtime the library itself runs on (already loaded with it), for the copies of Prover.prove_phased."""
+    global _hip
+    if _hip is None:
+        _hip = ctypes.CDLL("libamdhip64.so")
+        _hip.hipMemcpy.argtypes = [c_void_p, c_void_p, c_size_t, c_int]
+    return _hip
+
+
+def _set_phases(fn, handle, n_advice, advice_phase, challenge_phase):
+    adv = np.ascontiguousarray(advice_phase if advice_phase is not None else [], dtype=np.uint8)
+    chal = np.ascontiguousarray(challenge_phase if challenge_phase is not None else [], dtype=np.uint8)
+    if adv.size != n_advice:
+        raise ValueError(f"{adv.size} advice phases for {n_advice} advice columns")
+    fn.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p]
+    _check(fn(handle, _ptr(adv) if adv.size else None, c_uint32(chal.size), _ptr(chal) if chal.size else None))
+
+
+def _phases(fn, handle, n_advice):
+    adv = np.zeros(max(n_advice, 1), np.uint8)
+    chal = np.zeros(MAX_CHALLENGES, np.uint8)
+    nch = c_uint32(0)
+    fn.argtypes = [c_void_p, c_void_p, ctypes.POINTER(c_uint32), c_void_p]
+    n = int(fn(handle, _ptr(adv), ctypes.byref(nch), _ptr(chal)))
+    return n, [int(x) for x in adv[:n_advice]], [int(x) for x in chal[: nch.value]]
 
 # zg_prover_set_multiopen / zg_verifier_set_multiopen: the multi-open argument a proof ends with
 MULTIOPEN_GWC, MULTIOPEN_SHPLONK = 0, 1
@@ -847,6 +881,70 @@ class Prover:
         self.ctx.lib.zg_prover_transcript.argtypes = [c_void_p]
         return int(self.ctx.lib.zg_prover_transcript(self.h))
 
+    def set_phases(self, advice_phase, challenge_phase):
+        """zg_prover_set_phases: the phase of every advice column and of every challenge squeezed (lists of small ints)."""
+        _set_phases(self.ctx.lib.zg_prover_set_phases, self.h, self.n_advice, advice_phase, challenge_phase)
+
+    @property
+    def phases(self):
+        """zg_prover_phases: (number of phases, advice phases, challenge phases)."""
+        return _phases(self.ctx.lib.zg_prover_phases, self.h, self.n_advice)
+
+    def prove_phased_c(self, fn_ptr, instances, seeds, user: int = 0, raise_on_error=True):
+        """zg_prover_prove_phased with a zg_phase_fn given as a PHASE_FN object or the address of a C function."""
+        count = len(seeds)
+        insts, inst_len = [], 0
+        for b in range(count):
+            i, inst_len = self._inst(instances[b])
+            insts.append(i)
+        inst_ptrs = (c_void_p * count)(*[c_void_p(i.ctypes.data) for i in insts])
+        keys = b"".join(rng_key(s) for s in seeds)
+        bufs = [(ctypes.c_uint8 * self.proof_cap)() for _ in range(count)]
+        out_ptrs = (c_void_p * count)(*[ctypes.addressof(b) for b in bufs])
+        lens = (c_size_t * count)()
+        fn = fn_ptr if isinstance(fn_ptr, PHASE_FN) else ctypes.cast(fn_ptr, PHASE_FN)
+        lib = self.ctx.lib
+        lib.zg_prover_prove_phased.argtypes = [c_void_p, c_size_t, PHASE_FN, c_void_p, c_void_p, c_size_t, ctypes.c_char_p, c_void_p, c_void_p]
+        st = lib.zg_prover_prove_phased(self.h, c_size_t(count), fn, c_void_p(user), inst_ptrs, c_size_t(inst_len), keys, out_ptrs, lens)
+        if st != 0 and raise_on_error:
+            _check(st)
+        return [bytes(bufs[b][: lens[b]]) for b in range(count)], st
+
+    def prove_phased(self, synthesize, instances, seeds, raise_on_error=True):
+        """zg_prover_prove_phased with the witness made by a Python function: synthesize(phase, challenges) is called once
+        per phase with challenges uint64[count, n_challenges, 4] (Montgomery limbs, zero where not yet squeezed) and returns,
+        per proof, a dict {advice column: uint64[rows, 4]} of the columns of that phase, rows >= the usable rows; their
+        usable rows are copied into the proof's slot before the call returns to the library (the blinding rows are the
+        library's).  An exception, or a column outside 0 .. n_advice, aborts the batch (status -1).  Returns (proofs, status)."""
+        count = len(seeds)
+        n, hip = self.n, _hip_runtime()
+        usable = n - (self.image.c.blinding_factors + 1)
+        nch = len(self.phases[2])
+
+        def _cb(_user, phase, cnt, challenges, d_advice):
+            try:
+                ch = np.zeros((cnt, nch, 4), np.uint64)
+                if nch:
+                    ctypes.memmove(ch.ctypes.data, challenges, ch.nbytes)
+                cols = synthesize(int(phase), ch)
+                for b in range(cnt):
+                    for col, values in cols[b].items():
+                        if not 0 <= int(col) < self.n_advice:
+                            return 2
+                        v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)[:usable]
+                        if v.shape[0] != usable:
+                            return 3
+                        if hip.hipMemcpy(c_void_p(d_advice[b] + int(col) * n * 32), c_void_p(v.ctypes.data), c_size_t(v.nbytes), 1) != 0:
+                            return 4
+                return 0
+            except Exception:  # noqa: BLE001 -- nothing may propagate through the C frames
+                import traceback
+
+                traceback.print_exc()
+                return 1
+
+        return self.prove_phased_c(PHASE_FN(_cb), instances, seeds, raise_on_error=raise_on_error)
+
     @property
     def batch(self) -> int:
         return int(self.ctx.lib.zg_prover_batch(self.h))
@@ -1223,6 +1321,14 @@ class Verifier:
     def transcript(self) -> int:
         self.ctx.lib.zg_verifier_transcript.argtypes = [c_void_p]
         return int(self.ctx.lib.zg_verifier_transcript(self.h))
+
+    def set_phases(self, advice_phase, challenge_phase):
+        """zg_verifier_set_phases: the phases the proofs were made in (Prover.set_phases' arguments)."""
+        _set_phases(self.ctx.lib.zg_verifier_set_phases, self.h, self.image.c.n_advice, advice_phase, challenge_phase)
+
+    @property
+    def phases(self):
+        return _phases(self.ctx.lib.zg_verifier_phases, self.h, self.image.c.n_advice)
 
     def verify(self, proofs, instances, key) -> list:
         """Verdict per proof: 1 accepted, 0 rejected, < 0 malformed.  instances[b]: uint64[n_instance, len, 4];

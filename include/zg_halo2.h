@@ -434,12 +434,14 @@ int zg_ctx_coset_generator(zg_ctx *ctx, zg_fr *out);
  * 4 lookups and 8 permutation columns.  Every polynomial (gate, lookup input, lookup table) is given
  * in expanded form sum_m coeff_m * prod_f cell(query_f): exact over the field, so the value is the
  * one halo2's Expression tree / GraphEvaluator computes. */
-enum { ZG_FIXED = 0, ZG_ADVICE = 1, ZG_INSTANCE = 2 };
+enum { ZG_FIXED = 0, ZG_ADVICE = 1, ZG_INSTANCE = 2, ZG_CHALLENGE = 3 };
 enum { ZG_MAX_FACTORS = 8, ZG_MAX_LOOKUP_WIDTH = 4 };
+/* create_proof's phases (FirstPhase / SecondPhase / ThirdPhase) and Expression::Challenge: see zg_prover_set_phases */
+enum { ZG_MAX_CHALLENGES = 16, ZG_MAX_PHASES = 3 };
 
 typedef struct {
-    uint32_t kind;      /* ZG_FIXED / ZG_ADVICE / ZG_INSTANCE */
-    uint32_t column;
+    uint32_t kind;      /* ZG_FIXED / ZG_ADVICE / ZG_INSTANCE, or ZG_CHALLENGE: Expression::Challenge(column), rotation 0 */
+    uint32_t column;    /* (ZG_CHALLENGE: the challenge's index, < ZG_MAX_CHALLENGES; a circuit has 1 + the largest index used) */
     int32_t rotation;   /* Rotation(i32): row offset in the 2^k domain */
 } zg_query;
 
@@ -577,6 +579,51 @@ int zg_prover_prove(zg_prover *p, const zg_fr *advice, const zg_fr *instance, si
 int zg_prover_prove_dev(zg_prover *p, void *d_advice, const zg_fr *instance, size_t instance_len,
                         const uint8_t rng_key[32], uint8_t *proof, size_t proof_cap, size_t *proof_len);
 
+/* Advice phases and challenges: create_proof's multi-phase schedule (halo2_proofs v2023_04_20 src/plonk/prover.rs;
+ * ConstraintSystem::advice_column_in, challenge_usable_after, Expression::Challenge).  After the vk
+ * scalar and the instances the prover runs, for each phase in ascending order: the commitments of the advice columns of
+ * that phase (ascending column) into the transcript, then one squeeze per challenge of that phase (ascending index).
+ * theta follows the last phase.  Only the ORDER OF THE ADVICE COMMITMENTS at the head of a proof depends on the phases:
+ * evaluations, opening queries and the proof's length do not.  A ZG_CHALLENGE query evaluates to its challenge and has
+ * degree 0; it may stand in gates, lookup inputs and lookup tables.
+ *
+ * advice_phase: [n_advice] phases (may be NULL without advice columns); challenge_phase: [n_challenges] the phase after
+ * which each challenge is squeezed.  Before the call every advice column is in phase 0 and every challenge the circuit
+ * uses is squeezed after phase 0.  ZG_ERR_INVALID_ARG, and nothing changes, when a phase is >= ZG_MAX_PHASES, when a phase
+ * up to the last one used has no advice column (phases are contiguous from 0), when n_challenges is smaller than the
+ * circuit's count (1 + the largest index a ZG_CHALLENGE query names) or larger than ZG_MAX_CHALLENGES, or when a
+ * challenge's phase is greater than the last advice phase.  A fork starts with its parent's setting; the cached opening
+ * plans / query tables are made anew after a call.  The getter returns the number of phases (0 for a null object) and
+ * copies the setting: advice_phase [n_advice], *n_challenges, challenge_phase [ZG_MAX_CHALLENGES]; each may be NULL.
+ *
+ * Inside the library challenge j is an instance-like column behind the caller's n_instance ones -- the constant
+ * polynomial, filled by one kernel per phase (value row, coefficient row, coset slabs), never hashed, committed or opened
+ * -- so every kernel reads it as it reads any column.  The arithmetic-level entries that take instance families over the
+ * prover's circuit (zg_prover_evaluate_h*, zg_prover_lookup_compress_dev) therefore expect n_instance + challenges columns
+ * from the caller, the challenges' constant columns last.  Each challenge costs a slot one value row, one coefficient row
+ * and one slab per part of the extended domain.
+ *
+ * On a circuit with a challenge or a phase > 0: zg_prover_prove, _dev, _batch, _batch_dev work while every advice column
+ * is in phase 0 (the witness cannot depend on a challenge then) and return ZG_ERR_INVALID_ARG otherwise (use
+ * zg_prover_prove_phased); zg_prover_prove_multi*, zg_prover_prove_images*, zg_prover_check_*, zg_verifier_verify_multi
+ * with more than one circuit and a point-range shard are ZG_ERR_UNSUPPORTED; the ZG_LAT_GATE gate stays off. */
+int zg_prover_set_phases(zg_prover *p, const uint8_t *advice_phase, uint32_t n_challenges, const uint8_t *challenge_phase);
+int zg_prover_phases(const zg_prover *p, uint8_t *advice_phase, uint32_t *n_challenges, uint8_t *challenge_phase);
+/* create_proof's phase loop for a batch of `count` proofs whose witness is synthesised phase by phase.  The library
+ * calls fn(user, phase, count, challenges, d_advice) once per phase, phase 0 included, before it commits that phase's
+ * columns: challenges is [count][n_challenges] (Montgomery form, zero where not yet squeezed), d_advice[b] the device
+ * address of proof b's slot, [n_advice][2^k] (zg_prover_advice_slot).  The callback writes the USABLE rows (the first
+ * 2^k - blinding_factors - 1) of the columns of `phase` and nothing else: the blinding rows hold the proof's blinding
+ * scalars already (the same rand_fr tag and index per column and row as every other entry draws), and the columns of
+ * earlier phases are committed.  It orders its writes on zg_ctx_stream(ctx) or completes them before it returns.  A
+ * non-zero return aborts the batch with ZG_ERR_INVALID_ARG, the queue drained.  The context's lock is held across the
+ * callback: it must not call zg_prover_prove* on the same prover (or its context) from another thread and wait for it.
+ * proofs[b] must hold zg_prover_proof_size(p) bytes.  A circuit without challenges, in one phase, gives zg_prover_prove's
+ * bytes and launches. */
+typedef int (*zg_phase_fn)(void *user, uint32_t phase, size_t count, const zg_fr *challenges, void *const *d_advice);
+int zg_prover_prove_phased(zg_prover *p, size_t count, zg_phase_fn fn, void *user, const zg_fr *const *instance,
+                           size_t instance_len, const uint8_t *rng_keys, uint8_t *const *proofs, size_t *proof_lens);
+
 /* Point-range shard of the commitments across `world` GPUs (one process and one prover per GPU):
  * this prover's base sets hold points [first_point, first_point + zg_bases_len) of ParamsKZG::g / ::g_lagrange, it
  * multiplies only that range of every scalar vector, and per commitment phase the ranks exchange their partial sums
@@ -605,7 +652,10 @@ size_t zg_prover_proof_size(const zg_prover *p);
 /* Test hook: copies an intermediate of the LAST proof to the host.  what: 0 = h(X) on the extended
  * coset after the division by (X^n - 1) [2^ext_k], 1 = permutation z (index = set) [2^k Lagrange],
  * 2 = lookup z (index = lookup) [2^k Lagrange], 3 = permuted input a' (index = lookup),
- * 4 = permuted table s' (index = lookup), 5 = h pieces in coefficient form [5 * 2^k]. */
+ * 4 = permuted table s' (index = lookup), 5 = h pieces in coefficient form [5 * 2^k].  The pseudo-column of
+ * challenge `index` (zg_prover_set_phases): 6 = its value row [2^k], 7 = its coefficient row [2^k], 8 = its slab on the
+ * single extended coset [2^ext_k], 9 / 10 = its slabs on the first / second part of the split domain; the slabs in
+ * plain Montgomery form, and only for the extended domain the last proof used (else ZG_ERR_INVALID_ARG). */
 int zg_prover_fetch(zg_prover *p, uint32_t what, uint32_t index, zg_fr *out, size_t cap_elems);
 /* ... of proof `slot` of the last batch. */
 int zg_prover_fetch_slot(zg_prover *p, size_t slot, uint32_t what, uint32_t index, zg_fr *out, size_t cap_elems);
@@ -940,6 +990,13 @@ int zg_verifier_multiopen(const zg_verifier *v);
  * nothing changes. */
 int zg_verifier_set_transcript(zg_verifier *v, int transcript);
 int zg_verifier_transcript(const zg_verifier *v);
+/* The phases of the proofs handed to zg_verifier_verify_batch: zg_prover_set_phases' arguments, defaults, conditions and
+ * getter.  The transcript walk reads each phase's advice commitments, then squeezes that phase's challenges, and the
+ * expected h(x) takes a ZG_CHALLENGE query from them.  A verifier without the call reads every advice commitment before
+ * the challenges, so it rejects a proof made in several phases.  zg_verifier_verify_multi with more than one circuit is
+ * ZG_ERR_UNSUPPORTED for a circuit with a challenge or a phase > 0. */
+int zg_verifier_set_phases(zg_verifier *v, const uint8_t *advice_phase, uint32_t n_challenges, const uint8_t *challenge_phase);
+int zg_verifier_phases(const zg_verifier *v, uint8_t *advice_phase, uint32_t *n_challenges, uint8_t *challenge_phase);
 /* Host helper (no device): *result = 1 iff prod_i e(p[i], q[i]) = 1 in GT (BN254 optimal ate pairing); identity
  * points contribute 1.  The points are taken to be in G1 and G2.  bn256::multi_miller_loop + final_exponentiation. */
 int zg_pairing_check(const zg_g1_affine *p, const zg_g2_affine *q, size_t n, int *result);

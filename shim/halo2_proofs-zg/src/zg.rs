@@ -118,7 +118,9 @@ fn expand(e: &Expression<Fr>, q: &mut Queries) -> Option<Poly> {
             r.retain(|_, v| !bool::from(v.is_zero()));
             r
         }
-        Expression::Selector(_) | Expression::Challenge(_) => return None, // not compressed / multi-phase: stock prover
+        // (not compressed: stock prover.  A challenge: the C side has ZG_CHALLENGE queries and zg_prover_prove_phased now;
+        //  this glue does not drive them yet and stays on the stock prover)
+        Expression::Selector(_) | Expression::Challenge(_) => return None,
     })
 }
 
@@ -153,6 +155,8 @@ fn column_query(c: &Column<AnyColumn>) -> zg_query {
 }
 
 fn flatten(cs: &ConstraintSystem<Fr>) -> Option<Flat> {
+    // (several phases: the C side has zg_prover_set_phases / zg_prover_prove_phased; this glue
+    //  does not drive them yet and falls back to the stock prover)
     if cs.num_challenges() != 0 || cs.phases().count() != 1 {
         return None;
     }
