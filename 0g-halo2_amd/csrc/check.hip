@@ -410,6 +410,7 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
     ZG_ENTER(ctx);
     PkDev& v = *p->pk;  // (the key: the circuit's shape, its tables, the fixed and sigma values)
     ZG_REQUIRE(!p->phased(), ZG_ERR_UNSUPPORTED, "zg_prover_check: not for a circuit with challenges or advice phases (the check knows no challenge values)");
+    ZG_REQUIRE(p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "zg_prover_check: not for a circuit with shuffles (the totals have no place for a shuffle's)");
     ZG_TRY(batch_args_ok("zg_prover_check", "witnesses", p, count, instance, instance_len));
     if (v.I && instance_len)
         for (size_t b = 0; b < count; b++) ZG_REQUIRE(instance[b], ZG_ERR_INVALID_ARG, "zg_prover_check: instance %zu is null", b);

@@ -69,6 +69,8 @@ struct alignas(16) ProofConst {
     Fe points[PC_MAX_POINTS + 1];  // opening points x * omega^rotation, by slot; the last one: SHPLONK's u (PC_U_SLOT)
     Fe subs[PC_MAX_POINTS];     // eval_batch of GWC point set s
     Fe fold_w;                  // a proof of several circuits: the weight of this slot's quotient in the proof's (poly_fold_slots)
+    // the shuffle pass over h (poly_shuffle_h), library form: y, and y^(3 NS), by which the terms before the shuffles' move up
+    Fe sh_y, sh_ypow;
 };
 
 struct EvalHArgs {
@@ -141,7 +143,8 @@ enum {
     TAG_RANDOM_POLY = 6,
     TAG_VERIFY_BATCH = 7,  // the verifier's batch weights r_b (verify.hip), not a blinding scalar
     TAG_SRS_POWERS = 8,    // zg_params_check: the weights r_i of the powers relation (params.hip)
-    TAG_SRS_LAGRANGE = 9   // zg_params_check: the coefficients c_j of the Lagrange relation
+    TAG_SRS_LAGRANGE = 9,  // zg_params_check: the coefficients c_j of the Lagrange relation
+    TAG_SHUFFLE_Z = 10     // the blinding rows of shuffle j's product: index j * rows + row
 };
 inline Fe to_fe(const zg_fr* s) {
     Fe r;
@@ -194,6 +197,18 @@ size_t poly_grand_product_tmp_elems(uint32_t n, uint32_t batch);
 // host inversion of the totals -- a stream synchronisation -- and the apply launch): the two halves of one call, same arguments.
 int poly_grand_product(zg_ctx* ctx, const Fe* num, const Fe* den, const Fe* d_z0, Fe* z, Fe* tmp, uint32_t n,
                        uint32_t batch, uint32_t chain, uint32_t last, uint32_t per = 0, size_t z_outer = 0, int half = 0);
+// what zg_prover_create*_shuffles and zg_verifier_create_shuffles ask of the shuffles, before anything is allocated
+// (who: the entry's name; cs: the caller's circuit, a challenge still a ZG_CHALLENGE query)
+int shuffles_ok(const char* who, const zg_circuit* cs, const zg_shuffle* shuffles, uint32_t n_shuffles);
+// The shuffle arguments' grand-product terms: product q = b * ns + j of the batch (shuffle j of proof b) gets
+// num[q][row] = a + gamma, den[q][row] = s + gamma, a and s the theta-folds of shuffles[j]'s inputs / tables on the value rows
+int poly_shuffle_terms(zg_ctx* ctx, const DevCircuit& c, const DLookup* shuffles, uint32_t ns, const Cols& cols, const ProofConst* pc,
+                       uint32_t nb, Fe* num, Fe* den, uint32_t n);
+// The shuffle arguments' share of the quotient, a pass over h behind evaluate_h on one part of the extended domain:
+// h <- h y^(3 ns) + (sum over the shuffles, folded by y, of l0 (1 - z), l_last (z^2 - z), l_active (z(wX) (s + gamma) - z (a + gamma))) t_eval
+// a: evaluate_h's arguments for that part (columns, l-polynomials, t_eval, pc, strides, h; with h_hi the same pass over it);
+// sz_cos: shuffle 0's product slab of proof 0 (shuffle j's en further, proof b's a.cos_bs further)
+int poly_shuffle_h(zg_ctx* ctx, const EvalHArgs& a, const DLookup* shuffles, uint32_t ns, const Fe* sz_cos, uint32_t en, uint32_t nb);
 // n_columns = advice + instance + fixed columns of the circuit, unit_share = the rows of EvaluationDomain's extended domain
 // this launch stands for (both only shape the profile's byte charges); mode: every term into h, or the terms by degree
 // (EvalHArgs::gate_cls -- the grouped nine-limb kernel only)

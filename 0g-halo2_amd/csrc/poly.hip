@@ -273,6 +273,37 @@ int poly_lookup_terms(zg_ctx* ctx, const ProofConst* pc, uint32_t nb, const Fe* 
     return ZG_OK;
 }
 
+// shuffle commit_product: num = a + gamma, den = s + gamma, a and s the theta-folds of the input and the shuffle tuple
+// (shuffle j = blockIdx.y of proof b = blockIdx.z, outputs at product (b * ns + j) * n: poly_grand_product's batch layout)
+__global__ __launch_bounds__(256) void shuffle_terms_kernel(DevCircuit c, const DLookup* __restrict__ shuffles, Cols cols_all,
+                                                            const ProofConst* __restrict__ pc, Fe* num, Fe* den, uint32_t n) {
+    const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = blockIdx.y, b = blockIdx.z;
+    if (row >= n) return;
+    const Cols cols = cols_of(cols_all, b);
+    const Fe theta = pc[b].theta, gamma = pc[b].gamma;
+    const DLookup* sf = shuffles + j;
+    Fe ai = fe_zero(), si = fe_zero();
+    for (uint32_t e = 0; e < sf->width; e++) {  // (the first expression enters as it is, as the lookups' does)
+        const Fe in = eval_poly(c, cols, sf->inputs[e], row), sh = eval_poly(c, cols, sf->tables[e], row);
+        ai = e ? Fr::add(Fr::mul(ai, theta), in) : in;
+        si = e ? Fr::add(Fr::mul(si, theta), sh) : sh;
+    }
+    const size_t o = (size_t)(b * gridDim.y + j) * n + row;
+    stg(num + o, Fr::add(ai, gamma));
+    stg(den + o, Fr::add(si, gamma));
+}
+
+int poly_shuffle_terms(zg_ctx* ctx, const DevCircuit& c, const DLookup* shuffles, uint32_t ns, const Cols& cols, const ProofConst* pc,
+                       uint32_t nb, Fe* num, Fe* den, uint32_t n) {
+    if (!ns || !nb) return ZG_OK;
+    ZG_REQUIRE(shuffles && pc && num && den, ZG_ERR_INVALID_ARG, "shuffle_terms: null argument");
+    ZG_LAUNCH(ctx, "shuffle_terms", (double)nb * ns * n * 128, shuffle_terms_kernel, dim3((n + 255) / 256, ns, nb), dim3(256), 0, c,
+              shuffles, cols, pc, num, den, n);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
 // permutation commit, one set per blockIdx.y:
 //   den = prod_c (v_c + beta*sigma_c + gamma),  num = prod_c (v_c + delta^c * omega^i * beta + gamma)
 // (set0: the column set blockIdx.y = 0 stands for -- the stand-alone entry asks for ONE set, written as product 0)
@@ -1249,6 +1280,68 @@ int poly_evaluate_h(zg_ctx* ctx, const EvalHArgs& a, uint32_t en, uint32_t nb, u
         ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h9_kernel<false>, dim3((en + 255) / 256 * nb), dim3(256), 0, a, en, nb);
     else
         ZG_LAUNCH_U(ctx, "evaluate_h", nb * arrays * en * 32.0, unit, evaluate_h_kernel, dim3((en + 255) / 256, nb), dim3(256), 0, a, en);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+// ------------------------------------------------------------------ the shuffle arguments' share of the quotient
+// eval_poly on coset slabs that may carry the nine-limb form's factor 2^5 (hat): every cell read is brought back to the
+// library form by one product with 2^-5, so the expression comes out in the library form whatever its monomials' degrees
+struct LoadUnhat {
+    bool hat;
+    Fe unhat;
+    __device__ __forceinline__ Fe operator()(const Fe* p) const {
+        const Fe v = ldg(p);
+        return hat ? Fr::mul(v, unhat) : v;
+    }
+};
+// One lane per point of the part, proof b = blockIdx.y.  h (and h_hi, where the terms by degree keep the high terms'
+// sum beside it) is read once and written once; y^(3 ns) and y come from the proof's scalars, wave-uniform.  No LDS, no
+// atomics.  The sum of the shuffles' terms is formed in the library form and leaves through t_eval, which carries the
+// slabs' factor where they have one -- so the sum lands in h's form.
+__global__ __launch_bounds__(256) void shuffle_h_kernel(EvalHArgs a, const DLookup* __restrict__ shuffles, uint32_t ns,
+                                                        const Fe* __restrict__ sz_cos, uint32_t en, Fe unhat) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= en) return;
+    const uint32_t b = blockIdx.y;
+    const ProofConst* pc = a.pc + b;
+    const Cols cols = cols_of(a.cols, b);
+    const Fe y = pc->sh_y, gamma = pc->gamma, theta = pc->theta;
+    const uint32_t r_next = (idx + (uint32_t)a.cols.rot_scale) & (en - 1);
+    const LoadUnhat ld{a.hat, unhat};
+    const Fe l0 = ld(a.l0 + idx), llast = ld(a.llast + idx), lactive = ld(a.lactive + idx);
+    const Fe* zc = sz_cos + (size_t)b * a.cos_bs;
+    Fe value = fe_zero();
+    for (uint32_t j = 0; j < ns; j++, zc += en) {
+        const DLookup* sf = shuffles + j;
+        Fe ai = fe_zero(), si = fe_zero();
+        for (uint32_t e = 0; e < sf->width; e++) {
+            const Fe in = eval_poly_with(a.c, cols, sf->inputs[e], idx, ld), sh = eval_poly_with(a.c, cols, sf->tables[e], idx, ld);
+            ai = e ? Fr::add(Fr::mul(ai, theta), in) : in;
+            si = e ? Fr::add(Fr::mul(si, theta), sh) : sh;
+        }
+        const Fe z = ld(zc + idx), zn = ld(zc + r_next);
+        value = Fr::add(Fr::mul(value, y), Fr::mul(Fr::sub(Fr::one(), z), l0));
+        value = Fr::add(Fr::mul(value, y), Fr::mul(Fr::sub(Fr::sqr(z), z), llast));
+        const Fe prod = Fr::sub(Fr::mul(zn, Fr::add(si, gamma)), Fr::mul(z, Fr::add(ai, gamma)));
+        value = Fr::add(Fr::mul(value, y), Fr::mul(prod, lactive));
+    }
+    value = Fr::mul(value, ldg(a.t_eval + (idx & a.t_mask)));  // divide_by_vanishing_poly; (hat: back in the slabs' form)
+    const Fe ypow = pc->sh_ypow;
+    Fe* h = a.h + (size_t)b * a.h_bs + idx;
+    stg(h, Fr::add(Fr::mul(ldg(h), ypow), value));
+    if (a.h_hi) {
+        Fe* hh = a.h_hi + (size_t)b * a.h_bs + idx;
+        stg(hh, Fr::add(Fr::mul(ldg(hh), ypow), value));
+    }
+}
+
+int poly_shuffle_h(zg_ctx* ctx, const EvalHArgs& a, const DLookup* shuffles, uint32_t ns, const Fe* sz_cos, uint32_t en, uint32_t nb) {
+    if (!ns || !nb) return ZG_OK;
+    ZG_REQUIRE(shuffles && sz_cos && a.pc && a.h && (en & (en - 1)) == 0, ZG_ERR_INVALID_ARG, "shuffle_h: bad argument");
+    const Fe unhat = a.hat ? Fr::inv(Fr::from_u64(32)) : Fr::one();
+    ZG_LAUNCH(ctx, "shuffle_h", (double)nb * en * 32.0 * (2.0 + 3.0 + 2.0 * ns), shuffle_h_kernel, dim3((en + 255) / 256, nb), dim3(256), 0, a,
+              shuffles, ns, sz_cos, en, unhat);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

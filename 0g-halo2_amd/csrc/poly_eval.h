@@ -21,7 +21,12 @@ __device__ __forceinline__ void stg(Fe* p, const Fe& v) {
 }
 
 // ------------------------------------------------------------------ expression interpreter
-__device__ __forceinline__ Fe eval_poly(const DevCircuit& c, const Cols& cols, zg_poly p, uint32_t row) {
+// (Load: how a cell is read -- ldg as it stands, or with the slabs' factor taken off: poly.hip's shuffle pass over h)
+struct LoadPlain {
+    __device__ __forceinline__ Fe operator()(const Fe* p) const { return ldg(p); }
+};
+template <class Load>
+__device__ __forceinline__ Fe eval_poly_with(const DevCircuit& c, const Cols& cols, zg_poly p, uint32_t row, const Load& ld) {
     const uint32_t mask = (1u << cols.log_size) - 1u;
     Fe acc = fe_zero();
     for (uint32_t m = p.first; m < p.first + p.count; m++) {
@@ -33,7 +38,7 @@ __device__ __forceinline__ Fe eval_poly(const DevCircuit& c, const Cols& cols, z
             const zg_query q = c.queries[mo->factors[0]];
             const Fe* base = q.kind == ZG_FIXED ? cols.fixed : q.kind == ZG_ADVICE ? cols.advice : cols.instance;
             uint32_t idx = (row + (uint32_t)(q.rotation * cols.rot_scale)) & mask;
-            prod = ldg(base + ((size_t)q.column << cols.log_size) + idx);
+            prod = ld(base + ((size_t)q.column << cols.log_size) + idx);
             f = 1;
         } else {
             prod = mo->coeff;
@@ -42,11 +47,14 @@ __device__ __forceinline__ Fe eval_poly(const DevCircuit& c, const Cols& cols, z
             const zg_query q = c.queries[mo->factors[f]];
             const Fe* base = q.kind == ZG_FIXED ? cols.fixed : q.kind == ZG_ADVICE ? cols.advice : cols.instance;
             uint32_t idx = (row + (uint32_t)(q.rotation * cols.rot_scale)) & mask;
-            prod = Fr::mul(prod, ldg(base + ((size_t)q.column << cols.log_size) + idx));
+            prod = Fr::mul(prod, ld(base + ((size_t)q.column << cols.log_size) + idx));
         }
         acc = Fr::add(acc, prod);
     }
     return acc;
+}
+__device__ __forceinline__ Fe eval_poly(const DevCircuit& c, const Cols& cols, zg_poly p, uint32_t row) {
+    return eval_poly_with(c, cols, p, row, LoadPlain{});
 }
 
 __device__ __forceinline__ Cols cols_of(const Cols& c, uint32_t b) {  // proof b's view of a batch's columns

@@ -14,6 +14,7 @@ namespace zg {
 
 struct ProofShape {
     uint32_t A = 0, F = 0, P = 0, NL = 0, sets = 0;  // advice, fixed, permutation columns; lookups; permutation z polynomials
+    uint32_t NS = 0;                                 // shuffle arguments (one product polynomial each)
     uint32_t qpd = 0, bf = 0, log_n = 0;             // h pieces, blinding factors
     std::vector<std::pair<uint32_t, int32_t>> advice_queries, fixed_queries;  // (column, rotation)
     // create_proof's phases (ConstraintSystem::advice_column_phase / challenge_phase): the phase each advice column is
@@ -24,10 +25,15 @@ struct ProofShape {
 // A proof's commitments by family, in transcript order; behind them what an opening query may also name: the key's fixed
 // and sigma commitments and h = sum_i xn^i (h piece i).  A circuit's share of ADVICE .. LOOKUP_Z follows the circuit
 // before it; PERMUTED holds (input, table) per lookup: 2l, 2l + 1.
-enum Family : uint32_t { ADVICE, PERMUTED, PERM_Z, LOOKUP_Z, RANDOM, H_PIECE, OPENING, N_POINT_FAMILIES, FIXED = N_POINT_FAMILIES, SIGMA, H };
+//
+// The shuffle products (SHUFFLE_Z, one per shuffle and circuit) stand between LOOKUP_Z and RANDOM in the transcript; the
+// enumerator follows H, and the family's range is kept beside pt[] (ProofLayout::shuffle_pt), so that every family
+// before it keeps its number.  Without shuffles the range is empty and the layout is what it was.
+enum Family : uint32_t { ADVICE, PERMUTED, PERM_Z, LOOKUP_Z, RANDOM, H_PIECE, OPENING, N_POINT_FAMILIES, FIXED = N_POINT_FAMILIES, SIGMA, H, SHUFFLE_Z };
 // A proof's evaluations by family, in transcript order: every circuit's advice | fixed, random, sigma once | every
 // circuit's permutation evaluations (set s: z, z(wx), z(w^last x) at 3s .., the last set without the third) | every
-// circuit's lookup evaluations (z, z(wx), a', a'(w^-1 x), s') | the expected h(x), which no proof holds.
+// circuit's lookup evaluations (z, z(wx), a', a'(w^-1 x), s') | every circuit's shuffle evaluations (z, z(wx):
+// ProofLayout::shuffle_ev, beside ev[] as shuffle_pt is beside pt[]) | the expected h(x), which no proof holds.
 //
 // With advice phases the ADVICE family alone changes its order, for any N: phase-major, within a phase circuit-major,
 // within a circuit ascending column -- create_proof commits every circuit's columns of a phase, then squeezes that
@@ -56,6 +62,7 @@ struct ProofLayout {
     // and the column's place among them (empty: the one phase holds the columns in their order)
     std::vector<uint32_t> adv_first, adv_per, adv_place;
     Range pt[N_POINT_FAMILIES], ev[N_EVAL_FAMILIES];
+    Range shuffle_pt, shuffle_ev;           // SHUFFLE_Z's points (before pt[RANDOM]) and evaluations (before ev[EV_H])
     std::vector<Query> queries;             // create_proof's order
     std::vector<Query> evals;               // the same queries by evaluation index: transcript order, the expected h(x) last
     std::vector<int64_t> rotations;         // the distinct opening points x omega^r by first appearance (r as first met)
@@ -70,6 +77,7 @@ struct ProofLayout {
     // where commitment (fam, circuit, index) stands among the proof's points
     uint32_t point_index(Family fam, uint32_t circuit, uint32_t index) const {
         if (fam == ADVICE && !adv_first.empty()) return pt[ADVICE].first + adv_first[index] + circuit * adv_per[index] + adv_place[index];
+        if (fam == SHUFFLE_Z) return shuffle_pt.first + circuit * (shuffle_pt.count / N) + index;
         return pt[fam].first + circuit * (pt[fam].count / N) + index;
     }
     // Blake2b transcript, a fixed layout of 32-byte items: the evaluations stand between the h pieces and the argument's points
@@ -82,12 +90,20 @@ struct ProofLayout {
 };
 
 namespace layout_detail {
-inline void families(const ProofShape& s, uint32_t N, uint32_t n_open, ProofLayout::Range* pt, ProofLayout::Range* ev) {
+inline void families(const ProofShape& s, uint32_t N, uint32_t n_open, ProofLayout& l) {
+    ProofLayout::Range *pt = l.pt, *ev = l.ev;
     const uint32_t npz = s.sets ? 3 * s.sets - 1 : 0;
     const uint32_t pc[N_POINT_FAMILIES] = {N * s.A, N * 2 * s.NL, N * s.sets, N * s.NL, 1, s.qpd, n_open};
     const uint32_t ec[N_EVAL_FAMILIES] = {N * (uint32_t)s.advice_queries.size(), (uint32_t)s.fixed_queries.size(), 1, s.P, N * npz, N * 5 * s.NL, 1};
-    for (uint32_t f = 0, at = 0; f < N_POINT_FAMILIES; at += pc[f++]) pt[f] = {at, pc[f]};
-    for (uint32_t f = 0, at = 0; f < N_EVAL_FAMILIES; at += ec[f++]) ev[f] = {at, ec[f]};
+    // (the shuffle products: N * NS points in front of RANDOM, 2 N * NS evaluations in front of EV_H)
+    for (uint32_t f = 0, at = 0; f < N_POINT_FAMILIES; at += pc[f++]) {
+        if (f == RANDOM) l.shuffle_pt = {at, N * s.NS}, at += N * s.NS;
+        pt[f] = {at, pc[f]};
+    }
+    for (uint32_t f = 0, at = 0; f < N_EVAL_FAMILIES; at += ec[f++]) {
+        if (f == EV_H) l.shuffle_ev = {at, 2 * N * s.NS}, at += 2 * N * s.NS;
+        ev[f] = {at, ec[f]};
+    }
 }
 // the phases of the ADVICE family (ProofLayout::phases, adv_*)
 inline void phases(const ProofShape& s, ProofLayout& l) {
@@ -138,7 +154,7 @@ inline const char* phases_error(uint32_t A, const uint8_t* advice_phase, uint32_
 // possible opening point (2 + every advice and fixed query), or SHPLONK's 2.
 inline size_t proof_size_bound(const ProofShape& s, uint32_t N, bool shplonk, bool blake2b) {
     ProofLayout l;
-    layout_detail::families(s, N, shplonk ? 2 : 2 + (uint32_t)(s.advice_queries.size() + s.fixed_queries.size()), l.pt, l.ev);
+    layout_detail::families(s, N, shplonk ? 2 : 2 + (uint32_t)(s.advice_queries.size() + s.fixed_queries.size()), l);
     return l.bytes(blake2b);
 }
 
@@ -146,7 +162,7 @@ inline ProofLayout build_layout(const ProofShape& s, uint32_t N, bool shplonk) {
     ProofLayout l;
     l.N = N;
     l.shplonk = shplonk;
-    layout_detail::families(s, N, 0, l.pt, l.ev);
+    layout_detail::families(s, N, 0, l);
     layout_detail::phases(s, l);
     // ---- the opening queries; points by first appearance, rotations compared mod n as upstream compares field points
     const int64_t n = (int64_t)1 << s.log_n, last = -(int64_t)(s.bf + 1);
@@ -179,6 +195,11 @@ inline ProofLayout build_layout(const ProofShape& s, uint32_t N, bool shplonk) {
             add(0, PERMUTED, c, 2 * k + 1, ev_lk + 5 * k + 4);
             add(-1, PERMUTED, c, 2 * k, ev_lk + 5 * k + 3);
             add(1, LOOKUP_Z, c, k, ev_lk + 5 * k + 1);
+        }
+        for (uint32_t j = 0; j < s.NS; j++) {
+            const uint32_t ev_sh = l.shuffle_ev.first + 2 * (c * s.NS + j);
+            add(0, SHUFFLE_Z, c, j, ev_sh);
+            add(1, SHUFFLE_Z, c, j, ev_sh + 1);
         }
     }
     for (uint32_t i = 0; i < s.fixed_queries.size(); i++) add(s.fixed_queries[i].second, FIXED, 0, s.fixed_queries[i].first, l.ev[EV_FIXED].first + i);

@@ -224,6 +224,7 @@ struct ProveBatch {
     zg_ctx* ctx;
     hipStream_t st;
     uint32_t nb, n, k, ek, bf, usable, A, I, P, NL, S, Q;
+    uint32_t NS;  // shuffle arguments (PkDev::NS)
     uint32_t IU, NC;  // (I = IU + NC: the caller's instance columns, then the challenges' constant columns -- PkDev::NC)
     // the challenges squeezed so far, [nb][nch] (zero where not yet squeezed): what a phase's callback is handed
     uint32_t nch;
@@ -293,7 +294,7 @@ struct ProveBatch {
           status(count, ZG_OK), shplonk(p_->multiopen == ZG_MULTIOPEN_SHPLONK) {
         n = pk.n; k = pk.k; ek = pk.ext_k; bf = pk.bf; usable = pk.usable;
         A = pk.A; I = pk.I; P = pk.P; NL = pk.NL; S = pk.sets; Q = pk.qpd;
-        IU = pk.IU; NC = pk.NC;
+        IU = pk.IU; NC = pk.NC; NS = pk.NS;
         nch = (uint32_t)p->challenge_phase.size();
         chal.assign((size_t)nb * nch, zg_fr{});
         for (Transcript& t : tr) t.blake2b = p->transcript == ZG_TRANSCRIPT_BLAKE2B;
@@ -461,6 +462,7 @@ struct ProveBatch {
         const int v = knob(K_LAT_GATE);
         if (shplonk) return false;  // (its second half starts from h1 on the host: the plain order)
         if (p->phased() || phase_fn) return false;  // (a phase's witness starts from the challenges on the host)
+        if (pk.NS) return false;  // (a circuit with shuffles: the plain order)
         if (no_gate || (v < 0 ? LAT_GATE_DEFAULT : v) == 0 || !p->use_side || nb != 1 || p->world > 1 || p->rccl_comm) return false;
         if (p->warm_sig != form_sig()) return false;  // (first-use allocations and their synchronisations are behind us)
         // (a runtime that completes every launch before it submits the next one would never reach publish())
@@ -782,20 +784,40 @@ struct ProveBatch {
             MsmJob msm = phase_msm(cgl, p->zs, n, prod_per, zs_bs);
             if (!have_random) msm.bases_b = cg, msm.split = mb;
             msm.run_mask = z_runs; msm.naf_width = p->naf_gl_w;
-            ZG_TRY(commit(p, msm, W_PRODUCTS));
+            ZG_TRY(commit(p, msm, W_PRODUCTS, 0, NS == 0));
             {
                 const Grouping g = grouping(mb, zs_bs, pp_bs);
                 ZG_TRY(ntt_batch_to_dev(sx, p->zs, pp_at(p->ix_pz), n, (size_t)nb * mb, k, pk.omega_inv, &pk.ifft_div, &g));
             }
             if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_pz, mb));
         } else if (!have_random) {  // neither lookups nor permutation: commit the random polynomial on its own
-            ZG_TRY(commit(p, phase_msm(p->g, random_row, n, 1, perm_bs), W_PRODUCTS));
+            prod_per = 1;
+            ZG_TRY(commit(p, phase_msm(p->g, random_row, n, 1, perm_bs), W_PRODUCTS, 0, NS == 0));
+        } else {
+            prod_per = 0;
         }
+        if (NS) ZG_TRY(shuffles_queue());
         ZG_TICK("products: queued");
+        return ZG_OK;
+    }
+    // ---- the shuffle products (shuffle::Argument::commit_product): terms, ONE grand-product sequence and ONE MSM launch
+    // sequence over the nb * NS columns, behind the phase's other commitments in the results; then the way of a lookup
+    // product -- coefficients, cosets -- on the side stream
+    int shuffles_queue() {
+        const size_t sz_bs = (size_t)NS * n;
+        ZG_TRY(poly_shuffle_terms(ctx, pk.dc, pk.d_shuffles, NS, base_cols, p->d_pc, nb, p->snum, p->sden, n));
+        ZG_TRY(poly_grand_product(ctx, p->snum, p->sden, nullptr, p->sz, p->stmp, n, nb * NS, 0, n - bf - 1, NS, sz_bs, 0));
+        ZG_TRY(poly_blind_rows2(ctx, p->d_pc, nb, p->sz, sz_bs, n, NS, TAG_SHUFFLE_Z, 0, TAG_SHUFFLE_Z, n - bf, bf));
+        ZG_TRY(fork());
+        ZG_TRY(commit(p, phase_msm(p->gl, p->sz, n, NS, sz_bs), W_PRODUCTS, (size_t)nb * prod_per, true));
+        const Grouping g = grouping(NS, sz_bs, pp_bs);
+        ZG_TRY(ntt_batch_to_dev(sx, p->sz, pp_at(p->ix_sz), n, (size_t)nb * NS, k, pk.omega_inv, &pk.ifft_div, &g));
+        if (phase_cosets) ZG_TRY(to_cosets(sx, p->ix_sz, NS));
         return ZG_OK;
     }
     int products_absorb() {
         const uint32_t mb = S + NL;
+        if (NS) return products_absorb_shuffles();
         if (mb) {
             ZG_TRY(wait_points(p, (size_t)nb * prod_per, pts, W_PRODUCTS));
             ZG_TICK("products: points on the host");
@@ -823,6 +845,29 @@ struct ProveBatch {
         ZG_TICK("y");
         ZG_TRY(publish());
         ZG_TICK("y uploaded");
+        lap(2);
+        return ZG_OK;
+    }
+
+    // (with shuffles: the phase's results are [nb][prod_per] permutation z, lookup z and -- where it rides here -- the
+    //  random polynomial, then [nb][NS] shuffle z; the transcript takes permutation z, lookup z, shuffle z, random)
+    int products_absorb_shuffles() {
+        const uint32_t mb = S + NL;
+        ZG_TRY(wait_points(p, (size_t)nb * (prod_per + NS), pts, W_PRODUCTS));
+        for (uint32_t b = 0; b < nb; b++) {
+            const Jac* q = &pts[(size_t)b * prod_per];
+            for (uint32_t i = 0; i < mb; i++) tr[b].write_point(q[i]);
+            if (!have_random) random_commit[b] = q[mb];
+            const Jac* qs = &pts[(size_t)nb * prod_per + (size_t)b * NS];
+            for (uint32_t j = 0; j < NS; j++) tr[b].write_point(qs[j]);
+        }
+        have_random = true;
+        for (uint32_t b = 0; b < nb; b++) {
+            tr[b].write_point(random_commit[b]);
+            evalh_consts(p->hpc[b], tr[b].squeeze(), pk);
+        }
+        ZG_TICK("y");
+        ZG_TRY(publish());
         lap(2);
         return ZG_OK;
     }
@@ -856,12 +901,20 @@ struct ProveBatch {
             const EvalHMode mode = !by_degree ? EH_ALL : di == 1 ? EH_BOTH : EH_HIGH;
             ZG_TRY(poly_evaluate_h(ctx, a, pk.dom[di].en, nb, A + I + pk.F, (double)((size_t)1 << ek) * ((double)pk.dom[di].en / parts_en), mode));
         }
+        // the shuffles' terms, which stand last: a pass over h on every part (and over the high terms' sum where it is kept)
+        for (uint32_t di = dlo; NS && di < dhi; di++) {
+            EvalHArgs a = evalh_args(p, di);
+            if (!(by_degree && di == 1)) a.h_hi = nullptr;
+            const Fe* sz_cos = p->dbuf[di].cos + (size_t)(p->ix_sz - p->ix_adv) * pk.dom[di].en;
+            ZG_TRY(poly_shuffle_h(ctx, a, pk.d_shuffles, NS, sz_cos, pk.dom[di].en, nb));
+        }
         // multi: the slots' quotients into slot 0's, on each part, BEFORE the transforms back: those, the pieces and their
         // commitments then exist once (nq = 1)
         if (multi)
             for (uint32_t di = dlo; di < dhi; di++) ZG_TRY(poly_fold_slots(ctx, p->d_pc, nb, p->dbuf[di].h, pk.dom[di].en, pk.dom[di].en));
         p->have_last = true;
         p->last_split = split;
+        p->last_by_degree = by_degree;
         p->last_nb = nb;
         const double ext_inv_unit = (double)nq * 2.0 * (double)((size_t)1 << ek) * 32.0;  // (ext -> coeff, 2 * 8n * 32 B)
         if (!split) {
@@ -954,7 +1007,7 @@ struct ProveBatch {
     }
     // the prover's handles: a commitment's polynomial (with its circuit's slot above it in a list entry)
     uint32_t poly_of(Family fam, uint32_t index) const {
-        const uint32_t base[] = {p->ix_adv, p->ix_perm, p->ix_pz, p->ix_lz, p->ix_random, 0, 0, p->ix_fixed, p->ix_sigma, p->ix_hpoly};
+        const uint32_t base[] = {p->ix_adv, p->ix_perm, p->ix_pz, p->ix_lz, p->ix_random, 0, 0, p->ix_fixed, p->ix_sigma, p->ix_hpoly, p->ix_sz};
         return base[fam] + index;
     }
     uint32_t entry_of(Family fam, uint32_t circuit, uint32_t index) const { return circuit << 16 | poly_of(fam, index); }
@@ -1352,6 +1405,8 @@ static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
                "zg_prover_prove: advice phases and challenges are not made on a point-range shard of the SRS");
     ZG_REQUIRE(p->multiopen != ZG_MULTIOPEN_SHPLONK || (p->world <= 1 && !p->rccl_comm), ZG_ERR_UNSUPPORTED,
                "zg_prover_prove: the SHPLONK multi-open is not made on a point-range shard of the SRS");
+    ZG_REQUIRE(p->pk->NS == 0 || (p->world <= 1 && !p->rccl_comm), ZG_ERR_UNSUPPORTED,
+               "zg_prover_prove: a circuit with shuffles is not proved on a point-range shard of the SRS");
     ZG_REQUIRE(p->world > 1 || p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG,
                "zg_prover_prove: the base sets hold %u of %u points and no shard was declared (zg_prover_set_shard)", p->shard_n, p->pk->n);
     ZG_ENTER(p->ctx);
@@ -1379,6 +1434,7 @@ static int prove_multi_impl(zg_prover* p, size_t circuits, const zg_fr* const* a
     *proof_len = 0;
     ZG_TRY(batch_args_ok("zg_prover_prove_multi", "circuits", p, circuits, instance, instance_len));
     ZG_REQUIRE(!p->phased(), ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not for a circuit with challenges or advice phases");
+    ZG_REQUIRE(circuits == 1 || p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: several circuits in one proof, not for a circuit with shuffles");
     uint8_t* out[1] = {proof};
     if (circuits == 1) return prove_batch_impl(p, 1, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr);
     ZG_REQUIRE(p->world <= 1 && !p->rccl_comm, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not on a point-range shard of the SRS");

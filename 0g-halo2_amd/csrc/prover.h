@@ -43,6 +43,12 @@ struct PkDev {
     // (ConstraintSystem::degree counts them as degree 0: classify_terms).
     uint32_t IU = 0, NC = 0;
     std::vector<uint8_t> q_chal;
+    // The shuffle arguments (zg_prover_create_shuffles): NS of them, each a DLookup whose `tables` are
+    // the shuffle expressions, on the host and on the device.  Shuffle j's product z_j is polynomial ix_sz + j of a proof
+    // and coset slab A + I + sets + 3 NL + j.
+    uint32_t NS = 0;
+    std::vector<DLookup> shuffles;
+    const DLookup* d_shuffles = nullptr;
     std::vector<zg_query> advice_queries, fixed_queries;
     DevCircuit dc{};
     std::vector<void*> owned;  // device allocations freed with the key
@@ -104,6 +110,7 @@ struct PkDev {
 inline ProofShape proof_shape(const PkDev& k) {
     ProofShape s;
     s.A = k.A; s.F = k.F; s.P = k.P; s.NL = k.NL; s.sets = k.sets; s.qpd = k.qpd; s.bf = k.bf; s.log_n = k.k;
+    s.NS = k.NS;
     for (const zg_query& q : k.advice_queries) s.advice_queries.push_back({q.column, q.rotation});
     for (const zg_query& q : k.fixed_queries) s.fixed_queries.push_back({q.column, q.rotation});
     return s;
@@ -182,6 +189,9 @@ struct zg_prover {
     // indices into the coefficient-polynomial space (PolySet: < nsh = F + P shared, the rest per proof)
     uint32_t ix_fixed = 0, ix_sigma = 0, ix_adv = 0, ix_inst = 0, ix_pz = 0, ix_lz = 0, ix_perm = 0, ix_random = 0,
              ix_hpiece = 0, ix_hpoly = 0, nsh = 0;
+    uint32_t ix_sz = 0;  // the shuffle products: behind a'/s' among the polynomials and among the coset slabs
+    // the shuffle products' rows [cap][NS][n], their grand product's terms [cap * NS][n] each and its scratch
+    zg::Fe *sz = nullptr, *snum = nullptr, *sden = nullptr, *stmp = nullptr;
     zg::Fe* pp = nullptr;  // [cap][npp][n]
     struct DomBuf {
         zg::Fe *cos = nullptr /* [cap][ncos][en] */, *h = nullptr /* [cap][en] */;
@@ -240,6 +250,7 @@ struct zg_prover {
     bool have_last = false;
     bool in_flight = false;   // a batch was started and did not reach its end (an error return): work may still be queued
     bool last_split = false;  // which extended domain the last proof used (zg_prover_fetch)
+    bool last_by_degree = false;  // ... and whether it took the quotient's terms by degree (the first part's h is reused then)
     uint32_t last_nb = 0;
     double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };

@@ -81,6 +81,10 @@ void evalh_consts(ProofConst& c, const Fe& y, const PkDev& pk) {
     c.eh_delta_start[0] = Fr::mul(c.beta, zeta);   // beta * coset shift
     c.eh_delta_start[1] = Fr::mul(c.beta, zeta2);
     c.eh_scaled = 0;
+    if (pk.NS) {  // (the shuffle pass over h: its three terms per shuffle stand last, everything before them moves up)
+        c.sh_y = y;
+        c.sh_ypow = Fr::pow_u64(y, 3 * pk.NS);
+    }
     if (hat) {
         const Fe c261 = Fr9Params::c261_fe();
         for (Fe* cst : {&c.eh_y, &c.eh_beta, &c.eh_gamma, &c.eh_theta, &c.eh_delta_start[0], &c.eh_delta_start[1]})
@@ -193,11 +197,12 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
     const uint32_t n = k.n, F = k.F, A = k.A, I = k.I, P = k.P, NL = k.NL, S = k.sets, Q = k.qpd;
     (void)F;
     p->cap = cap;
-    p->ncos = A + I + S + NL + 2 * NL;
+    const uint32_t NS = k.NS;
+    p->ncos = A + I + S + NL + 2 * NL + NS;
     p->npp = p->ncos + 1 + Q + 1;
     p->nsh = k.F + P;
     p->ix_fixed = 0; p->ix_sigma = k.F; p->ix_adv = p->nsh; p->ix_inst = p->ix_adv + A; p->ix_pz = p->ix_inst + I;
-    p->ix_lz = p->ix_pz + S; p->ix_perm = p->ix_lz + NL; p->ix_random = p->ix_perm + 2 * NL;
+    p->ix_lz = p->ix_pz + S; p->ix_perm = p->ix_lz + NL; p->ix_sz = p->ix_perm + 2 * NL; p->ix_random = p->ix_sz + NS;
     p->ix_hpiece = p->ix_random + 1; p->ix_hpoly = p->ix_hpiece + Q;
     const size_t c = cap;
     ZG_TRY(dalloc_into(own, &p->pp, c * p->npp * n));
@@ -218,6 +223,13 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
     p->ctab = p->cin + c * NL * n;
     ZG_TRY(dalloc_into(own, &p->perm, c * (2 * NL + 1) * n));  // + the vanishing argument's random polynomial
     ZG_TRY(dalloc_into(own, &p->zs, c * (S + NL + 1) * n));
+    p->sz = p->snum = p->sden = p->stmp = nullptr;
+    if (NS) {
+        ZG_TRY(dalloc_into(own, &p->sz, c * NS * n));
+        ZG_TRY(dalloc_into(own, &p->snum, c * NS * n));
+        ZG_TRY(dalloc_into(own, &p->sden, c * NS * n));
+        ZG_TRY(dalloc_into(own, &p->stmp, poly_grand_product_tmp_elems(n, cap * NS)));
+    }
     const uint32_t mb = S + NL;
     ZG_TRY(dalloc_into(own, &p->num, c * mb * n));
     ZG_TRY(dalloc_into(own, &p->den, c * mb * n));
@@ -229,13 +241,13 @@ int alloc_slots_impl(zg_prover* p, uint32_t cap) {
     p->max_points = 4 + (uint32_t)(k.advice_queries.size() + k.fixed_queries.size());
     if (p->max_points > PC_MAX_POINTS) p->max_points = PC_MAX_POINTS;
     ZG_TRY(dalloc_into(own, &p->pw, c * p->max_points * n));
-    p->max_evals = (uint32_t)(k.advice_queries.size() + k.fixed_queries.size()) + P + 3 * S + 5 * NL + 4;
+    p->max_evals = (uint32_t)(k.advice_queries.size() + k.fixed_queries.size()) + P + 3 * S + 5 * NL + 2 * NS + 4;
     ZG_TRY(dalloc_into(own, &p->wpoly, c * 2 * p->max_points * n));
-    p->maxv = std::max<uint32_t>(std::max<uint32_t>(A, 2 * NL + 1), std::max<uint32_t>(S + NL + 1, std::max<uint32_t>(Q, p->max_points)));
+    p->maxv = std::max<uint32_t>(std::max<uint32_t>(A, 2 * NL + 1), std::max<uint32_t>(S + NL + 1 + NS, std::max<uint32_t>(Q, p->max_points)));
     ZG_TRY(dalloc_into(own, &p->xyzz, c * p->maxv));
     ZG_TRY(dalloc_into(own, &p->d_idx, (size_t)4 * p->max_evals + 64 + (size_t)p->max_points * 512));
     // (per circuit: its advice queries, 3 per permutation set but 2 for the last, 5 per lookup; once: fixed, sigma, h, random)
-    p->mlists_cap = c * (k.advice_queries.size() + (S ? 3 * S - 1 : 0) + 5 * NL) + k.fixed_queries.size() + P + 2;
+    p->mlists_cap = c * (k.advice_queries.size() + (S ? 3 * S - 1 : 0) + 5 * NL + 2 * NS) + k.fixed_queries.size() + P + 2;
     ZG_TRY(dalloc_into(own, &p->d_mlists, p->mlists_cap));
     ZG_TRY(dalloc_into(own, &p->ktmp, poly_kate_tmp_elems(n, cap * p->max_points)));
     ZG_TRY(dalloc_into(own, &p->d_pc, c));
@@ -729,7 +741,7 @@ int classify_terms(PkDev* pk, const zg_circuit* cs) {
     qt.gate_hi.assign(NG, 0);
     qt.set_hi.assign(S, 0);
     qt.lk_hi.assign(NL, 0);
-    qt.part2.assign((size_t)A + I + S + 3 * NL, 0);
+    qt.part2.assign((size_t)A + I + S + 3 * NL + pk->NS, 0);
     auto mark_cell = [&](const zg_query& q) {
         if (q.kind == ZG_ADVICE) qt.part2[q.column] = 1;
         else if (q.kind == ZG_INSTANCE) qt.part2[A + q.column] = 1;
@@ -775,6 +787,11 @@ int classify_terms(PkDev* pk, const zg_circuit* cs) {
         qt.part2[A + I + S + l] = 1;
         qt.part2[A + I + S + NL + 2 * l] = qt.part2[A + I + S + NL + 2 * l + 1] = 1;
         for (uint32_t e = 0; e < lk.width; e++) mark(lk.inputs[e]), mark(lk.tables[e]);
+    }
+    // (the shuffles' terms are computed on every part: their products and every cell they read are needed on the second)
+    for (uint32_t j = 0; j < pk->NS; j++) {
+        qt.part2[A + I + S + 3 * NL + j] = 1;
+        for (uint32_t e = 0; e < pk->shuffles[j].width; e++) mark(pk->shuffles[j].inputs[e]), mark(pk->shuffles[j].tables[e]);
     }
     // (without low terms, without the split domain or its grouped nine-limb kernel, or with more terms than eh_ypow has
     //  powers for, every term stays on both parts)
@@ -1009,10 +1026,46 @@ void zg_prover_destroy(zg_prover* p) {
     delete p;
 }
 
-static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fixed_values, const zg_fr* sigma_values,
-                              const zg_g1_affine* g, const zg_g1_affine* g_lagrange, const zg_bases* shared_g,
+}  // extern "C"
+// (poly.h)
+int zg::shuffles_ok(const char* who, const zg_circuit* cs, const zg_shuffle* shuffles, uint32_t n_shuffles) {
+    ZG_REQUIRE(shuffles || n_shuffles == 0, ZG_ERR_INVALID_ARG, "%s: %u shuffles and a null array", who, n_shuffles);
+    ZG_REQUIRE(n_shuffles <= ZG_MAX_SHUFFLES, ZG_ERR_UNSUPPORTED, "%s: %u shuffles (max %u)", who, n_shuffles, (uint32_t)ZG_MAX_SHUFFLES);
+    ZG_REQUIRE(n_shuffles == 0 || ((cs->monomials || !cs->n_monomials) && (cs->queries || !cs->n_queries)), ZG_ERR_INVALID_ARG,
+               "%s: null circuit arrays", who);
+    auto poly_ok = [&](const zg_poly& q) { return (uint64_t)q.first + q.count <= cs->n_monomials; };
+    // ConstraintSystem::degree's count of an expression: a challenge has degree 0, an expression at least 1
+    auto degree = [&](const zg_poly& q) {
+        uint32_t d = 1;
+        for (uint32_t m = q.first; m < q.first + q.count; m++) {
+            uint32_t f = 0;
+            for (uint32_t i = 0; i < cs->monomials[m].n_factors && i < ZG_MAX_FACTORS; i++) {
+                const uint32_t qi = cs->monomials[m].factors[i];
+                f += qi < cs->n_queries && cs->queries[qi].kind == ZG_CHALLENGE ? 0u : 1u;
+            }
+            d = std::max(d, f);
+        }
+        return d;
+    };
+    for (uint32_t j = 0; j < n_shuffles; j++) {
+        const zg_shuffle& sf = shuffles[j];
+        ZG_REQUIRE(sf.width >= 1 && sf.width <= ZG_MAX_LOOKUP_WIDTH, ZG_ERR_INVALID_ARG, "%s: shuffle %u width %u", who, j, sf.width);
+        for (uint32_t e = 0; e < sf.width; e++) {
+            ZG_REQUIRE(poly_ok(sf.inputs[e]) && poly_ok(sf.shuffles[e]), ZG_ERR_INVALID_ARG, "%s: shuffle %u polynomial out of range", who, j);
+            const uint32_t need = 2 + std::max(degree(sf.inputs[e]), degree(sf.shuffles[e]));
+            ZG_REQUIRE(cs->cs_degree >= need, ZG_ERR_INVALID_ARG, "%s: shuffle %u needs cs_degree %u, the circuit says %u", who, j, need,
+                       cs->cs_degree);
+        }
+    }
+    return ZG_OK;
+}
+extern "C" {
+
+static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_shuffle* shuffles, uint32_t n_shuffles, const zg_fr* fixed_values,
+                              const zg_fr* sigma_values, const zg_g1_affine* g, const zg_g1_affine* g_lagrange, const zg_bases* shared_g,
                               const zg_bases* shared_gl, const zg_fr* vk_repr, zg_prover** out) {
     ZG_REQUIRE(ctx && cs && vk_repr && out, ZG_ERR_INVALID_ARG, "zg_prover_create: null argument");
+    ZG_TRY(shuffles_ok("zg_prover_create", cs, shuffles, n_shuffles));
     ZG_REQUIRE(cs->n_fixed == 0 || fixed_values, ZG_ERR_INVALID_ARG, "zg_prover_create: fixed_values is null");
     ZG_REQUIRE(cs->n_perm_columns == 0 || sigma_values, ZG_ERR_INVALID_ARG, "zg_prover_create: sigma_values is null");
     ZG_REQUIRE(cs->cs_degree >= 3 && cs->cs_degree <= 9, ZG_ERR_UNSUPPORTED, "zg_prover_create: cs_degree %u", cs->cs_degree);
@@ -1037,6 +1090,19 @@ static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fi
     ZG_TRY(validate_circuit(pk, cs, monos, lks));
     check_info(pk, cs, monos, lks);
     ZG_TRY(upload_circuit(pk, cs, monos, lks, ctx->stream));
+    pk->NS = n_shuffles;
+    for (uint32_t j = 0; j < n_shuffles; j++) {
+        DLookup d{};
+        d.width = shuffles[j].width;
+        for (uint32_t e = 0; e < d.width; e++) d.inputs[e] = shuffles[j].inputs[e], d.tables[e] = shuffles[j].shuffles[e];
+        pk->shuffles.push_back(d);
+    }
+    if (n_shuffles) {
+        DLookup* d_sf = nullptr;
+        ZG_TRY(key_alloc(pk, &d_sf, n_shuffles));
+        ZG_HIP(hipMemcpy(d_sf, pk->shuffles.data(), n_shuffles * sizeof(DLookup), hipMemcpyHostToDevice));
+        pk->d_shuffles = d_sf;
+    }
     if (pk->hat) ZG_TRY(factored_view(pk, cs, monos));
     ZG_TRY(attach_bases(p, g, g_lagrange, shared_g, shared_gl));
     ZG_TRY(enable_tables(p));
@@ -1059,15 +1125,29 @@ static int prover_create_impl(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fi
 
 int zg_prover_create(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fixed_values, const zg_fr* sigma_values,
                      const zg_g1_affine* g, const zg_g1_affine* g_lagrange, const zg_fr* vk_repr, zg_prover** out) {
+    return zg_prover_create_shuffles(ctx, cs, nullptr, 0, fixed_values, sigma_values, g, g_lagrange, vk_repr, out);
+}
+
+int zg_prover_create_shuffles(zg_ctx* ctx, const zg_circuit* cs, const zg_shuffle* shuffles, uint32_t n_shuffles, const zg_fr* fixed_values,
+                              const zg_fr* sigma_values, const zg_g1_affine* g, const zg_g1_affine* g_lagrange, const zg_fr* vk_repr,
+                              zg_prover** out) {
     ZG_REQUIRE(g && g_lagrange, ZG_ERR_INVALID_ARG, "zg_prover_create: null SRS");
-    return prover_create_impl(ctx, cs, fixed_values, sigma_values, g, g_lagrange, nullptr, nullptr, vk_repr, out);
+    return prover_create_impl(ctx, cs, shuffles, n_shuffles, fixed_values, sigma_values, g, g_lagrange, nullptr, nullptr, vk_repr, out);
 }
 
 int zg_prover_create_shared(zg_ctx* ctx, const zg_circuit* cs, const zg_fr* fixed_values, const zg_fr* sigma_values,
                             const zg_bases* g, const zg_bases* g_lagrange, const zg_fr* vk_repr, zg_prover** out) {
-    ZG_REQUIRE(g && g_lagrange, ZG_ERR_INVALID_ARG, "zg_prover_create_shared: null bases");
-    return prover_create_impl(ctx, cs, fixed_values, sigma_values, nullptr, nullptr, g, g_lagrange, vk_repr, out);
+    return zg_prover_create_shared_shuffles(ctx, cs, nullptr, 0, fixed_values, sigma_values, g, g_lagrange, vk_repr, out);
 }
+
+int zg_prover_create_shared_shuffles(zg_ctx* ctx, const zg_circuit* cs, const zg_shuffle* shuffles, uint32_t n_shuffles,
+                                     const zg_fr* fixed_values, const zg_fr* sigma_values, const zg_bases* g, const zg_bases* g_lagrange,
+                                     const zg_fr* vk_repr, zg_prover** out) {
+    ZG_REQUIRE(g && g_lagrange, ZG_ERR_INVALID_ARG, "zg_prover_create_shared: null bases");
+    return prover_create_impl(ctx, cs, shuffles, n_shuffles, fixed_values, sigma_values, nullptr, nullptr, g, g_lagrange, vk_repr, out);
+}
+
+uint32_t zg_prover_shuffles(const zg_prover* p) { return p ? p->pk->NS : 0; }
 
 int zg_prover_set_batch(zg_prover* p, size_t max_batch) {
     ZG_REQUIRE(p, ZG_ERR_INVALID_ARG, "zg_prover_set_batch: null prover");
@@ -1232,6 +1312,16 @@ int zg_prover_fetch_slot(zg_prover* p, size_t slot, uint32_t what, uint32_t inde
             else src = p->dbuf[di].cos + (slot * p->ncos + pk.A + pk.IU + index) * (size_t)pk.dom[di].en, count = pk.dom[di].en;
             break;
         }
+        case 11: ZG_REQUIRE(index < pk.NS, ZG_ERR_INVALID_ARG, "zg_prover_fetch: shuffle %u", index);
+                 src = p->sz + (slot * pk.NS + index) * n; count = n; break;
+        case 12: case 13: {  // h as the last proof left it on a part of the split domain
+            const uint32_t di = what - 11;
+            ZG_REQUIRE(p->last_split && di < pk.nparts, ZG_ERR_INVALID_ARG, "zg_prover_fetch: the last proof did not use the split domain");
+            ZG_REQUIRE(!p->last_by_degree, ZG_ERR_INVALID_ARG,
+                       "zg_prover_fetch: the last proof took the quotient's terms by degree, which reuses the parts' h (zg_prover_set_quotient_terms(0))");
+            src = p->dbuf[di].h + slot * (size_t)pk.dom[di].en; count = pk.dom[di].en;
+            break;
+        }
         default: ZG_REQUIRE(false, ZG_ERR_INVALID_ARG, "zg_prover_fetch: unknown item %u", what);
     }
     ZG_REQUIRE(cap_elems >= count, ZG_ERR_INVALID_ARG, "zg_prover_fetch: need %zu elements", count);
@@ -1244,7 +1334,7 @@ int zg_prover_fetch_slot(zg_prover* p, size_t slot, uint32_t what, uint32_t inde
         ZG_HIP(hipMemcpy(out, tmp, count * 32, hipMemcpyDeviceToHost));
         return ZG_OK;
     }
-    if ((what == 0 || what >= 8) && pk.hat) {  // h and the slabs on a coset are kept as x * 2^261: hand back the library form
+    if ((what == 0 || (what >= 8 && what != 11)) && pk.hat) {  // h and the slabs on a coset are kept as x * 2^261: hand back the library form
         WsScope ws(p->ctx);
         Fe* tmp = ws.get<Fe>(count);
         if (!tmp) return ZG_ERR_OOM;
@@ -1323,6 +1413,7 @@ static int evaluate_h_impl(zg_prover* p, const void* advice_polys, const void* i
     ZG_REQUIRE((advice_polys || !pk.A) && (instance_polys || !pk.I) && (perm_z_polys || !pk.sets) &&
                    (lookup_z_polys || !pk.NL) && (permuted_polys || !pk.NL),
                ZG_ERR_INVALID_ARG, "zg_prover_evaluate_h: a polynomial family is missing");
+    ZG_REQUIRE(pk.NS == 0, ZG_ERR_UNSUPPORTED, "zg_prover_evaluate_h: not for a circuit with shuffles (their products are no argument of this entry)");
     ZG_REQUIRE(p->cap >= 1, ZG_ERR_INVALID_ARG, "zg_prover_evaluate_h: the prover has no slot");
     zg_ctx* ctx = p->ctx;
     ZG_ENTER(ctx);

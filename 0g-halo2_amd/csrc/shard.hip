@@ -49,6 +49,7 @@ __global__ void xyzz_sum_ranks_kernel(const XYZZ* __restrict__ parts, uint32_t w
 int shard_args_ok(const char* who, const zg_prover* p, uint32_t rank, uint32_t world, size_t first_point, bool fn_missing) {
     ZG_REQUIRE(world >= 1 && rank < world, ZG_ERR_INVALID_ARG, "%s: rank %u of %u", who, rank, world);
     ZG_REQUIRE(world == 1 || !p->phased(), ZG_ERR_UNSUPPORTED, "%s: a circuit with challenges or advice phases is not proved on a point-range shard", who);
+    ZG_REQUIRE(world == 1 || p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "%s: a circuit with shuffles is not proved on a point-range shard", who);
     ZG_REQUIRE(!fn_missing, ZG_ERR_INVALID_ARG, "%s: no exchange function", who);
     ZG_REQUIRE(first_point + p->g->n <= p->pk->n, ZG_ERR_INVALID_ARG, "%s: points [%zu, %zu) of %u", who, first_point,
                first_point + p->g->n, p->pk->n);

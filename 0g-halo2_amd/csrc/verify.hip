@@ -71,6 +71,7 @@ struct VArgs {
     const VMono* monos;
     const zg_poly* gates;
     const zg_lookup* lookups;
+    const zg_shuffle* shuffles;  // NS of them (zg_verifier_create_shuffles)
     const uint32_t* qsrc;   // per circuit query: evaluation index, or IEVAL | instance slot
     const uint32_t* psrc;   // per permutation column: the same, at rotation 0
     const uint32_t* iev_col;
@@ -94,6 +95,7 @@ struct VArgs {
     // where the random polynomial's commitment stands among a proof's points, and where the families start among its
     // evaluations (circuit c's share follows circuit c-1's: nAQ advice, npz permutation, 5 NL lookup evaluations each)
     uint32_t NC, walk[4], PT_RAND, EV_FIX, EV_SIG, EV_PZ, EV_LK, npz;
+    uint32_t NS, EV_SH;  // the shuffles: circuit c's 2 NS evaluations (z, z(wx) per shuffle) follow circuit c-1's from EV_SH on
     // the advice phases (the layout's): walk[0] is read as ph_points[ph] points per phase, each followed by the squeezes of
     // that phase's ph_nchal[ph] challenges, whose indices stand one phase behind the other in ph_chal
     uint32_t n_ph, ph_points[ZG_MAX_PHASES], ph_nchal[ZG_MAX_PHASES], ph_chal[ZG_MAX_CHALLENGES];
@@ -438,6 +440,21 @@ __host__ __device__ void scalars_one(const VArgs& a, uint32_t b) {
             FOLD(Fr::mul(ams, l0));
             FOLD(Fr::mul(Fr::mul(Fr::sub(e5[2], e5[3]), ams), lactive));
         }
+        // the shuffles: l_0 (1 - z), l_last (z^2 - z), l_active (z(wx) (s + gamma) - z (a + gamma))
+        const Fe* sh = ev + a.EV_SH + circ * 2 * a.NS;
+        for (uint32_t j = 0; j < a.NS; j++) {
+            const zg_shuffle S = a.shuffles[j];
+            Fe ai = fe_zero(), si = fe_zero();
+            for (uint32_t e = 0; e < ZG_MAX_LOOKUP_WIDTH; e++) {
+                if (e >= S.width) break;
+                ai = Fr::add(Fr::mul(ai, theta), eval_poly(a, S.inputs[e], qe));
+                si = Fr::add(Fr::mul(si, theta), eval_poly(a, S.shuffles[e], qe));
+            }
+            const Fe z = sh[2 * j], zn = sh[2 * j + 1];
+            FOLD(Fr::mul(Fr::sub(one, z), l0));
+            FOLD(Fr::mul(Fr::sub(Fr::sqr(z), z), llast));
+            FOLD(Fr::mul(Fr::sub(Fr::mul(zn, Fr::add(si, gamma)), Fr::mul(z, Fr::add(ai, gamma))), lactive));
+        }
     }
 #undef FOLD
     ev[a.ev_h] = Fr::mul(acc, den[0]);
@@ -749,7 +766,8 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
         for (uint32_t j : l.phases[ph].challenges) a.ph_chal[cj++] = j;
     }
     a.walk[1] = l.pt[PERMUTED].count;
-    a.walk[2] = l.pt[PERM_Z].count + l.pt[LOOKUP_Z].count + l.pt[RANDOM].count;
+    a.walk[2] = l.pt[PERM_Z].count + l.pt[LOOKUP_Z].count + l.shuffle_pt.count + l.pt[RANDOM].count;
+    a.EV_SH = l.shuffle_ev.first;
     a.walk[3] = l.pt[H_PIECE].count;
     a.PT_RAND = l.pt[RANDOM].first;
     a.EV_FIX = l.ev[EV_FIXED].first; a.EV_SIG = l.ev[EV_SIGMA].first; a.EV_PZ = l.ev[EV_PERM].first; a.EV_LK = l.ev[EV_LOOKUP].first;
@@ -770,8 +788,8 @@ int set_circuits(zg_verifier* v, uint32_t NC) {
     return ZG_OK;
 }
 
-int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fixed_c, const zg_g1_affine* sigma_c,
-                    const zg_g1_affine* g0, const zg_fr* vk_repr) {
+int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_shuffle* shuffles_in, uint32_t n_shuffles, const zg_g1_affine* fixed_c,
+                    const zg_g1_affine* sigma_c, const zg_g1_affine* g0, const zg_fr* vk_repr) {
     VArgs& a = v->a;
     const uint32_t n_log = cs->k;
     const uint64_t n = 1ull << n_log;
@@ -790,6 +808,7 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
     a.vk_repr = fe_of(*vk_repr);
     ProofShape& sh = v->shape;
     sh.A = a.A; sh.F = a.F; sh.P = a.P; sh.NL = a.NL; sh.sets = a.sets; sh.qpd = a.qpd; sh.bf = a.bf; sh.log_n = a.log_n;
+    sh.NS = a.NS = n_shuffles;
     for (uint32_t i = 0; i < a.nAQ; i++) sh.advice_queries.push_back({cs->advice_queries[i].column, cs->advice_queries[i].rotation});
     for (uint32_t i = 0; i < a.nFQ; i++) sh.fixed_queries.push_back({cs->fixed_queries[i].column, cs->fixed_queries[i].rotation});
 
@@ -861,6 +880,7 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
             ZG_REQUIRE(poly_ok(l.inputs[e]) && poly_ok(l.tables[e]), ZG_ERR_INVALID_ARG,
                        "zg_verifier_create: lookup polynomial out of range");
     }
+    std::vector<zg_shuffle> shuffles(shuffles_in, shuffles_in + n_shuffles);  // (validated: shuffles_ok)
     for (uint32_t i = 0; i < a.nAQ; i++)
         ZG_REQUIRE(cs->advice_queries[i].column < a.A, ZG_ERR_INVALID_ARG, "zg_verifier_create: bad advice query");
     for (uint32_t i = 0; i < a.nFQ; i++)
@@ -874,6 +894,7 @@ int verifier_create(zg_verifier* v, const zg_circuit* cs, const zg_g1_affine* fi
     ZG_TRY(upload(v, &a.monos, monos));
     ZG_TRY(upload(v, &a.gates, gates));
     ZG_TRY(upload(v, &a.lookups, lookups));
+    ZG_TRY(upload(v, &a.shuffles, shuffles));
     ZG_TRY(upload(v, &a.qsrc, qsrc));
     ZG_TRY(upload(v, &a.psrc, psrc));
     ZG_TRY(upload(v, &a.iev_col, iev_col));
@@ -890,7 +911,14 @@ extern "C" {
 int zg_verifier_create(zg_ctx* ctx, const zg_circuit* cs, const zg_g1_affine* fixed_commitments,
                        const zg_g1_affine* sigma_commitments, const zg_g1_affine* g0, const zg_g2_affine* g2,
                        const zg_g2_affine* s_g2, const zg_fr* vk_repr, zg_verifier** out) {
+    return zg_verifier_create_shuffles(ctx, cs, nullptr, 0, fixed_commitments, sigma_commitments, g0, g2, s_g2, vk_repr, out);
+}
+
+int zg_verifier_create_shuffles(zg_ctx* ctx, const zg_circuit* cs, const zg_shuffle* shuffles, uint32_t n_shuffles,
+                                const zg_g1_affine* fixed_commitments, const zg_g1_affine* sigma_commitments, const zg_g1_affine* g0,
+                                const zg_g2_affine* g2, const zg_g2_affine* s_g2, const zg_fr* vk_repr, zg_verifier** out) {
     ZG_REQUIRE(ctx && cs && g0 && g2 && s_g2 && vk_repr && out, ZG_ERR_INVALID_ARG, "zg_verifier_create: null argument");
+    ZG_TRY(shuffles_ok("zg_verifier_create_shuffles", cs, shuffles, n_shuffles));  // (the prover's checks, cs_degree included)
     ZG_REQUIRE((fixed_commitments || cs->n_fixed == 0) && (sigma_commitments || cs->n_perm_columns == 0),
                ZG_ERR_INVALID_ARG, "zg_verifier_create: null commitments");
     ZG_REQUIRE(cs->k >= 1 && cs->k <= 28 && cs->cs_degree >= 3, ZG_ERR_UNSUPPORTED, "zg_verifier_create: k = %u, degree %u",
@@ -900,7 +928,7 @@ int zg_verifier_create(zg_ctx* ctx, const zg_circuit* cs, const zg_g1_affine* fi
     v->ctx = ctx;
     v->g2 = *g2;
     v->s_g2 = *s_g2;
-    const int st = verifier_create(v, cs, fixed_commitments, sigma_commitments, g0, vk_repr);
+    const int st = verifier_create(v, cs, shuffles, n_shuffles, fixed_commitments, sigma_commitments, g0, vk_repr);
     if (st != ZG_OK) {
         zg_verifier_destroy(v);
         return st;
@@ -973,6 +1001,8 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
     ZG_REQUIRE(circuits >= 1 && circuits <= 1024, ZG_ERR_INVALID_ARG, "zg_verifier_verify_multi: proofs of %zu circuits", circuits);
     ZG_REQUIRE(circuits == 1 || !v->phased(), ZG_ERR_UNSUPPORTED,
                "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with challenges or advice phases");
+    ZG_REQUIRE(circuits == 1 || v->a.NS == 0, ZG_ERR_UNSUPPORTED,
+               "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with shuffles");
     ZG_REQUIRE(count < (1u << 24) && instance_len < (1u << 24), ZG_ERR_UNSUPPORTED,
                "zg_verifier_verify_batch: %zu proofs of %zu instance rows", count, instance_len);
     if (count == 0) return ZG_OK;

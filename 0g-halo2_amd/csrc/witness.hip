@@ -887,6 +887,7 @@ int zg_witness_run_dev(zg_witness_plan* p, const uint8_t* images, size_t count, 
 //  anything else is asked of the call, a plan included)
 static int images_unphased(const char* who, const zg_prover* p) {
     ZG_REQUIRE(!p || !p->phased(), ZG_ERR_UNSUPPORTED, "%s: not for a circuit with challenges or advice phases", who);
+    ZG_REQUIRE(!p || p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "%s: not for a circuit with shuffles", who);
     return ZG_OK;
 }
 
@@ -932,6 +933,7 @@ int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* i
 
 int zg_prover_prove_images_multi(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t circuits, const uint8_t* rng_keys,
                                  uint8_t* proof, size_t proof_cap, size_t* proof_len, zg_fr* outputs) {
+    ZG_TRY(images_unphased("zg_prover_prove_images_multi", p));
     ZG_REQUIRE(p && plan && images && rng_keys && proof && proof_len && (outputs || !plan->n_instance), ZG_ERR_INVALID_ARG,
                "zg_prover_prove_images_multi: null argument");
     void* slots[64];
@@ -942,6 +944,7 @@ int zg_prover_prove_images_multi(zg_prover* p, zg_witness_plan* plan, const uint
 
 int zg_prover_check_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t count, zg_fr* outputs,
                            zg_failure* failures, size_t cap, uint32_t* totals) {
+    ZG_TRY(images_unphased("zg_prover_check_images", p));
     ZG_REQUIRE(p && plan && images && totals && (outputs || !plan->n_instance) && (failures || cap == 0), ZG_ERR_INVALID_ARG,
                "zg_prover_check_images: null argument");
     void* slots[64];

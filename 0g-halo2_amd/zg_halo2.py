@@ -102,7 +102,34 @@ ABI_SYMBOLS = [
     "zg_prover_set_transcript", "zg_prover_transcript", "zg_verifier_set_transcript", "zg_verifier_transcript",
     "zg_g1_compress", "zg_g1_decompress", "zg_g1_decompress_dev",
     "zg_prover_set_phases", "zg_prover_phases", "zg_prover_prove_phased", "zg_verifier_set_phases", "zg_verifier_phases",
+    "zg_prover_create_shuffles", "zg_prover_create_shared_shuffles", "zg_prover_shuffles", "zg_verifier_create_shuffles",
 ]
+
+# zg_shuffle (include/zg_halo2.h): halo2's shuffle argument, the layout of zg_lookup
+MAX_LOOKUP_WIDTH, MAX_SHUFFLES = 4, 16
+
+
+class Poly(ctypes.Structure):
+    _fields_ = [("first", c_uint32), ("count", c_uint32)]
+
+
+class Shuffle(ctypes.Structure):
+    _fields_ = [("width", c_uint32), ("inputs", Poly * MAX_LOOKUP_WIDTH), ("shuffles", Poly * MAX_LOOKUP_WIDTH)]
+
+
+def shuffle_array(shuffles):
+    """[(inputs [(first, count)], shuffles [(first, count)])] -> (ctypes array of zg_shuffle or None, count): ranges into the
+    circuit image's monomials, to which the caller appended the expressions"""
+    if not shuffles:
+        return None, 0
+    arr = (Shuffle * len(shuffles))()
+    for j, (ins, shs) in enumerate(shuffles):
+        assert len(ins) == len(shs)
+        arr[j].width = len(ins)
+        for e, (a, b) in enumerate(zip(ins[:MAX_LOOKUP_WIDTH], shs[:MAX_LOOKUP_WIDTH])):
+            arr[j].inputs[e] = Poly(*a)
+            arr[j].shuffles[e] = Poly(*b)
+    return arr, len(shuffles)
 
 # zg_query.kind of an Expression::Challenge, and the limits of zg_prover_set_phases
 CHALLENGE, MAX_CHALLENGES, MAX_PHASES = 3, 16, 3
@@ -811,8 +838,10 @@ class Prover:
     """zg_prover: create_proof for one circuit (circuit.py CircuitImage) on one GPU, one proof or a lock-step batch."""
 
     def __init__(self, ctx: Ctx, image, fixed_values: np.ndarray = None, sigma_values: np.ndarray = None, g=None,
-                 g_lagrange=None, vk_repr: np.ndarray = None, _handle=None, _keep=None):
-        """g / g_lagrange: uint64[n, 8] host arrays, or two `Bases` handles shared between provers."""
+                 g_lagrange=None, vk_repr: np.ndarray = None, _handle=None, _keep=None, shuffles=None):
+        """g / g_lagrange: uint64[n, 8] host arrays, or two `Bases` handles shared between provers.
+        shuffles: the circuit's shuffle arguments (shuffle_array's input, or a (ctypes array, count) pair):
+        zg_prover_create_shuffles / zg_prover_create_shared_shuffles."""
         self.ctx = ctx
         self.image = image
         lib = ctx.lib
@@ -835,20 +864,38 @@ class Prover:
             fixed_values = np.ascontiguousarray(fixed_values, dtype=np.uint64)
             sigma_values = np.ascontiguousarray(sigma_values, dtype=np.uint64)
             h = c_void_p()
+            sh = shuffles if isinstance(shuffles, tuple) else shuffle_array(shuffles) if shuffles is not None else None
             if isinstance(g, Bases):
                 self._bases = (g, g_lagrange)  # keep the shared tables alive
-                _check(lib.zg_prover_create_shared(ctx.h, image.ptr(), _ptr(fixed_values), _ptr(sigma_values), g.h,
-                                                   g_lagrange.h, _ptr(_fr(vk_repr)), ctypes.byref(h)))
+                if sh is not None:
+                    _check(lib.zg_prover_create_shared_shuffles(ctx.h, image.ptr(), sh[0], c_uint32(sh[1]), _ptr(fixed_values),
+                                                                _ptr(sigma_values), g.h, g_lagrange.h, _ptr(_fr(vk_repr)),
+                                                                ctypes.byref(h)))
+                else:
+                    _check(lib.zg_prover_create_shared(ctx.h, image.ptr(), _ptr(fixed_values), _ptr(sigma_values), g.h,
+                                                       g_lagrange.h, _ptr(_fr(vk_repr)), ctypes.byref(h)))
             else:
                 g = np.ascontiguousarray(g, dtype=np.uint64)
                 g_lagrange = np.ascontiguousarray(g_lagrange, dtype=np.uint64)
-                _check(lib.zg_prover_create(ctx.h, image.ptr(), _ptr(fixed_values), _ptr(sigma_values), _ptr(g),
-                                            _ptr(g_lagrange), _ptr(_fr(vk_repr)), ctypes.byref(h)))
+                if sh is not None:
+                    _check(lib.zg_prover_create_shuffles(ctx.h, image.ptr(), sh[0], c_uint32(sh[1]), _ptr(fixed_values),
+                                                         _ptr(sigma_values), _ptr(g), _ptr(g_lagrange), _ptr(_fr(vk_repr)),
+                                                         ctypes.byref(h)))
+                else:
+                    _check(lib.zg_prover_create(ctx.h, image.ptr(), _ptr(fixed_values), _ptr(sigma_values), _ptr(g),
+                                                _ptr(g_lagrange), _ptr(_fr(vk_repr)), ctypes.byref(h)))
         self.h = h
         ctx._adopt(self)
         self.n = 1 << image.c.k
         self.n_advice = image.c.n_advice
         self.proof_cap = int(lib.zg_prover_proof_size(h))
+
+    @property
+    def shuffles(self) -> int:
+        """zg_prover_shuffles: the number of shuffle arguments of the prover's circuit"""
+        self.ctx.lib.zg_prover_shuffles.argtypes = [c_void_p]
+        self.ctx.lib.zg_prover_shuffles.restype = c_uint32
+        return int(self.ctx.lib.zg_prover_shuffles(self.h))
 
     def fork(self, ctx: Ctx) -> "Prover":
         """Another prover on the same proving key and base tables (no copy), on another context of the device."""
@@ -1287,9 +1334,9 @@ class Verifier:
     """zg_verifier: batched GWC verification of proofs of one circuit (circuit.py CircuitImage) on one GPU."""
 
     def __init__(self, ctx: Ctx, image, fixed_c: np.ndarray, sigma_c: np.ndarray, g0: np.ndarray, g2: np.ndarray,
-                 s_g2: np.ndarray, vk_repr: np.ndarray):
+                 s_g2: np.ndarray, vk_repr: np.ndarray, shuffles=None):
         """fixed_c / sigma_c: uint64[.., 8] affine commitments (Prover.vk_commitments); g0: uint64[8] = g[0];
-        g2, s_g2: uint64[16] G2 affine points of the parameters."""
+        g2, s_g2: uint64[16] G2 affine points of the parameters; shuffles: as Prover's (zg_verifier_create_shuffles)."""
         self.ctx = ctx
         self.image = image
         lib = ctx.lib
@@ -1297,8 +1344,13 @@ class Verifier:
         lib.zg_verifier_destroy.restype = None
         arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (fixed_c, sigma_c, g0, g2, s_g2)]
         h = c_void_p()
-        _check(lib.zg_verifier_create(ctx.h, image.ptr(), *[_ptr(a) for a in arrs], _ptr(_fr(vk_repr)),
-                                      ctypes.byref(h)))
+        if shuffles is not None:
+            sh = shuffles if isinstance(shuffles, tuple) else shuffle_array(shuffles)
+            _check(lib.zg_verifier_create_shuffles(ctx.h, image.ptr(), sh[0], c_uint32(sh[1]), *[_ptr(a) for a in arrs],
+                                                   _ptr(_fr(vk_repr)), ctypes.byref(h)))
+        else:
+            _check(lib.zg_verifier_create(ctx.h, image.ptr(), *[_ptr(a) for a in arrs], _ptr(_fr(vk_repr)),
+                                          ctypes.byref(h)))
         self.h = h
         ctx._adopt(self)
 

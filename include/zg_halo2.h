@@ -459,6 +459,17 @@ typedef struct {
     zg_poly tables[ZG_MAX_LOOKUP_WIDTH];         /* lookup::Argument::table_expressions */
 } zg_lookup;
 
+/* halo2's shuffle argument (ConstraintSystem::shuffle; privacy-scaling-explorations/halo2 v0.3.0 on): over the usable rows
+ * the tuples (inputs[0..width)) are a permutation of the tuples (shuffles[0..width)).  The layout is zg_lookup's; the
+ * expressions' monomials stand in zg_circuit.monomials with everything else's.  A circuit's shuffles are no part of
+ * zg_circuit: they are handed to zg_prover_create_shuffles / zg_verifier_create_shuffles beside it. */
+typedef struct {
+    uint32_t width;                              /* tuple length m, 1 .. ZG_MAX_LOOKUP_WIDTH */
+    zg_poly inputs[ZG_MAX_LOOKUP_WIDTH];         /* shuffle::Argument::input_expressions */
+    zg_poly shuffles[ZG_MAX_LOOKUP_WIDTH];       /* shuffle::Argument::shuffle_expressions */
+} zg_shuffle;
+enum { ZG_MAX_SHUFFLES = 16 };
+
 typedef struct {
     uint32_t k;                  /* rows = 2^k */
     uint32_t cs_degree;          /* ConstraintSystem::degree(); extended domain = smallest 2^e >= 2^k*(degree-1) */
@@ -507,6 +518,27 @@ int zg_prover_create(zg_ctx *ctx, const zg_circuit *circuit, const zg_fr *fixed_
 int zg_prover_create_shared(zg_ctx *ctx, const zg_circuit *circuit, const zg_fr *fixed_values,
                             const zg_fr *sigma_values, const zg_bases *g, const zg_bases *g_lagrange,
                             const zg_fr *vk_repr, zg_prover **out);
+/* zg_prover_create / zg_prover_create_shared for a circuit with shuffle arguments (n_shuffles = 0: the same call).  Per
+ * shuffle j the prover commits one product z_j where the lookup products are committed -- z_j[0] = 1,
+ * z_j[r + 1] = z_j[r] (a[r] + gamma) / (s[r] + gamma) over the usable rows, a and s the theta-folds of the two tuples as the
+ * lookups fold theirs, the blinding_factors rows behind them rand_fr(key, 10, j * blinding_factors + i) for the i-th -- adds l_0 (1 - z), l_last (z^2 - z) and
+ * (1 - (l_last + l_blind)) (z(wX) (s + gamma) - z(X) (a + gamma)) to the quotient behind all lookup terms, and evaluates
+ * and opens z_j at x and omega x behind the lookups' (DESIGN.md section 19).  circuit->cs_degree must cover
+ * max(2 + deg a, 2 + deg s), an expression's degree counting as at least 1.  A witness that is no shuffle still yields
+ * ZG_OK and a proof of full length, which no verifier accepts (upstream checks the product only under its sanity-check
+ * feature).  ZG_ERR_INVALID_ARG: a null array with a count, a width of 0 or above ZG_MAX_LOOKUP_WIDTH, a polynomial outside
+ * the monomials, a cs_degree below the shuffles'; ZG_ERR_UNSUPPORTED: more than ZG_MAX_SHUFFLES.
+ * A prover with shuffles makes single proofs and lock-step batches (zg_prover_prove, _dev, _batch, _batch_dev, _phased);
+ * zg_prover_prove_multi* of several circuits, zg_prover_prove_images*, zg_prover_check_*, a point-range shard and the
+ * arithmetic-level entries that take the whole circuit (zg_prover_evaluate_h*) answer ZG_ERR_UNSUPPORTED. */
+int zg_prover_create_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
+                              const zg_fr *fixed_values, const zg_fr *sigma_values, const zg_g1_affine *g,
+                              const zg_g1_affine *g_lagrange, const zg_fr *vk_repr, zg_prover **out);
+int zg_prover_create_shared_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
+                                     const zg_fr *fixed_values, const zg_fr *sigma_values, const zg_bases *g,
+                                     const zg_bases *g_lagrange, const zg_fr *vk_repr, zg_prover **out);
+/* the number of shuffle arguments of the prover's circuit */
+uint32_t zg_prover_shuffles(const zg_prover *p);
 /* A second prover on the SAME proving key (no copy: the key's HBM is shared and freed with its last prover) and
  * the same base tables (tables the parent registered itself are owned jointly and freed with the last prover; tables
  * the caller registered stay the caller's), on another context of the device -- another stream of proofs or proof
@@ -655,7 +687,10 @@ size_t zg_prover_proof_size(const zg_prover *p);
  * 4 = permuted table s' (index = lookup), 5 = h pieces in coefficient form [5 * 2^k].  The pseudo-column of
  * challenge `index` (zg_prover_set_phases): 6 = its value row [2^k], 7 = its coefficient row [2^k], 8 = its slab on the
  * single extended coset [2^ext_k], 9 / 10 = its slabs on the first / second part of the split domain; the slabs in
- * plain Montgomery form, and only for the extended domain the last proof used (else ZG_ERR_INVALID_ARG). */
+ * plain Montgomery form, and only for the extended domain the last proof used (else ZG_ERR_INVALID_ARG).
+ * 11 = shuffle z (index = shuffle) [2^k Lagrange].  12 / 13 = h on the first / second part of the split domain, as the
+ * last proof left it there (plain Montgomery form; ZG_ERR_INVALID_ARG when that proof used the single coset, or took the
+ * quotient's terms by degree, which reuses those buffers: zg_prover_set_quotient_terms(0) keeps them). */
 int zg_prover_fetch(zg_prover *p, uint32_t what, uint32_t index, zg_fr *out, size_t cap_elems);
 /* ... of proof `slot` of the last batch. */
 int zg_prover_fetch_slot(zg_prover *p, size_t slot, uint32_t what, uint32_t index, zg_fr *out, size_t cap_elems);
@@ -957,6 +992,15 @@ int zg_prover_vk_commitments(const zg_prover *p, zg_g1_affine *fixed_out, zg_g1_
 int zg_verifier_create(zg_ctx *ctx, const zg_circuit *circuit, const zg_g1_affine *fixed_commitments,
                        const zg_g1_affine *sigma_commitments, const zg_g1_affine *g0, const zg_g2_affine *g2,
                        const zg_g2_affine *s_g2, const zg_fr *vk_repr, zg_verifier **out);
+/* ... for a circuit with shuffle arguments (zg_prover_create_shuffles; n_shuffles = 0: the same call): the walk reads the
+ * shuffle products behind the lookup products and their evaluations behind the lookups', the expected h(x) takes the
+ * three terms per shuffle behind the lookup terms and the opening check the two queries per shuffle.  The shuffles are
+ * validated as zg_prover_create_shuffles validates them, circuit->cs_degree included.  zg_verifier_verify_multi
+ * of several circuits answers ZG_ERR_UNSUPPORTED for such a verifier. */
+int zg_verifier_create_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
+                                const zg_g1_affine *fixed_commitments, const zg_g1_affine *sigma_commitments,
+                                const zg_g1_affine *g0, const zg_g2_affine *g2, const zg_g2_affine *s_g2, const zg_fr *vk_repr,
+                                zg_verifier **out);
 void zg_verifier_destroy(zg_verifier *v);
 /* Verifies `count` proofs (EvmTranscript bytes proofs[b], proof_lens[b] long) against their public inputs
  * instance[b] ([n_instance][instance_len], as zg_prover_prove_batch takes them).  verdicts[b]: 1 = accepted; 0 = the
