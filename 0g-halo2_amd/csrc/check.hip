@@ -13,8 +13,17 @@
 // A failing lane sets its bit in a per-witness bitmap [constraint][n / 64] (one wave ballot = one 64-bit word, plain
 // vector stores) and a workgroup with failures bumps its witness's counter of that kind once.  The host reads the
 // count x 3 totals; only a witness with failures has its bitmap read back and walked into ordered records.
+//
+// zg_prover_check_circuit*  add, through the same check_batch_impl:
+//   challenges  the caller's values, one constant pseudo-column each behind the instance columns, read through Cols as
+//               any column is;
+//   shuffles    EXACT multiset equality.  Both sides' tuples are evaluated to canonical integers, each side's rows are
+//               sorted by (tuple, row) with the index network of the lookup tables under the comparator of
+//               check_tuple.h, and position by position the two orders are compared: the input row at a position whose
+//               tuple differs from the shuffle row's at that position fails, and names that row.  A fourth total.
 #include "prover.h"
 #include "poly_eval.h"
+#include "check_tuple.h"
 
 #include <algorithm>
 
@@ -176,26 +185,26 @@ __device__ __forceinline__ bool tup_greater(const TupView& t, uint32_t i, uint32
 constexpr uint32_t CS_CH = 1024;  // row indices per LDS chunk
 constexpr uint32_t CS_NT = 512;
 
-__device__ __forceinline__ void idx_cmpx(uint32_t* sh, const TupView& t, uint32_t i, uint32_t j, bool ascending) {
+// what the index network orders by: a lookup table's tuples, or a shuffle side's (tuple, row)
+__device__ __forceinline__ bool row_greater(const TupView& t, uint32_t i, uint32_t j) { return tup_greater(t, i, j); }
+__device__ __forceinline__ bool row_greater(const RowTuples& t, uint32_t i, uint32_t j) { return row_after(t, i, j); }
+
+template <class View>
+__device__ __forceinline__ void idx_cmpx(uint32_t* sh, const View& t, uint32_t i, uint32_t j, bool ascending) {
     const uint32_t a = sh[i], b = sh[j];
-    if (tup_greater(t, a, b) == ascending) {
+    if (row_greater(t, a, b) == ascending) {
         sh[i] = b;
         sh[j] = a;
     }
 }
 
-// The bitonic network of sort.hip over ROW INDICES (the keys stay where they are; a comparison gathers them).
+// The bitonic network of sort.hip over ROW INDICES (the keys stay where they are; a comparison gathers them), one
+// workgroup of CS_NT lanes on the chunk of `len` indices at `base`, position g0 of its row.
 // merge_size = 0: the indices are created here (idx[i] = i) and every chunk becomes a sorted run, direction alternating
 // with bit CS_CH of its position; otherwise the strides below CS_CH of merge level `merge_size`.
-__global__ __launch_bounds__(CS_NT) void check_sort_local_kernel(uint32_t* __restrict__ idx, size_t idx_bs, const Fe* __restrict__ vals,
-                                                                 size_t vals_bs, DevCircuit c, TabSlots sl, uint32_t n,
-                                                                 uint32_t usable, uint32_t merge_size) {
-    __shared__ uint32_t sh[CS_CH];
-    const uint32_t s = blockIdx.y, b = blockIdx.z;
-    const uint32_t g0 = blockIdx.x * CS_CH;
-    const uint32_t len = n < CS_CH ? n : CS_CH;
-    uint32_t* base = idx + (size_t)b * idx_bs + (size_t)s * n + g0;
-    const TupView t{vals + (size_t)b * vals_bs + sl.off[s], n, usable, c.lookups[sl.lookup[s]].width};
+template <class View>
+__device__ __forceinline__ void idx_sort_local(uint32_t* sh, uint32_t* __restrict__ base, const View& t, uint32_t g0, uint32_t len,
+                                               uint32_t merge_size) {
     for (uint32_t e = threadIdx.x; e < len; e += CS_NT) sh[e] = merge_size ? base[e] : g0 + e;
     __syncthreads();
     if (!merge_size) {
@@ -221,20 +230,34 @@ __global__ __launch_bounds__(CS_NT) void check_sort_local_kernel(uint32_t* __res
     for (uint32_t e = threadIdx.x; e < len; e += CS_NT) base[e] = sh[e];
 }
 
-// one compare-exchange pass with stride >= CS_CH
+// one compare-exchange of the pass with stride >= CS_CH: pair q of the row of n indices at `base`
+template <class View>
+__device__ __forceinline__ void idx_sort_global(uint32_t* __restrict__ base, const View& t, uint32_t q, uint32_t size, uint32_t stride) {
+    const uint32_t i = 2 * q - (q & (stride - 1)), j = i + stride;
+    const uint32_t a = base[i], bb = base[j];
+    if (row_greater(t, a, bb) == ((i & size) == 0)) {
+        base[i] = bb;
+        base[j] = a;
+    }
+}
+
+__global__ __launch_bounds__(CS_NT) void check_sort_local_kernel(uint32_t* __restrict__ idx, size_t idx_bs, const Fe* __restrict__ vals,
+                                                                 size_t vals_bs, DevCircuit c, TabSlots sl, uint32_t n,
+                                                                 uint32_t usable, uint32_t merge_size) {
+    __shared__ uint32_t sh[CS_CH];
+    const uint32_t s = blockIdx.y, b = blockIdx.z;
+    const uint32_t g0 = blockIdx.x * CS_CH;
+    const TupView t{vals + (size_t)b * vals_bs + sl.off[s], n, usable, c.lookups[sl.lookup[s]].width};
+    idx_sort_local(sh, idx + (size_t)b * idx_bs + (size_t)s * n + g0, t, g0, n < CS_CH ? n : CS_CH, merge_size);
+}
+
 __global__ __launch_bounds__(256) void check_sort_global_kernel(uint32_t* __restrict__ idx, size_t idx_bs, const Fe* __restrict__ vals,
                                                                 size_t vals_bs, DevCircuit c, TabSlots sl, uint32_t n, uint32_t usable,
                                                                 uint32_t size, uint32_t stride) {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, b = blockIdx.z;
     if (q >= n / 2) return;
-    uint32_t* base = idx + (size_t)b * idx_bs + (size_t)s * n;
     const TupView t{vals + (size_t)b * vals_bs + sl.off[s], n, usable, c.lookups[sl.lookup[s]].width};
-    const uint32_t i = 2 * q - (q & (stride - 1)), j = i + stride;
-    const uint32_t a = base[i], bb = base[j];
-    if (tup_greater(t, a, bb) == ((i & size) == 0)) {
-        base[i] = bb;
-        base[j] = a;
-    }
+    idx_sort_global(idx + (size_t)b * idx_bs + (size_t)s * n, t, q, size, stride);
 }
 
 // sorted[.. + e * n + i] = vals[.. + e * n + idx[i]], i < usable
@@ -272,6 +295,118 @@ static int prepare_tables(zg_ctx* ctx, const DevCircuit& dc, const Cols& cols, c
     }
     ZG_LAUNCH(ctx, "check_table_gather", cells * 64, check_table_gather_kernel, dim3((usable + 255) / 256, ns, nb), dim3(256), 0, idx,
               idx_bs, vals, vals_bs, sorted, sorted_bs, dc, sl, n, usable);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+// ------------------------------------------------------------------ challenges and shuffles (zg_prover_check_circuit*)
+// inst + b * inst_bs + (col0 + j) * n + row = challenge j of witness b, on all n rows
+__global__ __launch_bounds__(256) void check_challenge_fill_kernel(Fe* __restrict__ inst, size_t inst_bs, const Fe* __restrict__ chal,
+                                                                   uint32_t col0, uint32_t n_chal, uint32_t n) {
+    const uint32_t row = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, b = blockIdx.z;
+    if (row >= n) return;
+    stg(inst + (size_t)b * inst_bs + (size_t)(col0 + j) * n + row, ldg(chal + (size_t)b * n_chal + j));
+}
+
+constexpr uint32_t CK_NO_PARTNER = 0xffffffffu;
+
+// shuffle j's values of a witness, [side][width][n] canonical integers (side 0: the input expressions), start off[j]
+// elements into the witness's; grid.y of the kernels below = 2 j + side, or j
+struct ShufSlots {
+    const DLookup* sh;
+    uint32_t off[ZG_MAX_SHUFFLES];
+};
+__device__ __forceinline__ RowTuples shuf_side(const ShufSlots& a, const Fe* vals, uint32_t j, uint32_t side, uint32_t n, uint32_t usable) {
+    const uint32_t width = a.sh[j].width;
+    return RowTuples{reinterpret_cast<const uint32_t*>(vals + a.off[j] + (size_t)side * width * n), n, usable, width};
+}
+
+__global__ __launch_bounds__(256) void check_shuffle_eval_kernel(DevCircuit c, Cols cols_all, ShufSlots a, Fe* __restrict__ vals,
+                                                                 size_t vals_bs, uint32_t n) {
+    const uint32_t row = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y >> 1, side = blockIdx.y & 1u, b = blockIdx.z;
+    if (row >= n) return;
+    const Cols cols = cols_of(cols_all, b);
+    const DLookup* sf = a.sh + j;
+    const zg_poly* ex = side ? sf->tables : sf->inputs;
+    Fe* out = vals + (size_t)b * vals_bs + a.off[j] + (size_t)side * sf->width * n + row;
+    for (uint32_t e = 0; e < sf->width; e++) stg(out + (size_t)e * n, Fr::to_raw(eval_poly(c, cols, ex[e], row)));
+}
+
+// idx: [nb][2 NS][n] row indices, row 2 j + side
+__global__ __launch_bounds__(CS_NT) void check_shuffle_sort_local_kernel(uint32_t* __restrict__ idx, size_t idx_bs,
+                                                                         const Fe* __restrict__ vals, size_t vals_bs, ShufSlots a,
+                                                                         uint32_t n, uint32_t usable, uint32_t merge_size) {
+    __shared__ uint32_t sh[CS_CH];
+    const uint32_t s = blockIdx.y, b = blockIdx.z;
+    const uint32_t g0 = blockIdx.x * CS_CH;
+    const RowTuples t = shuf_side(a, vals + (size_t)b * vals_bs, s >> 1, s & 1u, n, usable);
+    idx_sort_local(sh, idx + (size_t)b * idx_bs + (size_t)s * n + g0, t, g0, n < CS_CH ? n : CS_CH, merge_size);
+}
+
+__global__ __launch_bounds__(256) void check_shuffle_sort_global_kernel(uint32_t* __restrict__ idx, size_t idx_bs,
+                                                                        const Fe* __restrict__ vals, size_t vals_bs, ShufSlots a,
+                                                                        uint32_t n, uint32_t usable, uint32_t size, uint32_t stride) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, b = blockIdx.z;
+    if (q >= n / 2) return;
+    const RowTuples t = shuf_side(a, vals + (size_t)b * vals_bs, s >> 1, s & 1u, n, usable);
+    idx_sort_global(idx + (size_t)b * idx_bs + (size_t)s * n, t, q, size, stride);
+}
+
+// Position i of the two orders: the input row there against the shuffle row there.  partner: [nb][NS][n]; the usable rows
+// sort first on both sides, so every input row below `usable` is written exactly once and no other word is written.
+__global__ __launch_bounds__(256) void check_shuffle_compare_kernel(ShufSlots a, const uint32_t* __restrict__ idx, size_t idx_bs,
+                                                                    const Fe* __restrict__ vals, size_t vals_bs,
+                                                                    uint32_t* __restrict__ partner, size_t partner_bs, uint32_t n,
+                                                                    uint32_t usable) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, b = blockIdx.z;
+    if (i >= usable) return;
+    const uint32_t* rows = idx + (size_t)b * idx_bs + (size_t)2 * j * n;
+    const uint32_t ra = rows[i], rb = rows[n + i];
+    if (ra >= usable || rb >= usable) return;  // (cannot happen: the usable rows sort first)
+    const Fe* v = vals + (size_t)b * vals_bs;
+    const RowTuples in = shuf_side(a, v, j, 0, n, usable), sf = shuf_side(a, v, j, 1, n, usable);
+    partner[(size_t)b * partner_bs + (size_t)j * n + ra] = row_tuple_cmp(in, ra, sf, rb) ? rb : CK_NO_PARTNER;
+}
+
+// the shuffles' rows of the bitmap (constraints first .. first + NS - 1) and the witness's shuffle total
+__global__ __launch_bounds__(256) void check_shuffle_flag_kernel(const uint32_t* __restrict__ partner, size_t partner_bs, uint32_t n,
+                                                                 uint32_t usable, unsigned long long* __restrict__ bm, uint32_t nc,
+                                                                 uint32_t first, uint32_t w, uint32_t* __restrict__ totals) {
+    const uint32_t row = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, b = blockIdx.z;
+    const bool bad = row < usable && partner[(size_t)b * partner_bs + (size_t)j * n + row] != CK_NO_PARTNER;
+    flag_rows(bad, row, n, bm + ((size_t)b * nc + first + j) * w, totals + b);
+}
+
+// The shuffles of nb witnesses: vals [nb][vals_bs] elements, idx [nb][2 NS][n], partner [nb][NS][n] words; tot4: [nb].
+static int check_shuffles(zg_ctx* ctx, const PkDev& v, const Cols& cols, uint32_t nb, Fe* vals, size_t vals_bs, uint32_t* idx,
+                          uint32_t* partner, unsigned long long* bm, uint32_t nc, uint32_t w, uint32_t* tot4) {
+    const uint32_t n = v.n, usable = v.usable, NS = v.NS;
+    ShufSlots sl{};
+    sl.sh = v.d_shuffles;
+    size_t at = 0;
+    for (uint32_t j = 0; j < NS; j++) {
+        sl.off[j] = (uint32_t)at;
+        at += (size_t)2 * v.shuffles[j].width * n;
+    }
+    const size_t idx_bs = (size_t)2 * NS * n, partner_bs = (size_t)NS * n;
+    const double cells = (double)nb * (double)vals_bs;
+    ZG_LAUNCH(ctx, "check_shuffle_eval", cells * 64, check_shuffle_eval_kernel, dim3((n + 255) / 256, 2 * NS, nb), dim3(256), 0, v.dc, cols,
+              sl, vals, vals_bs, n);
+    const uint32_t chunks = n <= CS_CH ? 1 : n / CS_CH;
+    const dim3 gl(chunks, 2 * NS, nb), gg((n / 2 + 255) / 256, 2 * NS, nb);
+    ZG_LAUNCH(ctx, "check_shuffle_sort_local", cells * 32, check_shuffle_sort_local_kernel, gl, dim3(CS_NT), 0, idx, idx_bs, vals, vals_bs,
+              sl, n, usable, 0u);
+    for (uint32_t size = 2 * CS_CH; size <= n; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride >= CS_CH; stride >>= 1)
+            ZG_LAUNCH(ctx, "check_shuffle_sort_global", cells * 32, check_shuffle_sort_global_kernel, gg, dim3(256), 0, idx, idx_bs, vals,
+                      vals_bs, sl, n, usable, size, stride);
+        ZG_LAUNCH(ctx, "check_shuffle_sort_local", cells * 32, check_shuffle_sort_local_kernel, gl, dim3(CS_NT), 0, idx, idx_bs, vals,
+                  vals_bs, sl, n, usable, size);
+    }
+    ZG_LAUNCH(ctx, "check_shuffle_compare", cells * 32, check_shuffle_compare_kernel, dim3((usable + 255) / 256, NS, nb), dim3(256), 0, sl,
+              idx, idx_bs, vals, vals_bs, partner, partner_bs, n, usable);
+    ZG_LAUNCH(ctx, "check_shuffle_flag", (double)nb * NS * n * 4, check_shuffle_flag_kernel, dim3((n + 255) / 256, NS, nb), dim3(256), 0,
+              partner, partner_bs, n, usable, bm, nc, v.NG + v.NL + v.P, w, tot4);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
@@ -402,18 +537,23 @@ static int check_key(zg_ctx* ctx, PkDev& v, std::shared_ptr<CheckKey>& out) {
 }
 
 // ------------------------------------------------------------------ the check
-static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advice_host, void* const* advice_dev,
-                            const zg_fr* const* instance, size_t instance_len, zg_failure* failures, size_t cap, uint32_t* totals) {
-    ZG_REQUIRE(p && totals, ZG_ERR_INVALID_ARG, "zg_prover_check: null argument");
-    ZG_REQUIRE(failures || cap == 0, ZG_ERR_INVALID_ARG, "zg_prover_check: room for %zu failures per witness but no array", cap);
+// What every entry shares.  nk: totals per witness -- 3 (zg_prover_check_batch*: their refusals are decided in front of
+// this) or 4 (zg_prover_check_circuit*: a shuffle total, and `challenges` [count][n_chal] for the challenges' columns).
+static int check_batch_impl(const char* who, zg_prover* p, size_t count, const zg_fr* const* advice_host, void* const* advice_dev,
+                            const zg_fr* const* instance, size_t instance_len, const zg_fr* challenges, uint32_t nk,
+                            zg_failure* failures, size_t cap, uint32_t* totals) {
+    ZG_REQUIRE(p && totals, ZG_ERR_INVALID_ARG, "%s: null argument", who);
+    ZG_REQUIRE(failures || cap == 0, ZG_ERR_INVALID_ARG, "%s: room for %zu failures per witness but no array", who, cap);
     zg_ctx* ctx = p->ctx;
     ZG_ENTER(ctx);
     PkDev& v = *p->pk;  // (the key: the circuit's shape, its tables, the fixed and sigma values)
-    ZG_REQUIRE(!p->phased(), ZG_ERR_UNSUPPORTED, "zg_prover_check: not for a circuit with challenges or advice phases (the check knows no challenge values)");
-    ZG_REQUIRE(p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "zg_prover_check: not for a circuit with shuffles (the totals have no place for a shuffle's)");
-    ZG_TRY(batch_args_ok("zg_prover_check", "witnesses", p, count, instance, instance_len));
-    if (v.I && instance_len)
-        for (size_t b = 0; b < count; b++) ZG_REQUIRE(instance[b], ZG_ERR_INVALID_ARG, "zg_prover_check: instance %zu is null", b);
+    const uint32_t NS = nk == 4 ? v.NS : 0;
+    // (the challenges' columns exist for every entry; only zg_prover_check_circuit* has values for them)
+    const uint32_t n_chal = std::max<uint32_t>(v.NC, (uint32_t)p->challenge_phase.size());
+    ZG_REQUIRE(nk != 4 || !v.NC || challenges, ZG_ERR_INVALID_ARG, "%s: the circuit has %u challenges but challenges is null", who, v.NC);
+    ZG_TRY(batch_args_ok(who, "witnesses", p, count, instance, instance_len));
+    if (v.IU && instance_len)
+        for (size_t b = 0; b < count; b++) ZG_REQUIRE(instance[b], ZG_ERR_INVALID_ARG, "%s: instance %zu is null", who, b);
     if (p->in_flight) ZG_TRY(prover_drain(p));  // (a batch left through an error return may still read the slots)
     std::shared_ptr<CheckKey> ck;
     ZG_TRY(check_key(ctx, v, ck));
@@ -421,12 +561,16 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
     hipStream_t st = ctx->stream;
     const uint32_t nb = (uint32_t)count, n = v.n;
     const size_t adv_bs = (size_t)v.A * n, inst_bs = (size_t)v.I * n;
+    size_t shuf_bs = 0;  // a witness's shuffle values: [side][width][n] per shuffle
+    for (uint32_t j = 0; j < NS; j++) shuf_bs += (size_t)2 * v.shuffles[j].width * n;
+    ZG_REQUIRE(shuf_bs < (1ull << 32), ZG_ERR_UNSUPPORTED, "%s: shuffles too large", who);
     ZG_TRY(advice_into_slots(p, nb, advice_host, advice_dev));
-    const uint32_t nc = v.NG + v.NL + v.P, w = (n + 63) / 64;
+    const uint32_t nc = v.NG + v.NL + v.P + NS, w = (n + 63) / 64;
+    const bool fill_chal = nk == 4 && v.NC;
     WsScope ws(ctx);
     Fe* inst = ws.get<Fe>((size_t)nb * inst_bs);  // the prover's own instance columns belong to its proofs
     unsigned long long* bm = ws.get<unsigned long long>((size_t)nb * nc * w);
-    uint32_t* d_tot = ws.get<uint32_t>((size_t)nb * 3);
+    uint32_t* d_tot = ws.get<uint32_t>((size_t)nb * 4);  // [nb][3] by kind, then [nb] shuffle totals
     Fe *var_vals = nullptr, *var_sorted = nullptr;
     uint32_t* var_idx = nullptr;
     if (ck->n_var) {
@@ -434,26 +578,46 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
         var_sorted = ws.get<Fe>((size_t)nb * ck->var_elems);
         var_idx = ws.get<uint32_t>((size_t)nb * ck->n_var * n);
     }
+    Fe *d_chal = nullptr, *shuf_vals = nullptr;
+    uint32_t *shuf_idx = nullptr, *partner = nullptr;
+    if (fill_chal) d_chal = ws.get<Fe>((size_t)nb * v.NC);
+    if (NS) {
+        shuf_vals = ws.get<Fe>((size_t)nb * shuf_bs);
+        shuf_idx = ws.get<uint32_t>((size_t)nb * 2 * NS * n);
+        partner = ws.get<uint32_t>((size_t)nb * NS * n);
+    }
     if (ws.failed) return ZG_ERR_OOM;
-    const size_t in_bytes = (size_t)nb * v.I * instance_len * 32, tot_off = (in_bytes + 63) & ~size_t(63);
-    ZG_TRY(pinned_reserve(ctx, tot_off + (size_t)nb * 3 * 4 + 64));
-    ZG_HIP(hipMemsetAsync(d_tot, 0, (size_t)nb * 3 * 4, st));
+    const size_t col_bytes = instance_len * 32, in_bytes = (size_t)nb * v.IU * col_bytes, chal_off = (in_bytes + 63) & ~size_t(63);
+    const size_t chal_bytes = fill_chal ? (size_t)nb * v.NC * 32 : 0, tot_off = (chal_off + chal_bytes + 63) & ~size_t(63);
+    ZG_TRY(pinned_reserve(ctx, tot_off + (size_t)nb * 4 * 4 + 64));
+    ZG_HIP(hipMemsetAsync(d_tot, 0, (size_t)nb * 4 * 4, st));
     if (v.I) {
         ZG_HIP(hipMemsetAsync(inst, 0, (size_t)nb * inst_bs * 32, st));
-        if (instance_len) {
-            for (uint32_t b = 0; b < nb; b++)
-                memcpy((char*)ctx->pinned + (size_t)b * v.I * instance_len * 32, instance[b], (size_t)v.I * instance_len * 32);
-            ZG_HIP(hipMemcpy2DAsync(inst, (size_t)n * 32, ctx->pinned, instance_len * 32, instance_len * 32, (size_t)nb * v.I,
-                                    hipMemcpyHostToDevice, st));
+        if (v.IU && instance_len) {
+            for (uint32_t b = 0; b < nb; b++) memcpy((char*)ctx->pinned + (size_t)b * v.IU * col_bytes, instance[b], (size_t)v.IU * col_bytes);
+            if (v.I == v.IU) {
+                ZG_HIP(hipMemcpy2DAsync(inst, (size_t)n * 32, ctx->pinned, col_bytes, col_bytes, (size_t)nb * v.IU, hipMemcpyHostToDevice, st));
+            } else {  // (the challenges' columns stand between one witness's instance columns and the next's)
+                for (uint32_t b = 0; b < nb; b++)
+                    ZG_HIP(hipMemcpy2DAsync(inst + (size_t)b * inst_bs, (size_t)n * 32, (char*)ctx->pinned + (size_t)b * v.IU * col_bytes,
+                                            col_bytes, col_bytes, v.IU, hipMemcpyHostToDevice, st));
+            }
         }
+    }
+    const dim3 blk(256);
+    const uint32_t rb = (n + 255) / 256;
+    const double rows = (double)nb * n;
+    if (fill_chal) {
+        char* h_chal = (char*)ctx->pinned + chal_off;
+        for (uint32_t b = 0; b < nb; b++) memcpy(h_chal + (size_t)b * v.NC * 32, (const char*)challenges + (size_t)b * n_chal * 32, (size_t)v.NC * 32);
+        ZG_HIP(hipMemcpyAsync(d_chal, h_chal, chal_bytes, hipMemcpyHostToDevice, st));
+        ZG_LAUNCH(ctx, "check_challenge_fill", rows * v.NC * 32, check_challenge_fill_kernel, dim3(rb, v.NC, nb), blk, 0, inst, inst_bs, d_chal,
+                  v.IU, v.NC, n);
     }
     Cols cols{};
     cols.fixed = v.fixed_val; cols.advice = p->adv_val; cols.instance = inst;
     cols.log_size = v.k; cols.rot_scale = 1;
     cols.adv_bs = adv_bs; cols.inst_bs = inst_bs;
-    const dim3 blk(256);
-    const uint32_t rb = (n + 255) / 256;
-    const double rows = (double)nb * n;
     if (v.NG)
         ZG_LAUNCH(ctx, "check_gates", rows * (v.F + v.A + v.I) * 32, check_gates_kernel, dim3(rb, v.NG, nb), blk, 0, v.dc, cols, n, v.usable,
                   bm, nc, w, d_tot);
@@ -466,25 +630,37 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
     if (v.P)
         ZG_LAUNCH(ctx, "check_copies", rows * v.P * 72, check_copies_kernel, dim3(rb, v.P, nb), blk, 0, v.dc, cols, ck->d_next, n, bm, nc, w,
                   d_tot);
+    if (NS) ZG_TRY(check_shuffles(ctx, v, cols, nb, shuf_vals, shuf_bs, shuf_idx, partner, bm, nc, w, d_tot + (size_t)nb * 3));
     ZG_HIP(hipGetLastError());
     uint32_t* h_tot = reinterpret_cast<uint32_t*>((char*)ctx->pinned + tot_off);
-    ZG_HIP(hipMemcpyAsync(h_tot, d_tot, (size_t)nb * 3 * 4, hipMemcpyDeviceToHost, st));
+    ZG_HIP(hipMemcpyAsync(h_tot, d_tot, (size_t)nb * 4 * 4, hipMemcpyDeviceToHost, st));
     ZG_HIP(hipStreamSynchronize(st));
-    memcpy(totals, h_tot, (size_t)nb * 3 * 4);
+    for (uint32_t b = 0; b < nb; b++) {
+        memcpy(totals + (size_t)nk * b, h_tot + 3 * b, 3 * 4);
+        if (nk == 4) totals[(size_t)nk * b + ZG_FAIL_SHUFFLE] = h_tot[(size_t)nb * 3 + b];
+    }
 
     // ---- the report: only a witness with failures has its bitmap walked, constraint by constraint, row by row
     std::vector<unsigned long long> hbm;
+    std::vector<uint32_t> hpart;
+    const uint32_t first_shuffle = v.NG + v.NL + v.P;
     for (uint32_t b = 0; b < nb && cap; b++) {
-        const uint64_t total = (uint64_t)totals[3 * b] + totals[3 * b + 1] + totals[3 * b + 2];
+        uint64_t total = 0;
+        for (uint32_t kd = 0; kd < nk; kd++) total += totals[(size_t)nk * b + kd];
         if (!total) continue;
         hbm.resize((size_t)nc * w);
         ZG_HIP(hipMemcpyAsync(hbm.data(), bm + (size_t)b * nc * w, hbm.size() * 8, hipMemcpyDeviceToHost, st));
+        if (nk == 4 && totals[(size_t)nk * b + ZG_FAIL_SHUFFLE]) {  // (whom each failing row met)
+            hpart.resize((size_t)NS * n);
+            ZG_HIP(hipMemcpyAsync(hpart.data(), partner + (size_t)b * NS * n, hpart.size() * 4, hipMemcpyDeviceToHost, st));
+        }
         ZG_HIP(hipStreamSynchronize(st));
         zg_failure* out = failures + (size_t)b * cap;
         size_t at = 0;
         for (uint32_t ci = 0; ci < nc && at < cap; ci++) {
-            const uint32_t kind = ci < v.NG ? ZG_FAIL_GATE : ci < v.NG + v.NL ? ZG_FAIL_LOOKUP : ZG_FAIL_COPY;
-            const uint32_t index = kind == ZG_FAIL_GATE ? ci : kind == ZG_FAIL_LOOKUP ? ci - v.NG : ci - v.NG - v.NL;
+            const uint32_t kind = ci < v.NG ? ZG_FAIL_GATE : ci < v.NG + v.NL ? ZG_FAIL_LOOKUP : ci < first_shuffle ? ZG_FAIL_COPY : ZG_FAIL_SHUFFLE;
+            const uint32_t index = kind == ZG_FAIL_GATE ? ci : kind == ZG_FAIL_LOOKUP ? ci - v.NG : kind == ZG_FAIL_COPY ? ci - v.NG - v.NL
+                                                                                                                          : ci - first_shuffle;
             for (uint32_t wi = 0; wi < w && at < cap; wi++) {
                 unsigned long long m = hbm[(size_t)ci * w + wi];
                 while (m && at < cap) {
@@ -495,12 +671,21 @@ static int check_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
                         const uint32_t to = ck->next[(size_t)index * n + row];
                         f.other_index = to / n;
                         f.other_row = to % n;
+                    } else if (kind == ZG_FAIL_SHUFFLE) {
+                        f.other_row = hpart[(size_t)index * n + row];
                     }
                     out[at++] = f;
                 }
             }
         }
     }
+    return ZG_OK;
+}
+
+// zg_prover_check_batch* and zg_prover_check_images know three kinds and no challenge values
+static int check_three_kinds(const zg_prover* p) {
+    ZG_REQUIRE(!p || !p->phased(), ZG_ERR_UNSUPPORTED, "zg_prover_check: not for a circuit with challenges or advice phases (the check knows no challenge values)");
+    ZG_REQUIRE(!p || p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "zg_prover_check: not for a circuit with shuffles (the totals have no place for a shuffle's)");
     return ZG_OK;
 }
 
@@ -512,12 +697,25 @@ extern "C" {
 
 int zg_prover_check_batch(zg_prover* p, size_t count, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,
                           zg_failure* failures, size_t cap, uint32_t* totals) {
-    return check_batch_impl(p, count, advice, nullptr, instance, instance_len, failures, cap, totals);
+    ZG_TRY(check_three_kinds(p));
+    return check_batch_impl("zg_prover_check", p, count, advice, nullptr, instance, instance_len, nullptr, 3, failures, cap, totals);
 }
 
 int zg_prover_check_batch_dev(zg_prover* p, size_t count, void* const* d_advice, const zg_fr* const* instance, size_t instance_len,
                               zg_failure* failures, size_t cap, uint32_t* totals) {
-    return check_batch_impl(p, count, nullptr, d_advice, instance, instance_len, failures, cap, totals);
+    ZG_TRY(check_three_kinds(p));
+    return check_batch_impl("zg_prover_check", p, count, nullptr, d_advice, instance, instance_len, nullptr, 3, failures, cap, totals);
+}
+
+int zg_prover_check_circuit(zg_prover* p, size_t count, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,
+                            const zg_fr* challenges, zg_failure* failures, size_t cap, uint32_t* totals) {
+    return check_batch_impl("zg_prover_check_circuit", p, count, advice, nullptr, instance, instance_len, challenges, 4, failures, cap, totals);
+}
+
+int zg_prover_check_circuit_dev(zg_prover* p, size_t count, void* const* d_advice, const zg_fr* const* instance, size_t instance_len,
+                                const zg_fr* challenges, zg_failure* failures, size_t cap, uint32_t* totals) {
+    return check_batch_impl("zg_prover_check_circuit", p, count, nullptr, d_advice, instance, instance_len, challenges, 4, failures, cap,
+                            totals);
 }
 
 int zg_permutation_mapping(uint32_t k, uint32_t n_perm, const zg_fr* sigma_values, uint32_t* next_col, uint32_t* next_row) {

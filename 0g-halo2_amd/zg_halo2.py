@@ -87,6 +87,7 @@ ABI_SYMBOLS = [
     "zg_tuning_set", "zg_tuning_get", "zg_tuning_names", "zg_bases_enable_digit_table", "zg_prover_enable_digit_tables",
     "zg_prover_vk_commitments", "zg_verifier_create", "zg_verifier_destroy", "zg_verifier_verify_batch", "zg_pairing_check",
     "zg_prover_check_batch", "zg_prover_check_batch_dev", "zg_prover_check_images", "zg_permutation_mapping",
+    "zg_prover_check_circuit", "zg_prover_check_circuit_dev",
     "zg_fr_cube_root", "zg_ctx_set_coset_generator", "zg_ctx_coset_generator", "zg_prover_coset_generator",
     "zg_permutation_sigma", "zg_prover_export_key", "zg_params_lagrange", "zg_params_lagrange_dev", "zg_params_check",
     "zg_prover_proof_size_multi", "zg_prover_prove_multi", "zg_prover_prove_multi_dev", "zg_prover_prove_images_multi",
@@ -223,7 +224,7 @@ class KernelStat(ctypes.Structure):
                 ("algo_bytes", ctypes.c_double), ("unit_bytes", ctypes.c_double)]
 
 
-FAIL_GATE, FAIL_LOOKUP, FAIL_COPY = 0, 1, 2
+FAIL_GATE, FAIL_LOOKUP, FAIL_COPY, FAIL_SHUFFLE = 0, 1, 2, 3
 
 
 class Failure(ctypes.Structure):
@@ -1154,10 +1155,10 @@ class Prover:
 
     # ---- witness check (Wnn::mock_proof)
     @staticmethod
-    def _reports(count, cap, recs, totals):
+    def _reports(count, cap, recs, totals, kinds=3):
         out = []
         for b in range(count):
-            t = [int(totals[3 * b + j]) for j in range(3)]
+            t = [int(totals[kinds * b + j]) for j in range(kinds)]
             out.append((t, [recs[b * cap + i].as_tuple() for i in range(min(sum(t), cap))]))
         return out
 
@@ -1191,6 +1192,70 @@ class Prover:
     def check(self, advice: np.ndarray, instance: np.ndarray, cap: int = 64):
         """One witness: (totals, records); see check_batch."""
         return self.check_batch([advice], [instance], cap)[0]
+
+    @property
+    def n_challenges(self) -> int:
+        """The challenges per witness zg_prover_check_circuit expects: zg_prover_phases' count, or (no phases set) the
+        circuit's own, 1 + the largest index a challenge query names."""
+        nch = len(self.phases[2])
+        if nch:
+            return nch
+        c = self.image.c
+        return max([c.queries[i].column + 1 for i in range(c.n_queries) if c.queries[i].kind == 3], default=0)
+
+    def check_circuit(self, advice, instances, challenges=None, cap: int = 64, device: bool = False):
+        """zg_prover_check_circuit(_dev): the witness check for a circuit with shuffles and challenges.  One (totals,
+        records) per witness as check_batch, totals = [gate, lookup, copy, shuffle]; a shuffle record is (3, shuffle, input
+        row, 0, the shuffle row it met).  challenges: uint64[count, n_challenges, 4], the caller's values (Montgomery limbs),
+        None for a circuit without challenges; the witness is whole, synthesised for those values."""
+        count = len(instances)
+        lib = self.ctx.lib
+        keep = []
+        if advice is None:
+            adv_ptrs = None
+        elif device:
+            adv_ptrs = (c_void_p * count)(*[c_void_p(a) if a else None for a in advice])
+        else:
+            keep = [np.ascontiguousarray(a, dtype=np.uint64) if a is not None else None for a in advice]
+            adv_ptrs = (c_void_p * count)(*[c_void_p(a.ctypes.data) if a is not None else None for a in keep])
+        insts, inst_len = [], 0
+        for b in range(count):
+            i, inst_len = self._inst(instances[b])
+            insts.append(i)
+        inst_ptrs = (c_void_p * count)(*[c_void_p(i.ctypes.data) for i in insts])
+        chal = None
+        if challenges is not None:
+            chal = np.ascontiguousarray(challenges, dtype=np.uint64)
+            if chal.shape != (count, self.n_challenges, 4):
+                raise ValueError(f"challenges of shape {chal.shape} for {count} witnesses of {self.n_challenges} challenges")
+        recs = (Failure * max(1, count * cap))()
+        totals = (c_uint32 * (4 * count))()
+        fn = lib.zg_prover_check_circuit_dev if device else lib.zg_prover_check_circuit
+        _check(fn(self.h, c_size_t(count), adv_ptrs, inst_ptrs, c_size_t(inst_len), _ptr(chal) if chal is not None and chal.size else None,
+                  recs if cap else None, c_size_t(cap), totals))
+        return self._reports(count, cap, recs, totals, 4)
+
+    def check_phased(self, synthesize, instances, challenges, cap: int = 64):
+        """check_circuit with the witness made as prove_phased's is: synthesize(phase, challenges) is called once per phase
+        with the caller's challenges uint64[count, n_challenges, 4] and returns, per witness, {advice column: uint64[rows, 4]}
+        of the columns of that phase; their usable rows are copied into the slots, which are then checked as they stand
+        (the other rows keep what the slots held: they take no part in a shuffle, and a rotation may read them)."""
+        count = len(instances)
+        n, hip = self.n, _hip_runtime()
+        usable = n - (self.image.c.blinding_factors + 1)
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(count, self.n_challenges, 4)
+        for phase in range(self.phases[0]):
+            cols = synthesize(phase, ch.copy())
+            for b in range(count):
+                for col, values in cols[b].items():
+                    if not 0 <= int(col) < self.n_advice:
+                        raise ValueError(f"advice column {col} of {self.n_advice}")
+                    v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)[:usable]
+                    if v.shape[0] != usable:
+                        raise ValueError(f"advice column {col}: {v.shape[0]} rows, {usable} usable")
+                    if hip.hipMemcpy(c_void_p(self.advice_slot(b) + int(col) * n * 32), c_void_p(v.ctypes.data), c_size_t(v.nbytes), 1) != 0:
+                        raise ZgError(-2, "hipMemcpy into the advice slot failed")
+        return self.check_circuit(None, instances, ch if ch.size else None, cap)
 
     def check_images(self, plan: "WitnessPlan", images: np.ndarray, cap: int = 64):
         """Wnn::mock_proof for a batch: image bytes -> (reports as check_batch, outputs uint64[count, n_instance, 4])."""

@@ -529,8 +529,9 @@ int zg_prover_create_shared(zg_ctx *ctx, const zg_circuit *circuit, const zg_fr 
  * feature).  ZG_ERR_INVALID_ARG: a null array with a count, a width of 0 or above ZG_MAX_LOOKUP_WIDTH, a polynomial outside
  * the monomials, a cs_degree below the shuffles'; ZG_ERR_UNSUPPORTED: more than ZG_MAX_SHUFFLES.
  * A prover with shuffles makes single proofs and lock-step batches (zg_prover_prove, _dev, _batch, _batch_dev, _phased);
- * zg_prover_prove_multi* of several circuits, zg_prover_prove_images*, zg_prover_check_*, a point-range shard and the
- * arithmetic-level entries that take the whole circuit (zg_prover_evaluate_h*) answer ZG_ERR_UNSUPPORTED. */
+ * zg_prover_prove_multi* of several circuits, zg_prover_prove_images*, zg_prover_check_batch, _batch_dev and _images (a
+ * witness of such a circuit is checked by zg_prover_check_circuit*), a point-range shard and the arithmetic-level entries
+ * that take the whole circuit (zg_prover_evaluate_h*) answer ZG_ERR_UNSUPPORTED. */
 int zg_prover_create_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
                               const zg_fr *fixed_values, const zg_fr *sigma_values, const zg_g1_affine *g,
                               const zg_g1_affine *g_lagrange, const zg_fr *vk_repr, zg_prover **out);
@@ -637,8 +638,10 @@ int zg_prover_prove_dev(zg_prover *p, void *d_advice, const zg_fr *instance, siz
  *
  * On a circuit with a challenge or a phase > 0: zg_prover_prove, _dev, _batch, _batch_dev work while every advice column
  * is in phase 0 (the witness cannot depend on a challenge then) and return ZG_ERR_INVALID_ARG otherwise (use
- * zg_prover_prove_phased); zg_prover_prove_multi*, zg_prover_prove_images*, zg_prover_check_*, zg_verifier_verify_multi
- * with more than one circuit and a point-range shard are ZG_ERR_UNSUPPORTED; the ZG_LAT_GATE gate stays off. */
+ * zg_prover_prove_phased); zg_prover_prove_multi*, zg_prover_prove_images*, zg_prover_check_batch, _batch_dev and _images
+ * (a witness of such a circuit is checked by zg_prover_check_circuit*, with the caller's challenge values),
+ * zg_verifier_verify_multi with more than one circuit and a point-range shard are ZG_ERR_UNSUPPORTED; the ZG_LAT_GATE
+ * gate stays off. */
 int zg_prover_set_phases(zg_prover *p, const uint8_t *advice_phase, uint32_t n_challenges, const uint8_t *challenge_phase);
 int zg_prover_phases(const zg_prover *p, uint8_t *advice_phase, uint32_t *n_challenges, uint8_t *challenge_phase);
 /* create_proof's phase loop for a batch of `count` proofs whose witness is synthesised phase by phase.  The library
@@ -934,13 +937,13 @@ int zg_prover_prove_images_multi(zg_prover* p, zg_witness_plan* plan, const uint
  * MockProver's CellNotAssigned / ConstraintPoisoned diagnostics have no counterpart: the ABI carries values, not regions.
  * Per witness the check reports the exact number of failures of each kind and the first min(total, cap) failures in
  * ascending (kind, index, row) order. */
-enum { ZG_FAIL_GATE = 0, ZG_FAIL_LOOKUP = 1, ZG_FAIL_COPY = 2 };
+enum { ZG_FAIL_GATE = 0, ZG_FAIL_LOOKUP = 1, ZG_FAIL_COPY = 2, ZG_FAIL_SHUFFLE = 3 /* zg_prover_check_circuit* only */ };
 typedef struct {
     uint32_t kind;        /* ZG_FAIL_*                                                         */
-    uint32_t index;       /* gate / lookup / permutation-column index                          */
+    uint32_t index;       /* gate / lookup / permutation-column / shuffle index                */
     uint32_t row;
     uint32_t other_index; /* ZG_FAIL_COPY: permutation column of next(c, r); else 0            */
-    uint32_t other_row;   /* ZG_FAIL_COPY: its row; else 0                                     */
+    uint32_t other_row;   /* ZG_FAIL_COPY: its row; ZG_FAIL_SHUFFLE: the shuffle row met; else 0 */
 } zg_failure;
 
 /* count <= max_batch witnesses.  advice[b]: host [n_advice][2^k] (copied into slot b), or NULL = slot b as it stands;
@@ -961,6 +964,34 @@ int zg_prover_check_batch_dev(zg_prover *p, size_t count, void *const *d_advice,
  * the plan's conditions as zg_prover_prove_images. */
 int zg_prover_check_images(zg_prover *p, zg_witness_plan *plan, const uint8_t *images, size_t count, zg_fr *outputs,
                            zg_failure *failures, size_t cap, uint32_t *totals);
+/* The witness check for a circuit with shuffles (zg_prover_create_shuffles) and challenges (ZG_CHALLENGE queries): what
+ * zg_prover_check_batch* refuse.  Gates, lookups and copies as above, except that a ZG_CHALLENGE query evaluates to the
+ * challenge value the caller passed for that witness.  A fourth kind, ZG_FAIL_SHUFFLE, modelled on MockProver::verify's
+ * shuffle check (privacy-scaling-explorations/halo2 from v0.3.0 on, dev.rs): written from the published source, NOT
+ * checked against it here (no upstream build is at hand).  For shuffle j of width m, in[r] the tuple of its m input
+ * expressions at row r, sh[r] that of its m shuffle expressions, both for r < usable and as canonical integers (not
+ * Montgomery limbs): the input rows are sorted ascending by (in[r], r), the shuffle rows by (sh[r], r) -- tuples compare
+ * lexicographically, component 0 first; the row index is the last key, so both orders are total.  For each position
+ * i < usable, with a the input row at i and b the shuffle row at i, input row a FAILS iff in[a] != sh[b]; the record is
+ * {ZG_FAIL_SHUFFLE, j, a, 0, b}.  Rows >= usable take no part, whatever they hold; a query with rotation t reads row
+ * (r + t) mod n of the column as it stands.  The comparison is exact (no theta, no gamma, no probability): a witness has
+ * no shuffle failure iff the two multisets are equal, iff the argument's product closes for every gamma.  ONE spoiled cell
+ * may report many rows, because the sorted sequences shift (MockProver's behaviour, kept); the totals are exact counts.
+ * Reports stay in ascending (kind, index, row) order, shuffles last; a capped report is the head of the full one.
+ *
+ * totals: [count][4] by kind.  challenges: [count][n_challenges], Montgomery form, n_challenges as zg_prover_phases
+ * reports it (the circuit's own count, 1 + the largest index a ZG_CHALLENGE query names, while zg_prover_set_phases was
+ * never called).  The values are the CALLER's and any values are accepted: the library does not derive MockProver's own
+ * challenge values (that derivation cannot be checked against upstream here).  NULL only when the circuit has no
+ * challenge, ZG_ERR_INVALID_ARG otherwise.  The witness is WHOLE: the columns of every phase are in the slot or in
+ * advice[b], synthesised by the caller for those challenge values; the check runs no callback.  Everything else --
+ * advice, instance, failures, cap, the slots only read, blocking, the status of the call, a point-range shard -- as
+ * zg_prover_check_batch / _dev.  On a circuit without shuffles and challenges the report is zg_prover_check_batch's with
+ * a fourth total of 0, from the same launches. */
+int zg_prover_check_circuit(zg_prover *p, size_t count, const zg_fr *const *advice, const zg_fr *const *instance,
+                            size_t instance_len, const zg_fr *challenges, zg_failure *failures, size_t cap, uint32_t *totals);
+int zg_prover_check_circuit_dev(zg_prover *p, size_t count, void *const *d_advice, const zg_fr *const *instance,
+                                size_t instance_len, const zg_fr *challenges, zg_failure *failures, size_t cap, uint32_t *totals);
 /* Host helper (no device): next_col / next_row [n_perm][2^k] such that sigma_values[c][r] = delta^next_col *
  * omega^next_row -- Assembly::mapping back from what halo2's ProvingKey holds (pk.permutation.permutations).
  * ZG_ERR_INVALID_ARG when a value is no such product. */
