@@ -23,35 +23,10 @@ import numpy as np
 
 import poly_ref as pr
 from circuit import ADVICE, DELTA, FIXED, INSTANCE, R, omega_for
+from transcript_ref import EvmWriter
 
 # blinding tags of oracle/prover.h (rand_fr(key, tag, index))
 TAG_ADVICE_BLIND, TAG_PERMUTED_INPUT, TAG_PERMUTED_TABLE, TAG_PERM_Z, TAG_LOOKUP_Z, TAG_RANDOM_POLY = 1, 2, 3, 4, 5, 6
-
-
-class Transcript:
-    """snark-verifier's EvmTranscript, writer side (oracle/prover.c tr_*)."""
-
-    def __init__(self, keccak):
-        self.keccak, self.buf, self.out = keccak, b"", bytearray()
-
-    def common_scalar(self, v: int):
-        self.buf += v.to_bytes(32, "big")
-
-    def write_scalar(self, v: int):
-        self.common_scalar(v)
-        self.out += v.to_bytes(32, "big")
-
-    def write_point(self, pt):
-        x, y = pt
-        assert (x, y) != (0, 0), "EvmTranscript cannot absorb the identity"
-        b = x.to_bytes(32, "big") + y.to_bytes(32, "big")
-        self.buf += b
-        self.out += b
-
-    def squeeze(self) -> int:
-        h = self.keccak(self.buf + (b"\x01" if len(self.buf) == 32 else b""))
-        self.buf = h
-        return int.from_bytes(h, "big") % R
 
 
 def n_sets(cs) -> int:
@@ -59,18 +34,19 @@ def n_sets(cs) -> int:
     return (len(cs.perm_columns) + chunk - 1) // chunk if cs.perm_columns else 0
 
 
-def create_proof(be, cs, vk_repr, advice, instance) -> bytes:
-    """advice: uint64[A][n][4] as assigned (the blinding rows are overwritten here); instance: uint64[I][len][4]."""
+def create_proof(be, cs, vk_repr, advice, instance, writer=EvmWriter) -> bytes:
+    """advice: uint64[A][n][4] as assigned (the blinding rows are overwritten here); instance: uint64[I][len][4];
+    writer: the transcript's writer class (tests/transcript_ref.py)."""
     k = cs.k
     n, bf = 1 << k, cs.blinding_factors()
     usable = n - (bf + 1)
     A, I, NL, P = cs.n_advice, cs.n_instance, len(cs.lookups), len(cs.perm_columns)
     sets, qpd, w = n_sets(cs), cs.degree() - 1, omega_for(k)
-    tr = Transcript(be.keccak)
+    tr = writer(be.keccak)
 
     # 1. vk and instance scalars
     tr.common_scalar(pr.to_int(vk_repr))
-    instance = np.ascontiguousarray(instance, dtype=np.uint64).reshape(I, -1, 4)
+    instance = np.ascontiguousarray(instance, dtype=np.uint64).reshape(I, -1, 4) if I else np.zeros((0, 0, 4), np.uint64)
     inst_cols = np.zeros((I, n, 4), np.uint64)
     inst_cols[:, :instance.shape[1]] = instance
     for c in range(I):

@@ -228,7 +228,7 @@ SMALL = {"plain": plain, "wide": wide, "three": three, "only": only, "rotated": 
 
 
 def cell_at(pc, advice_ints, challenges=()):
-    """the witness as shuffle_ref.shuffle_product reads it: advice_ints[column][row] canonical integers (fixed from the key)"""
+    """the witness as proof_ref.shuffle_product reads it: advice_ints[column][row] canonical integers (fixed from the key)"""
     cs, n = pc.cs, pc.n
 
     def at(row):

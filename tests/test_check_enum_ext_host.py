@@ -1,6 +1,6 @@
 """tests/check_enum_ext.failures4, the comparator of the zg_prover_check_circuit tests, held to the references the suite
 already has: check_enum.failures for gates, lookups and copies (the challenges substituted first) and
-shuffle_ref.shuffle_product for the shuffles; and the conditions the GPU test's capped cases rest on.  No device."""
+proof_ref.shuffle_product for the shuffles; and the conditions the GPU test's capped cases rest on.  No device."""
 import copy
 import random
 import types
@@ -10,8 +10,8 @@ import pytest
 import check_circuit_cases as cases
 import check_enum
 import phases_circuits
+import proof_ref
 import shuffle_circuits
-import shuffle_ref
 from check_enum_ext import CHALLENGE, SHUFFLE, columns_of, failures4, instance_of, report
 from circuit import R, Expr
 from shuffle_circuits import BAD
@@ -74,7 +74,7 @@ def test_shuffle_failures_iff_the_product_does_not_close(name):
         at = shuffle_circuits.cell_at(pc, adv, ch)
         for j in range(len(pc.cs.shuffles)):
             clean = not any(r[0] == SHUFFLE and r[1] == j for r in recs)
-            closes = [shuffle_ref.shuffle_product(pc.cs, j, at, rng.randrange(R), rng.randrange(R))[pc.usable] == 1 for _ in range(2)]
+            closes = [proof_ref.shuffle_product(pc.cs, j, at, rng.randrange(R), rng.randrange(R))[pc.usable] == 1 for _ in range(2)]
             assert closes == [clean, clean], (variant, j)
 
 

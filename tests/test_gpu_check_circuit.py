@@ -1,6 +1,6 @@
 """zg_prover_check_circuit / _dev on the device: the witness check for circuits with shuffles and
 challenges.  Every report -- totals and records -- is compared element for element with tests/check_enum_ext.failures4,
-the Python-integer enumeration (held to check_enum and shuffle_ref by tests/test_check_enum_ext_host.py).  Circuits:
+the Python-integer enumeration (held to check_enum and proof_ref by tests/test_check_enum_ext_host.py).  Circuits:
 tests/shuffle_circuits.py and tests/phases_circuits.py; witnesses: tests/check_circuit_cases.py.
 
 Tolerances: none -- everything here is exact arithmetic mod r, counts, row numbers or bytes."""

@@ -1,5 +1,5 @@
 """One proof of several circuit instances (zg_prover_prove_multi: create_proof's `circuits` slice) and its verification on
-the device (zg_verifier_verify_multi).  The judge of every multi-circuit proof is tests/multi_ref.py, a Python-integer
+the device (zg_verifier_verify_multi).  The judge of every multi-circuit proof is tests/proof_ref.py, a Python-integer
 verify_proof for N circuits that shares nothing with the library; at N = 1 the bytes are the oracle's.
 
 All witnesses of one proof belong to ONE key: the families below are built from seeds whose copy constraints do not
@@ -9,13 +9,13 @@ import random
 import numpy as np
 import pytest
 
-import multi_ref
+import proof_ref
 from circuit import ADVICE
 from circuits import toy_circuit, variant_circuit
 
 pytestmark = pytest.mark.gpu
 
-R = multi_ref.R
+R = proof_ref.R
 
 
 def cls(v):
@@ -64,7 +64,7 @@ class Setup:
         fc, sc = self.prover.vk_commitments()
         self.verifier = zg.Verifier(ctx, self.img, fc, sc, self.params.g_np()[0], np.array(self.params.g2, np.uint64),
                                     np.array(self.params.s_g2, np.uint64), self.vk_repr)
-        self.ref = multi_ref.Vk(cs, self.params, fixed, sigma, self.vk_repr)
+        self.ref = proof_ref.Vk(cs, self.params, fixed, sigma, self.vk_repr)
         self.adv = [a.advice_values() for _, a, _ in family]
         self.inst = [a.instance_values(ilen) for _, a, _ in family]
         self.prover.set_batch(max(len(family), 1))
@@ -81,7 +81,7 @@ class Setup:
     def verdicts(self, proof, insts, circuits=None, key=3):
         """(device verdict, reference verdict) of one multi proof"""
         circuits = len(insts) if circuits is None else circuits
-        return self.verifier.verify_multi([proof], [insts], key, circuits)[0], multi_ref.verify(self.ref, insts, proof)
+        return self.verifier.verify_multi([proof], [insts], key, circuits)[0], proof_ref.verify(self.ref, insts, proof).verdict
 
     def close(self):
         self.verifier.close()
@@ -103,8 +103,8 @@ def test_n_circuits_verify(ctx, zg, orc, N):
     s = Setup(orc, zg, ctx, toy_family(N))
     assert len({i.tobytes() for i in s.inst}) == N  # different instances (and witnesses)
     proof = s.both_forms(list(range(N)), [11 + c for c in range(N)])
-    assert len(proof) == multi_ref.proof_len(s.cs, N)
-    assert multi_ref.verify(s.ref, s.inst, proof) == 1
+    assert len(proof) == proof_ref.proof_len(s.cs, N=N)
+    assert proof_ref.verify(s.ref, s.inst, proof).verdict == 1
     assert s.verifier.verify_multi([proof], [s.inst], 9, N) == [1]
     s.close()
 
@@ -114,7 +114,7 @@ CHUNK = 128  # combine_pairs_kernel takes a point set's list in chunks of HC9_MA
 
 def short_first_chunk_N(cs) -> tuple:
     """(N, length): the N in 1..64 whose longest point-set list is nearest above a multiple of 128 (the smallest such N)"""
-    longest = {N: max(multi_ref.point_set_lengths(cs, N).values()) for N in range(1, 65)}
+    longest = {N: max(proof_ref.point_set_lengths(cs, N).values()) for N in range(1, 65)}
     N = min((L % CHUNK, N) for N, L in longest.items() if L > CHUNK and L % CHUNK)[1]
     return N, longest[N]
 
@@ -128,9 +128,9 @@ def test_lazy_sum_kernels_at_their_edges(ctx, zg, orc, N):
     gives 522 = 10 + 4 * 128."""
     s = Setup(orc, zg, ctx, toy_family(N))
     assert short_first_chunk_N(s.cs) == (15, 130)
-    assert max(multi_ref.point_set_lengths(s.cs, N).values()) == 8 * N + 10
+    assert max(proof_ref.point_set_lengths(s.cs, N).values()) == 8 * N + 10
     proof = s.both_forms(list(range(N)), [71 + c for c in range(N)])
-    assert len(proof) == multi_ref.proof_len(s.cs, N)
+    assert len(proof) == proof_ref.proof_len(s.cs, N=N)
     assert s.verdicts(proof, s.inst) == (1, 1)
     if N > 4:  # the last circuit's quotient is in the sum: its instance exchanged with another's is rejected by both
         assert s.inst[N - 1].tobytes() != s.inst[0].tobytes()
@@ -159,7 +159,7 @@ def test_structure_of_a_three_circuit_proof(ctx, zg, orc):
     s = Setup(orc, zg, ctx, toy_family(3))
     seeds = [21, 22, 23]
     proof = s.both_forms([0, 1, 2], seeds)
-    A, NL, S = s.cs.n_advice, len(s.cs.lookups), multi_ref.n_sets(s.cs)
+    A, NL, S = s.cs.n_advice, len(s.cs.lookups), proof_ref.n_sets(s.cs)
     singles = [s.prover.prove(s.adv[c], s.inst[c], seeds[c]) for c in range(3)]
     for c in range(3):
         assert proof[64 * A * c:64 * A * (c + 1)] == singles[c][:64 * A], c
@@ -182,9 +182,9 @@ SHAPES = {
 def test_circuit_shapes(ctx, zg, orc, shape):
     s = Setup(orc, zg, ctx, SHAPES[shape]())
     if shape.startswith("toy"):
-        assert multi_ref.n_sets(s.cs) > 1
+        assert proof_ref.n_sets(s.cs) > 1
     proof = s.both_forms([0, 1, 2], [31, 32, 33])
-    assert len(proof) == multi_ref.proof_len(s.cs, 3)
+    assert len(proof) == proof_ref.proof_len(s.cs, N=3)
     assert s.verdicts(proof, s.inst) == (1, 1)
     s.close()
 
@@ -202,7 +202,7 @@ def test_rejections(ctx, zg, orc):
     s.prover.set_overlap(True)
     unsat_proof = s.prover.prove_multi([s.adv[0], s.adv[1], unsat], s.inst, seeds)
     cs = s.cs
-    A, NL, S = cs.n_advice, len(cs.lookups), multi_ref.n_sets(cs)
+    A, NL, S = cs.n_advice, len(cs.lookups), proof_ref.n_sets(cs)
     AQ = len(cs.advice_queries)
     s0 = 64 * (3 * (A + 3 * NL + S) + 1 + cs.degree() - 1) + 32 * (2 * AQ)  # the last circuit's first advice evaluation
     sc0 = int.from_bytes(good[s0:s0 + 32], "big")
@@ -246,7 +246,7 @@ def test_lookup_failure_in_one_circuit_fails_the_proof(ctx, zg, orc):
 
 def test_arguments(ctx, zg, orc):
     s = Setup(orc, zg, ctx, toy_family(2))
-    assert s.prover.proof_size_multi(2) >= multi_ref.proof_len(s.cs, 2) and s.prover.proof_size_multi(1) == s.prover.proof_cap
+    assert s.prover.proof_size_multi(2) >= proof_ref.proof_len(s.cs, N=2) and s.prover.proof_size_multi(1) == s.prover.proof_cap
     for count in (0, 3):  # max_batch = 2
         with pytest.raises(zg.ZgError) as e:
             s.prover.prove_multi([s.adv[0]] * count, [s.inst[0]] * count, list(range(count)))
@@ -279,7 +279,7 @@ def test_tiny_model_three_images(tiny, zg):
     s = tiny
     images = [s.real, np.zeros_like(s.real), np.full_like(s.real, 255)]
     proof, outputs = s.prover.prove_images_multi(s.plan, np.stack(images), [61, 62, 63])
-    assert len(proof) == multi_ref.proof_len(s.cs, 3)
+    assert len(proof) == proof_ref.proof_len(s.cs, N=3)
     for c, im in enumerate(images):
         assert [zg.fr_to_int(x) for x in outputs[c]] == s.wnn.predict(im), c
     insts = [outputs[c][None, :, :] for c in range(3)]
@@ -297,7 +297,7 @@ def test_tiny_model_thirty_two_images(tiny, zg):
     rng = np.random.default_rng(32)
     images = [s.real] + [rng.integers(0, 256, size=s.real.shape, dtype=s.real.dtype) for _ in range(31)]
     proof, outputs = s.prover.prove_images_multi(s.plan, np.stack(images), list(range(100, 132)))
-    assert len(proof) == multi_ref.proof_len(s.cs, 32)
+    assert len(proof) == proof_ref.proof_len(s.cs, N=32)
     insts = [outputs[c][None, :, :] for c in range(32)]
     assert s.verifier.verify_multi([proof], [insts], 17, 32) == [1]
     insts[31], insts[30] = insts[30], insts[31]

@@ -1,6 +1,7 @@
 """Advice phases and challenges on the device: zg_prover_set_phases / zg_prover_prove_phased / zg_verifier_set_phases and
-the ZG_CHALLENGE query kind.  The oracle knows no challenges, so the judge is tests/phases_ref.py,
-the Python-integer verify_proof with phases (pinned to the oracle on one-phase circuits by tests/test_phases_host.py),
+the ZG_CHALLENGE query kind.  The oracle knows no challenges, so the judge is tests/proof_ref.py,
+the Python-integer verify_proof (pinned to the oracle on one-phase circuits by tests/test_phases_host.py and to recorded
+proofs with phases by tests/test_proof_golden_host.py),
 next to the library's own batch verifier.  Circuits: tests/phases_circuits.py, k = 5 except the one k = 14 case."""
 import ctypes
 
@@ -9,7 +10,7 @@ import pytest
 import torch  # noqa: F401 -- before the first HIP call of the process (tests/conftest.py)
 
 import phases_circuits
-import phases_ref
+import proof_ref
 from circuit import R
 from circuits import toy_circuit
 
@@ -35,7 +36,7 @@ class Setup:
         if set_phases:
             self.prover.set_phases(pc.advice_phase, pc.challenge_phase)
             self.verifier.set_phases(pc.advice_phase, pc.challenge_phase)
-        self.vk = phases_ref.Vk(pc.cs, self.params, fixed, sigma, self.vk_repr)
+        self.vk = proof_ref.Vk(pc.cs, self.params, fixed, sigma, self.vk_repr)
 
     def prove(self, variants, seeds, seen=None, prover=None):
         p = prover or self.prover
@@ -45,7 +46,8 @@ class Setup:
 
     def ref(self, proof, variant=0, instance=None, scheme=GWC, transcript=EVM):
         inst = self.pc.instance(variant) if instance is None else instance
-        return phases_ref.verify(self.vk, [inst], proof, self.pc.advice_phase, self.pc.challenge_phase, scheme, transcript)
+        return proof_ref.verify(self.vk, [inst], proof, advice_phase=self.pc.advice_phase, challenge_phase=self.pc.challenge_phase,
+                                scheme=scheme, transcript=transcript)
 
     def dev(self, proofs, variants=None, instances=None):
         insts = instances if instances is not None else [self.pc.instance(v) for v in (variants or [0] * len(proofs))]
@@ -57,7 +59,7 @@ class Setup:
 
 
 def scalar_offset(cs):
-    S = phases_ref.n_sets(cs)
+    S = proof_ref.n_sets(cs)
     return 64 * (cs.n_advice + 3 * len(cs.lookups) + S + 1 + cs.degree() - 1)
 
 
@@ -74,7 +76,7 @@ def test_proofs_are_accepted_and_tampered_ones_rejected(ctx, zg, orc, name):
     s = Setup(orc, zg, ctx, pc)
     assert s.prover.phases == (pc.n_phases, pc.advice_phase, pc.challenge_phase) == s.verifier.phases
     (proof,) = s.prove([0], [7])
-    assert len(proof) == phases_ref.proof_len(pc.cs) <= s.prover.proof_cap
+    assert len(proof) == proof_ref.proof_len(pc.cs) <= s.prover.proof_cap
     r = s.ref(proof)
     assert r.verdict == 1 and sorted(r.challenges) == list(range(len(pc.challenge_phase)))
     assert s.dev([proof]) == [1]
@@ -104,7 +106,7 @@ def test_a_verifier_without_the_phases_rejects(ctx, zg, orc, name):
                         s.vk_repr)
     assert plain.phases == (1, [0] * pc.cs.n_advice, [0] * len(pc.challenge_phase))
     assert plain.verify([proof], [pc.instance(0)], 1)[0] <= 0
-    assert phases_ref.verify(s.vk, [pc.instance(0)], proof, None, [0] * len(pc.challenge_phase)).verdict <= 0
+    assert proof_ref.verify(s.vk, [pc.instance(0)], proof, advice_phase=None, challenge_phase=[0] * len(pc.challenge_phase)).verdict <= 0
     plain.close()
     s.close()
 
@@ -155,12 +157,12 @@ def test_each_commitment_is_its_column_at_its_phases_place(ctx, zg, orc, name):
     s = Setup(orc, zg, ctx, pc)
     (proof,) = s.prove([1], [21])
     r = s.ref(proof, 1)
-    assert r.verdict == 1 and r.order == phases_ref.advice_order(pc.cs, 1, pc.advice_phase)
+    assert r.verdict == 1 and r.order == proof_ref.advice_order(pc.cs, 1, pc.advice_phase)
     cols = read_slot(s.prover)  # as committed: the blinding rows included
     gl = s.params.g_lagrange_np()
     for (ph, _, col) in r.order:
         want = orc.msm(np.ascontiguousarray(cols[col]), gl, threads=16)
-        assert np.array_equal(phases_ref.affine(r.advice[ph, 0, col]), phases_ref.affine(want)), (ph, col)
+        assert np.array_equal(proof_ref.affine(r.advice[ph, 0, col]), proof_ref.affine(want)), (ph, col)
     assert cols[:, pc.usable:].any()  # (the blinding rows are drawn)
     # the usable rows are the callback's witness for the challenges the proof replays
     ch = [r.challenges[j] for j in range(len(pc.challenge_phase))]
@@ -181,7 +183,7 @@ def test_every_multiopen_and_transcript(ctx, zg, orc, name, scheme, transcript):
         obj.set_multiopen(scheme)
         obj.set_transcript(transcript)
     (proof,) = s.prove([0], [5])
-    assert len(proof) == phases_ref.proof_len(pc.cs, scheme, transcript) <= s.prover.proof_cap
+    assert len(proof) == proof_ref.proof_len(pc.cs, scheme=scheme, transcript=transcript) <= s.prover.proof_cap
     assert s.ref(proof, scheme=scheme, transcript=transcript).verdict == 1
     assert s.dev([proof]) == [1]
     bad = flip(proof, len(proof) - 40)

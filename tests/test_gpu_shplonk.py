@@ -1,5 +1,5 @@
 """The SHPLONK multi-open on the device (zg_prover_set_multiopen / zg_verifier_set_multiopen).
-Bytes are held against the reference prover of tests/shplonk_ref.py (upstream's order, chained divisions, over the host
+Bytes are held against the reference prover of tests/proof_ref.py (upstream's order, chained divisions, over the host
 backend of tests/arith_level.py) wherever it runs, verdicts against its verifier; tests/test_shplonk_host.py holds the
 reference against itself and the oracle on a machine without a GPU."""
 import json
@@ -8,16 +8,15 @@ import numpy as np
 import pytest
 
 import arith_level
-import multi_ref
 import poly_ref as pr
-import shplonk_ref
+import proof_ref
 from circuits import toy_circuit, variant_circuit
 from test_gpu_multi import toy_family
-from test_shplonk_host import GOLDEN_N2, seventeen_points_circuit, seventeen_sets_circuit
+from test_shplonk_host import GOLDEN_N2, seventeen_points_circuit, seventeen_sets_circuit, shplonk
 
 pytestmark = pytest.mark.gpu
 
-R, Q = multi_ref.R, multi_ref.Q
+R, Q = proof_ref.R, proof_ref.Q
 GWC, SHPLONK = 0, 1
 
 CIRCUITS = {
@@ -50,7 +49,7 @@ class Setup:
         fc, sc = self.prover.vk_commitments()
         self.verifier = zg.Verifier(ctx, self.img, fc, sc, self.params.g_np()[0], np.array(self.params.g2, np.uint64),
                                     np.array(self.params.s_g2, np.uint64), self.vk_repr)
-        self.ref = multi_ref.Vk(cs, self.params, self.fixed, self.sigma, self.vk_repr)
+        self.ref = proof_ref.Vk(cs, self.params, self.fixed, self.sigma, self.vk_repr)
         self.adv = [a.advice_values() for _, a, _ in family]
         self.inst = [a.instance_values(ilen) for _, a, _ in family]
         self.prover.set_batch(len(family))
@@ -71,7 +70,7 @@ class Setup:
         challenges = [pr.to_int(tr.fe(name)) for name in ("theta", "beta", "gamma", "y")]
         orc.trace_free(tr)
         be = arith_level.HostBackend(orc, self.cs, self.fixed, self.sigma, self.params, seed, h_ext, challenges)
-        return shplonk_ref.create_proof(be, self.ref, self.adv[i], self.inst[i])
+        return proof_ref.create_proof(be, self.ref, self.adv[i], self.inst[i], scheme=SHPLONK)
 
     def both_forms(self, make):
         self.prover.set_overlap(True)
@@ -91,8 +90,8 @@ def test_bytes_are_the_reference_provers_in_both_forms(ctx, zg, orc, name):
     s = Setup(orc, zg, ctx, [CIRCUITS[name]()])
     got = s.both_forms(lambda: s.prover.prove(s.adv[0], s.inst[0], 11))
     assert got == s.reference(0, 11)
-    assert len(got) == shplonk_ref.proof_len(s.cs, 1) <= s.prover.proof_cap
-    assert shplonk_ref.verify(s.ref, [s.inst[0]], got) == 1
+    assert len(got) == proof_ref.proof_len(s.cs, N=1, scheme=SHPLONK) <= s.prover.proof_cap
+    assert shplonk(s.ref, [s.inst[0]], got) == 1
     assert s.verifier.verify([got], [s.inst[0]], 5) == [1]
     s.close()
 
@@ -125,16 +124,16 @@ def test_prove_multi(ctx, zg, orc):
     two = s.both_forms(lambda: s.prover.prove_multi(s.adv, s.inst, [31, 32]))
     rec = json.load(open(GOLDEN_N2))  # the proof the host test judges: these bytes
     assert (rec["params_seed"], rec["vk_repr"], rec["seeds"]) == (0xABCDEF, 0x1234567, [31, 32]) and two.hex() == rec["proof"]
-    assert len(two) == shplonk_ref.proof_len(s.cs, 2) <= s.prover.proof_size_multi(2)
+    assert len(two) == proof_ref.proof_len(s.cs, N=2, scheme=SHPLONK) <= s.prover.proof_size_multi(2)
     # the prefix is the GWC proof's of the same circuits and keys
     s.prover.set_multiopen(GWC)
     gwc = s.prover.prove_multi(s.adv, s.inst, [31, 32])
     s.prover.set_multiopen(SHPLONK)
-    assert two[:-128] == gwc[:len(gwc) - 64 * multi_ref.n_point_sets(s.cs)]
-    assert shplonk_ref.verify(s.ref, s.inst, two, circuits=2) == 1
+    assert two[:-128] == gwc[:len(gwc) - 64 * proof_ref.n_point_sets(s.cs)]
+    assert shplonk(s.ref, s.inst, two) == 1
     assert s.verifier.verify_multi([two], [s.inst], 9, 2) == [1]
     swapped = [s.inst[1], s.inst[0]]
-    assert shplonk_ref.verify(s.ref, swapped, two, circuits=2) == 0
+    assert shplonk(s.ref, swapped, two) == 0
     assert s.verifier.verify_multi([two], [swapped], 9, 2) == [0]
     s.close()
 
@@ -171,7 +170,7 @@ def test_caller_side_walk_over_the_device_entries(ctx, zg, orc):
     g, gl = ctx.register_bases(s.params.g_np()), ctx.register_bases(s.params.g_lagrange_np())
     try:
         be = arith_level.DeviceBackend(zg, ctx, s.prover, s.cs, s.fixed, s.sigma, g, gl, 13)
-        walked = shplonk_ref.create_proof(be, s.ref, s.adv[0], s.inst[0])
+        walked = proof_ref.create_proof(be, s.ref, s.adv[0], s.inst[0], scheme=SHPLONK)
         ctx.sync()
     finally:
         g.free()
@@ -190,16 +189,16 @@ def test_tiny_model_k14(ctx, zg, orc):
     s = Setup(orc, zg, ctx, [(cs, asg, ilen)], seed=0x5EED, vk=0xC0FFEE)
     proof = s.prover.prove(s.adv[0], s.inst[0], 7)
     gwc = s.oracle_gwc(0, 7)
-    assert len(gwc) == 3840 and len(proof) == 3712 == shplonk_ref.proof_len(cs, 1)
-    assert proof[:-128] == gwc[:len(gwc) - 64 * multi_ref.n_point_sets(cs)]
-    assert shplonk_ref.verify(s.ref, [s.inst[0]], proof) == 1
+    assert len(gwc) == 3840 and len(proof) == 3712 == proof_ref.proof_len(cs, N=1, scheme=SHPLONK)
+    assert proof[:-128] == gwc[:len(gwc) - 64 * proof_ref.n_point_sets(cs)]
+    assert shplonk(s.ref, [s.inst[0]], proof) == 1
     assert s.verifier.verify([proof], [s.inst[0]], 3) == [1]
     s.close()
 
 
 def tampered(s, good):
     c = s.img.c
-    s0 = 64 * (c.n_advice + 3 * c.n_lookups + multi_ref.n_sets(s.cs) + 1 + c.cs_degree - 1)  # the first evaluation
+    s0 = 64 * (c.n_advice + 3 * c.n_lookups + proof_ref.n_sets(s.cs) + 1 + c.cs_degree - 1)  # the first evaluation
     sc0 = int.from_bytes(good[s0:s0 + 32], "big")
     g0 = s.params.g_np()[0]
     g0b = be32(s.orc.fq_to_int(g0[0:4])) + be32(s.orc.fq_to_int(g0[4:8]))
@@ -224,7 +223,7 @@ def test_verdict_classes_and_the_other_schemes_proofs(ctx, zg, orc):
     s = Setup(orc, zg, ctx, [toy_circuit(k=5)])
     good = s.prover.prove(s.adv[0], s.inst[0], 1)
     for name, (proof, want) in tampered(s, good).items():
-        ref = shplonk_ref.verify(s.ref, [s.inst[0]], proof)
+        ref = shplonk(s.ref, [s.inst[0]], proof)
         got = s.verifier.verify([proof], [s.inst[0]], 5)[0]
         assert cls(got) == ref == want, name
     gwc = s.oracle_gwc(0, 1)
@@ -244,7 +243,7 @@ def test_batch_of_eight_with_one_bad_proof(ctx, zg, orc):
     proofs[5] = bytes(bad)
     lone = [s.verifier.verify([p], [s.inst[0]], 8)[0] for p in proofs]
     assert s.verifier.verify(proofs, [s.inst[0]] * 8, 8) == lone
-    assert [cls(v) for v in lone] == [shplonk_ref.verify(s.ref, [s.inst[0]], p) for p in proofs]
+    assert [cls(v) for v in lone] == [shplonk(s.ref, [s.inst[0]], p) for p in proofs]
     assert lone[:5] == [1] * 5 and lone[6:] == [1, 1] and lone[5] != 1
     s.close()
 

@@ -1,6 +1,7 @@
 """halo2's shuffle argument on the device: zg_prover_create_shuffles / zg_verifier_create_shuffles.
-The oracle knows no shuffles, so the judge is tests/shuffle_ref.py, the Python-integer verify_proof with shuffles (pinned
-to the oracle and to phases_ref on circuits without shuffles by tests/test_shuffle_host.py), next to the library's own
+The oracle knows no shuffles, so the judge is tests/proof_ref.py, the Python-integer verify_proof (pinned to the oracle on
+circuits without shuffles by tests/test_shuffle_host.py and to recorded proofs with shuffles by
+tests/test_proof_golden_host.py), next to the library's own
 batch verifier.  Circuits: tests/shuffle_circuits.py, k = 5 except where said.
 
 Tolerances: none -- everything here is exact arithmetic mod r or bytes."""
@@ -10,8 +11,8 @@ import numpy as np
 import pytest
 import torch  # noqa: F401 -- before the first HIP call of the process (tests/conftest.py)
 
+import proof_ref
 import shuffle_circuits
-import shuffle_ref
 from circuit import R, omega_for
 from circuits import toy_circuit
 from shuffle_circuits import BAD
@@ -40,7 +41,7 @@ class Setup:
         if self.phased:
             self.prover.set_phases(pc.advice_phase, pc.challenge_phase)
             self.verifier.set_phases(pc.advice_phase, pc.challenge_phase)
-        self.vk = shuffle_ref.Vk(pc.cs, self.params, self.fixed, self.sigma, self.vk_repr)
+        self.vk = proof_ref.Vk(pc.cs, self.params, self.fixed, self.sigma, self.vk_repr)
 
     def make_verifier(self, shuffles):
         p = self.params
@@ -64,7 +65,8 @@ class Setup:
 
     def ref(self, proof, variant=0, instance=None, scheme=GWC, transcript=EVM):
         inst = self.pc.instance(variant) if instance is None else instance
-        return shuffle_ref.verify(self.vk, [inst], proof, self.pc.advice_phase, self.pc.challenge_phase, scheme, transcript)
+        return proof_ref.verify(self.vk, [inst], proof, advice_phase=self.pc.advice_phase, challenge_phase=self.pc.challenge_phase,
+                                scheme=scheme, transcript=transcript)
 
     def dev(self, proofs, variants=None, verifier=None):
         insts = [self.pc.instance(v) for v in (variants or [0] * len(proofs))]
@@ -83,8 +85,8 @@ def flip(proof, at):
 
 def offsets(cs):
     """byte offsets (EVM transcript) of the first shuffle commitment and of the first shuffle evaluation"""
-    S, NL, NS = shuffle_ref.n_sets(cs), len(cs.lookups), len(cs.shuffles)
-    points, scalars = shuffle_ref.counts(cs, 1, GWC)
+    S, NL, NS = proof_ref.n_sets(cs), len(cs.lookups), len(cs.shuffles)
+    points, scalars = proof_ref.counts(cs, N=1, scheme=GWC)
     com = 64 * (cs.n_advice + 3 * NL + S)
     ev0 = 64 * (cs.n_advice + 3 * NL + S + NS + 1 + cs.degree() - 1)
     return com, ev0 + 32 * (scalars - 2 * NS)
@@ -93,10 +95,10 @@ def offsets(cs):
 def proof_size(cs, scheme=GWC, transcript=EVM):
     """what zg_prover_proof_size returns: SHPLONK's length is the proof's; GWC's bound counts one W per possible opening
     point (2 + every advice and fixed query) where the proof holds one per distinct point"""
-    length = shuffle_ref.proof_len(cs, scheme, transcript)
+    length = proof_ref.proof_len(cs, scheme=scheme, transcript=transcript)
     if scheme == SHPLONK:
         return length
-    spare = 2 + len(cs.advice_queries) + len(cs.fixed_queries) - shuffle_ref.n_point_sets(cs)
+    spare = 2 + len(cs.advice_queries) + len(cs.fixed_queries) - proof_ref.n_point_sets(cs)
     return length + (32 if transcript == BLAKE2B else 64) * spare
 
 
@@ -118,7 +120,7 @@ def test_proofs_are_accepted_and_tampered_ones_rejected(ctx, zg, orc, name):
     s = Setup(orc, zg, ctx, pc)
     assert s.prover.shuffles == len(pc.cs.shuffles) > 0
     (proof,) = s.prove([0], [7])
-    assert len(proof) == shuffle_ref.proof_len(pc.cs) and s.prover.proof_cap == proof_size(pc.cs)
+    assert len(proof) == proof_ref.proof_len(pc.cs) and s.prover.proof_cap == proof_size(pc.cs)
     assert s.ref(proof).verdict == 1
     assert s.dev([proof]) == [1]
     com, ev = offsets(pc.cs)
@@ -167,12 +169,12 @@ def test_a_wrong_instance_is_rejected(ctx, zg, orc):
                            shuffles=shuffles)
     inst = asg.instance_values(ilen)
     proof = prover.prove(asg.advice_values(), inst, 9)
-    vk = shuffle_ref.Vk(cs, params, fixed, sigma, vk_repr)
-    assert len(proof) == shuffle_ref.proof_len(cs) == prover.proof_cap - 64 * (2 + len(cs.advice_queries) + len(cs.fixed_queries) - shuffle_ref.n_point_sets(cs))
-    assert shuffle_ref.verify(vk, [inst], proof).verdict == 1 and verifier.verify([proof], [inst], 3) == [1]
+    vk = proof_ref.Vk(cs, params, fixed, sigma, vk_repr)
+    assert len(proof) == proof_ref.proof_len(cs) == prover.proof_cap - 64 * (2 + len(cs.advice_queries) + len(cs.fixed_queries) - proof_ref.n_point_sets(cs))
+    assert proof_ref.verify(vk, [inst], proof).verdict == 1 and verifier.verify([proof], [inst], 3) == [1]
     wrong = inst.copy()
     wrong[0, 0] = orc.fr_from_int(5)
-    assert shuffle_ref.verify(vk, [wrong], proof).verdict == 0 and verifier.verify([proof], [wrong], 3) == [0]
+    assert proof_ref.verify(vk, [wrong], proof).verdict == 0 and verifier.verify([proof], [wrong], 3) == [0]
     verifier.close()
     prover.close()
 
@@ -194,12 +196,12 @@ def test_z_is_the_recurrence_and_its_commitment_the_msm(ctx, zg, orc, name, k):
         for j in range(len(pc.cs.shuffles)):
             zrow = s.prover.fetch(FETCH_SHUFFLE_Z, j, pc.n)
             z = ints(orc, zrow)
-            want = shuffle_ref.shuffle_product(pc.cs, j, at, r.named["theta"], r.named["gamma"])
+            want = proof_ref.shuffle_product(pc.cs, j, at, r.named["theta"], r.named["gamma"])
             assert z[0] == 1 and z[pc.usable] == 1
             assert z[:pc.usable + 1] == want, j
             assert len(set(z[pc.usable + 1:])) == pc.n - pc.usable - 1 and 0 not in z[pc.usable + 1:]  # (the blinding rows are drawn)
             com = orc.msm(np.ascontiguousarray(zrow), gl, threads=16)
-            assert np.array_equal(shuffle_ref.affine(r.shuffle_z[0][j]), shuffle_ref.affine(com)), j
+            assert np.array_equal(proof_ref.affine(r.shuffle_z[0][j]), proof_ref.affine(com)), j
     s.close()
 
 
@@ -335,7 +337,7 @@ def test_every_multiopen_and_transcript(ctx, zg, orc, scheme, transcript):
         obj.set_multiopen(scheme)
         obj.set_transcript(transcript)
     (proof,) = s.prove([0], [5])
-    assert len(proof) == shuffle_ref.proof_len(pc.cs, scheme, transcript)
+    assert len(proof) == proof_ref.proof_len(pc.cs, scheme=scheme, transcript=transcript)
     assert s.prover.proof_cap == proof_size(pc.cs, scheme, transcript) and (scheme == GWC or s.prover.proof_cap == len(proof))
     assert s.ref(proof, scheme=scheme, transcript=transcript).verdict == 1
     assert s.dev([proof]) == [1]
@@ -353,7 +355,7 @@ def test_split_domain_and_terms_by_degree_at_k14(ctx, zg, orc):
     s = Setup(orc, zg, ctx, pc)
     adv, inst = s.advice(0), pc.instance(0)
     proof = s.prover.prove(adv, inst, 3)
-    assert len(proof) == shuffle_ref.proof_len(pc.cs) and s.dev([proof]) == [1] and s.ref(proof).verdict == 1
+    assert len(proof) == proof_ref.proof_len(pc.cs) and s.dev([proof]) == [1] and s.ref(proof).verdict == 1
     s.prover.set_overlap(False)
     assert s.prover.quotient_terms()["active"]
     for by_degree in (True, False):

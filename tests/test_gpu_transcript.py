@@ -1,8 +1,8 @@
 """halo2's Blake2b transcript with compressed points on the device (zg_prover_set_transcript / zg_verifier_set_transcript,
 zg_g1_compress / zg_g1_decompress).  Proof bytes are held against create_proof walked by the CALLER
 over the library's arithmetic-level entries (tests/arith_level.py DeviceBackend) with the Blake2b writer of
-tests/blake2b_ref.py -- that path takes its challenges as arguments and shares no transcript code with the prover --
-verdicts against the reference verifiers of tests/multi_ref.py and tests/shplonk_ref.py on that transcript, and decompressed
+tests/transcript_ref.py -- that path takes its challenges as arguments and shares no transcript code with the prover --
+verdicts against the reference verifier of tests/proof_ref.py on that transcript, and decompressed
 points against Python integers.  tests/test_transcript_host.py holds the host code and the golden proof without a GPU."""
 import ctypes
 import json
@@ -11,16 +11,16 @@ import numpy as np
 import pytest
 
 import arith_level
-import blake2b_ref as b2
 import field9_ref as fref
-import multi_ref
+import proof_ref
 import transcript_cases as tc
+import transcript_ref as b2
 from circuits import toy_circuit, variant_circuit
 from test_gpu_multi import toy_family
 
 pytestmark = pytest.mark.gpu
 
-R, Q = multi_ref.R, multi_ref.Q
+R, Q = proof_ref.R, proof_ref.Q
 GWC, SHPLONK = 0, 1
 EVM, BLAKE2B = 0, 1
 
@@ -31,11 +31,6 @@ CIRCUITS = {
     "no_lookup": lambda: variant_circuit("no_lookup", k=5),
     "wide_lookup": lambda: variant_circuit("wide_lookup", k=5),
 }
-
-
-@pytest.fixture(autouse=True)
-def blake2b_walkers(monkeypatch):
-    b2.use(monkeypatch)
 
 
 class Setup:
@@ -57,7 +52,7 @@ class Setup:
         fc, sc = self.prover.vk_commitments()
         self.verifier = zg.Verifier(ctx, self.img, fc, sc, self.params.g_np()[0], np.array(self.params.g2, np.uint64),
                                     np.array(self.params.s_g2, np.uint64), self.vk_repr)
-        self.ref = multi_ref.Vk(cs, self.params, self.fixed, self.sigma, self.vk_repr)
+        self.ref = proof_ref.Vk(cs, self.params, self.fixed, self.sigma, self.vk_repr)
         self.adv = [a.advice_values() for _, a, _ in family]
         self.inst = [a.instance_values(self.ilen) for _, a, _ in family]
         self.prover.set_batch(len(family))
@@ -65,10 +60,14 @@ class Setup:
             obj.set_multiopen(scheme)
             obj.set_transcript(BLAKE2B)
 
-    def walked(self, i, seed):
-        """create_proof walked by the caller over the device entries, Blake2b writer"""
+    def walked(self, i, seed, writer=None):
+        """create_proof walked by the caller over the device entries, Blake2b writer (or, GWC only, the one given)"""
         be = arith_level.DeviceBackend(self.zg, self.ctx, self.prover, self.cs, self.fixed, self.sigma, self.g, self.gl, seed)
-        out = b2.create_proof(be, self.ref, self.adv[i], self.inst[i], self.scheme)
+        if writer is None:
+            out = proof_ref.create_proof(be, self.ref, self.adv[i], self.inst[i], scheme=self.scheme, transcript=BLAKE2B)
+        else:
+            assert self.scheme == GWC
+            out = arith_level.create_proof(be, self.cs, self.vk_repr, self.adv[i], self.inst[i], writer=writer)
         self.ctx.sync()
         return out
 
@@ -81,7 +80,7 @@ class Setup:
         return a
 
     def ref_verify(self, insts, proof):
-        return b2.verify(self.ref, insts, proof, self.scheme)
+        return proof_ref.verify(self.ref, insts, proof, scheme=self.scheme, transcript=BLAKE2B).verdict
 
     def close(self):
         self.verifier.close()
@@ -101,7 +100,7 @@ def test_bytes_are_the_caller_walked_proofs_in_both_forms(ctx, zg, orc, name, sc
     s = Setup(orc, zg, ctx, [CIRCUITS[name]()], scheme)
     got = s.both_forms(lambda: s.prover.prove(s.adv[0], s.inst[0], 11))
     assert got == s.walked(0, 11)
-    assert len(got) == b2.proof_len(s.cs, 1, scheme) <= s.prover.proof_cap
+    assert len(got) == proof_ref.proof_len(s.cs, N=1, scheme=scheme, transcript=BLAKE2B) <= s.prover.proof_cap
     assert s.ref_verify([s.inst[0]], got) == 1
     assert s.verifier.verify([got], [s.inst[0]], 5) == [1]
     s.close()
@@ -124,7 +123,7 @@ def test_prove_multi_is_the_golden_record_and_one_circuit_is_prove(ctx, zg, orc)
     two = s.both_forms(lambda: s.prover.prove_multi(s.adv, s.inst, [31, 32]))
     rec = json.load(open(tc.GOLDEN_B2_N2))  # the proof the host test judges: these bytes
     assert (rec["params_seed"], rec["vk_repr"], rec["seeds"]) == (0xABCDEF, 0x1234567, [31, 32]) and two.hex() == rec["proof"]
-    assert len(two) == b2.proof_len(s.cs, 2, GWC) <= s.prover.proof_size_multi(2) < multi_ref.proof_len(s.cs, 2)
+    assert len(two) == proof_ref.proof_len(s.cs, N=2, transcript=BLAKE2B) <= s.prover.proof_size_multi(2) < proof_ref.proof_len(s.cs, N=2)
     assert s.verifier.verify_multi([two], [s.inst], 9, 2) == [1]
     assert s.verifier.verify_multi([two], [[s.inst[1], s.inst[0]]], 9, 2) == [0]
     s.close()
@@ -163,7 +162,7 @@ def test_switching_back_gives_the_evm_bytes_and_a_fork_inherits(ctx, zg, orc):
     s.close()
 
 
-class CountingTranscript(b2.Transcript):
+class CountingTranscript(b2.Blake2bWriter):
     """the writer, counting what it absorbs: the total at every finalisation"""
 
     def __init__(self, keccak=None):
@@ -185,13 +184,12 @@ class CountingTranscript(b2.Transcript):
         return super().squeeze()
 
 
-def test_block_edges_a_squeeze_at_a_full_block_and_one_byte_later(ctx, zg, orc, monkeypatch):
+def test_block_edges_a_squeeze_at_a_full_block_and_one_byte_later(ctx, zg, orc):
     """the toy circuit (3 advice columns, 1 lookup, 1 instance column) with 24 instance values: the beta squeeze finalises
     at 9 whole blocks, the gamma squeeze one byte later"""
     s = Setup(orc, zg, ctx, [toy_circuit(k=5)], ilen=24)
     assert (s.cs.n_advice, len(s.cs.lookups), s.cs.n_instance, s.inst[0].shape[1]) == (3, 1, 1, 24)
-    monkeypatch.setattr(arith_level, "Transcript", CountingTranscript)
-    walked = s.walked(0, 17)
+    walked = s.walked(0, 17, writer=CountingTranscript)
     totals = CountingTranscript.last.at_squeeze
     assert totals[:3] == [33 * 25 + 65 * 3 + 1, 33 * 25 + 65 * 3 + 1 + 65 * 2 + 1, 33 * 25 + 65 * 3 + 1 + 65 * 2 + 2]
     assert totals[1] == 1152 == 9 * 128 and totals[2] % 128 == 1
@@ -206,8 +204,8 @@ def test_block_edges_a_squeeze_at_a_full_block_and_one_byte_later(ctx, zg, orc, 
 # ---------------------------------------------------------------------------------------------------- verdicts
 def tampered(s, good):
     """name -> (proof, instance, expected class)"""
-    points, _ = b2.counts(s.cs, 1, s.scheme)
-    tail = 2 if s.scheme == SHPLONK else multi_ref.n_point_sets(s.cs)
+    points, _ = proof_ref.counts(s.cs, N=1, scheme=s.scheme)
+    tail = 2 if s.scheme == SHPLONK else proof_ref.n_point_sets(s.cs)
     s0 = 32 * (points - tail)  # the first evaluation
     sc0 = int.from_bytes(good[s0:s0 + 32], "little")
     inst = s.inst[0]
@@ -339,8 +337,8 @@ def test_tiny_model_k14_image_to_proof(ctx, zg, orc):
     plan = zg.WitnessPlan(ctx, witness_tape.trace(wnn, k).arrays())
     proofs, outputs, sts = s.prover.prove_images(plan, real[None], [7])
     assert sts == [0]
-    points, scalars = b2.counts(s.cs, 1, GWC)
-    assert (points, scalars) == (30, 60) and len(proofs[0]) == 32 * (points + scalars) == b2.proof_len(s.cs, 1, GWC)
+    points, scalars = proof_ref.counts(s.cs, N=1, scheme=GWC)
+    assert (points, scalars) == (30, 60) and len(proofs[0]) == 32 * (points + scalars) == proof_ref.proof_len(s.cs, N=1, transcript=BLAKE2B)
     assert [zg.fr_to_int(x) for x in outputs[0]] == wnn.predict(real)
     inst = outputs[0][None, :, :]
     assert s.verifier.verify([proofs[0]], [inst], 3) == [1]

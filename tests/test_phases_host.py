@@ -1,6 +1,6 @@
-"""Advice phases and challenges, the host side: tests/phases_ref.py (the Python-integer verify_proof with phases) held
+"""Advice phases and challenges, the host side: tests/proof_ref.py (the Python-integer verify_proof, here its phases) held
 against the oracle's pairing verifier where both apply; csrc/proof_layout.h's phase order, boundaries, challenge lists
-and point_index against the order phases_ref walks, through tests/abi/phases_layout_probe (a stand-alone host program,
+and point_index against the order proof_ref walks, through tests/abi/phases_layout_probe (a stand-alone host program,
 built once more under the sanitizers); and the test circuits of tests/phases_circuits.py against a mock check.  No device."""
 import os
 import random
@@ -9,9 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
-import multi_ref
 import phases_circuits
-import phases_ref
+import proof_ref
 from circuit import ADVICE, FIXED, INSTANCE, R
 from circuits import toy_circuit, variant_circuit
 
@@ -33,7 +32,7 @@ def test_reference_gives_the_oracles_verdicts_on_one_phase_circuits(orc, make):
     adv, inst = asg.advice_values(), asg.instance_values(ilen)
     st, proof, _ = orc.create_proof(pk, adv, inst, 7)
     assert st == 0
-    vk = phases_ref.Vk(cs, params, fixed, sigma, vk_repr)
+    vk = proof_ref.Vk(cs, params, fixed, sigma, vk_repr)
     wrong = inst.copy()
     wrong[0, 0] = orc.fr_from_int(5)
     tampered = bytearray(proof)
@@ -44,12 +43,11 @@ def test_reference_gives_the_oracles_verdicts_on_one_phase_circuits(orc, make):
              (inst, proof + b"\0")]
     for i, (ins, prf) in enumerate(cases):
         want = orc.verify_proof_pairing(pk, ins, prf)
-        got = phases_ref.verify(vk, [ins], prf)
+        got = proof_ref.verify(vk, [ins], prf)
         assert got.verdict == (1 if want == 1 else 0 if want == 0 else -1), (i, want, got.verdict)
-        assert got.verdict == multi_ref.verify(vk, [ins], prf), i
-    ok = phases_ref.verify(vk, [inst], proof)
+    ok = proof_ref.verify(vk, [inst], proof)
     assert ok.verdict == 1 and ok.challenges == {} and ok.order == [(0, 0, c) for c in range(cs.n_advice)]
-    assert len(proof) == phases_ref.proof_len(cs)
+    assert len(proof) == proof_ref.proof_len(cs)
 
 
 # ---------------------------------------------------------------------------------------------- the test circuits themselves
@@ -122,7 +120,7 @@ def test_the_circuits_are_what_the_issue_asks_for():
 
 # ---------------------------------------------------------------------------------------------- the layout
 def script_line(cs, N, advice_phase, challenge_phase):
-    head = [cs.n_advice, cs.n_fixed, len(cs.perm_columns), len(cs.lookups), multi_ref.n_sets(cs), cs.degree() - 1, cs.blinding_factors(), cs.k, N]
+    head = [cs.n_advice, cs.n_fixed, len(cs.perm_columns), len(cs.lookups), proof_ref.n_sets(cs), cs.degree() - 1, cs.blinding_factors(), cs.k, N]
     for qs in (cs.advice_queries, cs.fixed_queries):
         head.append(len(qs))
         for col, rot in qs:
@@ -165,8 +163,8 @@ def check(exe, tmp_path):
         pc = made[name]
         cs, A = pc.cs, pc.cs.n_advice
         assert g["legal"] == "yes", (name, g["legal"])
-        order = phases_ref.advice_order(cs, N, pc.advice_phase)
-        walk = phases_ref.phases_of(cs, pc.advice_phase, pc.challenge_phase)
+        order = proof_ref.advice_order(cs, N, pc.advice_phase)
+        walk = proof_ref.phases_of(cs, pc.advice_phase, pc.challenge_phase)
         for scheme in ("gwc", "shplonk"):
             s = g[scheme]
             # where each (circuit, column) stands: the order the reference reads the commitments in
@@ -183,9 +181,9 @@ def check(exe, tmp_path):
             assert end == N * A
             # nothing else moves, and the proof is as long as without phases
             sizes = dict(zip(s["sizes"][::2], (int(v) for v in s["sizes"][1::2])))
-            sch = phases_ref.SHPLONK if scheme == "shplonk" else phases_ref.GWC
-            assert sizes["evm"] == phases_ref.proof_len(cs, sch, phases_ref.EVM, N)
-            assert sizes["blake2b"] == phases_ref.proof_len(cs, sch, phases_ref.BLAKE2B, N)
+            sch = proof_ref.SHPLONK if scheme == "shplonk" else proof_ref.GWC
+            assert sizes["evm"] == proof_ref.proof_len(cs, N=N, scheme=sch, transcript=proof_ref.EVM)
+            assert sizes["blake2b"] == proof_ref.proof_len(cs, N=N, scheme=sch, transcript=proof_ref.BLAKE2B)
     by_case = {}
     for (name, N, z), g in zip(flat, got[len(cases):]):
         by_case[name, N, z] = g
@@ -222,5 +220,5 @@ def test_layout_probe_under_the_sanitizers(tmp_path):
 
 def test_interleaved_commitment_order_differs_from_column_order():
     pc = phases_circuits.interleaved()
-    assert phases_ref.advice_order(pc.cs, 1, pc.advice_phase) == [(0, 0, 1), (1, 0, 0), (1, 0, 2)]
-    assert phases_ref.advice_order(pc.cs, 2, pc.advice_phase) == [(0, 0, 1), (0, 1, 1), (1, 0, 0), (1, 0, 2), (1, 1, 0), (1, 1, 2)]
+    assert proof_ref.advice_order(pc.cs, 1, pc.advice_phase) == [(0, 0, 1), (1, 0, 0), (1, 0, 2)]
+    assert proof_ref.advice_order(pc.cs, 2, pc.advice_phase) == [(0, 0, 1), (0, 1, 1), (1, 0, 0), (1, 0, 2), (1, 1, 0), (1, 1, 2)]

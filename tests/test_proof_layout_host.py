@@ -1,15 +1,13 @@
 """csrc/proof_layout.h -- the one statement of a proof's order that prover, verifier and the proof-size functions share --
 against the Python references, through tests/abi/proof_layout_probe (a stand-alone host program): the opening queries in
-create_proof's order (multi_ref.circuit_queries and the shared tail), the evaluations in transcript order, GWC's point
-sets (multi_ref.n_point_sets, point_set_lengths), SHPLONK's commitments, rotation sets and T
-(shplonk_ref.intermediate_sets on the same queries), the exact lengths of all four (scheme, transcript) pairs and the
+create_proof's order (proof_ref.circuit_queries and the shared tail), the evaluations in transcript order, GWC's point
+sets (proof_ref.n_point_sets, point_set_lengths), SHPLONK's commitments, rotation sets and T
+(proof_ref.intermediate_sets on the same queries), the exact lengths of all four (scheme, transcript) pairs and the
 bound the ABI returns (orc.proof_size).  No device needed."""
 import os
 import subprocess
 
-import blake2b_ref
-import multi_ref
-import shplonk_ref
+import proof_ref
 from test_shplonk_host import CIRCUITS, many_queries_circuit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,7 +50,7 @@ def shapes():
 
 
 def script_line(cs, N):
-    head = [cs.n_advice, cs.n_fixed, len(cs.perm_columns), len(cs.lookups), multi_ref.n_sets(cs), cs.degree() - 1, cs.blinding_factors(), cs.k, N]
+    head = [cs.n_advice, cs.n_fixed, len(cs.perm_columns), len(cs.lookups), proof_ref.n_sets(cs), cs.degree() - 1, cs.blinding_factors(), cs.k, N]
     for qs in (cs.advice_queries, cs.fixed_queries):
         head.append(len(qs))
         for col, rot in qs:
@@ -81,10 +79,10 @@ def run(exe, tmp_path, cases):
 
 def expected_queries(cs, N):
     """(rotation, (family, circuit, index), evaluation index) in create_proof's order: every circuit's own queries
-    (multi_ref.circuit_queries), then what the circuits share -- fixed queries, sigmas, h, random, the last three at 0.
+    (proof_ref.circuit_queries), then what the circuits share -- fixed queries, sigmas, h, random, the last three at 0.
     Evaluations in transcript order: every circuit's advice | fixed, random, sigma | every circuit's permutation
     evaluations (3 per set, 2 for the last) | every circuit's lookup evaluations (5 each) | the expected h(x)."""
-    AQ, FQ, P, NL, S = len(cs.advice_queries), len(cs.fixed_queries), len(cs.perm_columns), len(cs.lookups), multi_ref.n_sets(cs)
+    AQ, FQ, P, NL, S = len(cs.advice_queries), len(cs.fixed_queries), len(cs.perm_columns), len(cs.lookups), proof_ref.n_sets(cs)
     npz = 3 * S - 1 if S else 0
     ev_fix = N * AQ
     ev_rand = ev_fix + FQ
@@ -96,7 +94,7 @@ def expected_queries(cs, N):
             "ptab": lambda i: ("perm", 2 * i + 1)}
     out = []
     for c in range(N):
-        for rot, fam, index, key in multi_ref.circuit_queries(cs):
+        for rot, fam, index, key in proof_ref.circuit_queries(cs):
             ev = {"adv": lambda i: c * AQ + i, "pz": lambda s, j: ev_pz + c * npz + 3 * s + j, "lk": lambda l, j: ev_lk + c * 5 * NL + 5 * l + j}[key[0]](*key[1:])
             f, i = poly[fam](index)
             out.append((rot, (f, c, i), ev))
@@ -121,7 +119,7 @@ def check_case(cs, N, got):
     for scheme in ("gwc", "shplonk"):
         g = got[scheme]
         rotations = [int(r) % n for r in g["rotations"]]
-        assert len(set(rotations)) == len(rotations) == multi_ref.n_point_sets(cs)
+        assert len(set(rotations)) == len(rotations) == proof_ref.n_point_sets(cs)
         queries = []
         for tok in g["queries"]:
             p, rest = tok.split("@")
@@ -138,15 +136,16 @@ def check_case(cs, N, got):
         by_ev = sorted(queries, key=lambda q: q[2])
         assert [q[2] for q in by_ev] == list(range(ev_h + 1))
         assert [(poly_of(t.split("@")[0]), rotations[int(t.split("@")[1])]) for t in g["transcript"]] == [(q[1], q[0]) for q in by_ev]
-        points, scalars = blake2b_ref.counts(cs, N, blake2b_ref.SHPLONK if scheme == "shplonk" else blake2b_ref.GWC)
+        code = proof_ref.SHPLONK if scheme == "shplonk" else proof_ref.GWC
+        points, scalars = proof_ref.counts(cs, N=N, scheme=code)
         sizes = dict(zip(g["sizes"][::2], (int(v) for v in g["sizes"][1::2])))
         assert (sizes["points"], sizes["scalars"]) == (points, scalars) and scalars == ev_h
-        assert sizes["evm"] == (shplonk_ref.proof_len(cs, N) if scheme == "shplonk" else multi_ref.proof_len(cs, N))
-        assert sizes["blake2b"] == blake2b_ref.proof_len(cs, N, blake2b_ref.SHPLONK if scheme == "shplonk" else blake2b_ref.GWC)
+        assert sizes["evm"] == proof_ref.proof_len(cs, N=N, scheme=code, transcript=proof_ref.EVM)
+        assert sizes["blake2b"] == proof_ref.proof_len(cs, N=N, scheme=code, transcript=proof_ref.BLAKE2B)
         # the families tile the points and the evaluations in the stated order; the Blake2b items: the evaluations stand
         # between the h pieces and the argument's points
         fam = [t.split(":") for t in g["points"]]
-        A, NL, S = cs.n_advice, len(cs.lookups), multi_ref.n_sets(cs)
+        A, NL, S = cs.n_advice, len(cs.lookups), proof_ref.n_sets(cs)
         tail = 2 if scheme == "shplonk" else len(rotations)
         assert [(f, int(c)) for f, _, c in fam] == [("adv", N * A), ("perm", N * 2 * NL), ("pz", N * S), ("lz", N * NL), ("rand", 1),
                                                    ("hp", cs.degree() - 1), ("open", tail)]
@@ -162,9 +161,9 @@ def check_case(cs, N, got):
     sets = [ints(t) for t in got["gwc"]["sets"]]
     qs = [(rot % n, p) for rot, p, _ in want]
     assert sets == [[i for i, q in enumerate(qs) if q[0] == rot] for rot in rotations]
-    assert {rot: len(s) for rot, s in zip(rotations, sets)} == multi_ref.point_set_lengths(cs, N)
-    # SHPLONK: shplonk_ref.intermediate_sets on the same queries
-    ref_sets, T = shplonk_ref.intermediate_sets(qs)
+    assert {rot: len(s) for rot, s in zip(rotations, sets)} == proof_ref.point_set_lengths(cs, N)
+    # SHPLONK: proof_ref.intermediate_sets on the same queries
+    ref_sets, T = proof_ref.intermediate_sets(qs)
     g = got["shplonk"]
     coms = []
     for tok in g["coms"]:
@@ -195,15 +194,15 @@ def test_the_shapes_cover_what_they_are_here_for():
     s = shapes()
     n = 32
     qs = [(r % n, p) for r, p, _ in expected_queries(s["many_queries"], 1)[0]]
-    assert len(set(frozenset(p) for p, _ in shplonk_ref.intermediate_sets(qs)[0])) >= 4
-    sets, T = shplonk_ref.intermediate_sets([(r % n, p) for r, p, _ in expected_queries(s["hand_written"], 1)[0]])
+    assert len(set(frozenset(p) for p, _ in proof_ref.intermediate_sets(qs)[0])) >= 4
+    sets, T = proof_ref.intermediate_sets([(r % n, p) for r, p, _ in expected_queries(s["hand_written"], 1)[0]])
     adv = [[k[2] for k in keys if k[0] == "adv"] for _, keys in sets]
     assert adv == [[0, 4], [1, 5], [2], [3]] and [len(p) for p, _ in sets] == [2, 1, 2, 3] and len(T) == 4
     # 3 = -29 and 0 = 32: the two advice columns share the rotation set {3, 0}; 1 = -31 puts the fixed column with z(wx)
-    sets, T = shplonk_ref.intermediate_sets([(r % n, p) for r, p, _ in expected_queries(s["wrapped"], 1)[0]])
+    sets, T = proof_ref.intermediate_sets([(r % n, p) for r, p, _ in expected_queries(s["wrapped"], 1)[0]])
     assert sets[0] == ([3, 0], [("adv", 0, 0), ("adv", 0, 1)])
-    assert multi_ref.n_point_sets(s["wrapped"]) == len(T) == 5 and sorted(T) == [0, 1, 3, 26, 31]
-    assert len(s["two_lookups"].lookups) == 2 and multi_ref.n_sets(s["toy"]) == 2
+    assert proof_ref.n_point_sets(s["wrapped"]) == len(T) == 5 and sorted(T) == [0, 1, 3, 26, 31]
+    assert len(s["two_lookups"].lookups) == 2 and proof_ref.n_sets(s["toy"]) == 2
 
 
 def test_host_build_meets_the_references(tmp_path):

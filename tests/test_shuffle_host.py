@@ -1,6 +1,6 @@
-"""The shuffle argument without a device: csrc/proof_layout.h with NS shuffles against tests/shuffle_ref.py's order,
+"""The shuffle argument without a device: csrc/proof_layout.h with NS shuffles against tests/proof_ref.py's order,
 through tests/abi/shuffle_layout_probe (a stand-alone host program); the ABI's new entries and zg_shuffle's layout;
-shuffle_ref against the oracle and phases_ref on circuits without shuffles; the test circuits themselves."""
+proof_ref against the oracle on circuits without shuffles; the test circuits themselves."""
 import ctypes
 import json
 import os
@@ -8,11 +8,8 @@ import subprocess
 
 import pytest
 
-import multi_ref
-import phases_ref
-import shplonk_ref
+import proof_ref
 import shuffle_circuits
-import shuffle_ref
 import test_proof_layout_host as plh
 from circuits import toy_circuit, variant_circuit
 from test_abi import header_functions
@@ -32,7 +29,7 @@ def with_shuffles(cs, ns):
 
 def script_line(cs, N):
     tok = plh.script_line(cs, N).split()
-    return " ".join(tok[:9] + [str(len(shuffle_ref.shuffles_of(cs)))] + tok[9:])
+    return " ".join(tok[:9] + [str(len(proof_ref.shuffles_of(cs)))] + tok[9:])
 
 
 def run(exe, tmp_path, cases, line=script_line):
@@ -58,11 +55,11 @@ def parse(stdout, count):
 
 
 def expected_queries(cs):
-    """(rotation, (family, 0, index), evaluation index) of ONE circuit in create_proof's order, from shuffle_ref.circuit_queries
+    """(rotation, (family, 0, index), evaluation index) of ONE circuit in create_proof's order, from proof_ref.circuit_queries
     and the shared tail; the evaluations in transcript order: advice | fixed, random, sigma | permutation | lookups |
     shuffles (z, z(wx) each) | the expected h(x)"""
-    AQ, FQ, P, NL, S = len(cs.advice_queries), len(cs.fixed_queries), len(cs.perm_columns), len(cs.lookups), multi_ref.n_sets(cs)
-    NS = len(shuffle_ref.shuffles_of(cs))
+    AQ, FQ, P, NL, S = len(cs.advice_queries), len(cs.fixed_queries), len(cs.perm_columns), len(cs.lookups), proof_ref.n_sets(cs)
+    NS = len(proof_ref.shuffles_of(cs))
     ev_fix = AQ
     ev_rand = ev_fix + FQ
     ev_sig = ev_rand + 1
@@ -74,7 +71,7 @@ def expected_queries(cs):
             "ptab": lambda i: ("perm", 2 * i + 1), "sz": lambda i: ("sz", i)}
     where = {"adv": lambda i: i, "pz": lambda s, j: ev_pz + 3 * s + j, "lk": lambda l, j: ev_lk + 5 * l + j, "sh": lambda j, e: ev_sh + 2 * j + e}
     out = []
-    for rot, fam, index, key in shuffle_ref.circuit_queries(cs):
+    for rot, fam, index, key in proof_ref.circuit_queries(cs):
         f, i = poly[fam](index)
         out.append((rot, (f, 0, i), where[key[0]](*key[1:])))
     out += [(rot, ("fix", 0, col), ev_fix + i) for i, (col, rot) in enumerate(cs.fixed_queries)]
@@ -84,15 +81,15 @@ def expected_queries(cs):
 
 
 def check_case(cs, got):
-    n, NS = 1 << cs.k, len(shuffle_ref.shuffles_of(cs))
-    A, NL, S = cs.n_advice, len(cs.lookups), multi_ref.n_sets(cs)
+    n, NS = 1 << cs.k, len(proof_ref.shuffles_of(cs))
+    A, NL, S = cs.n_advice, len(cs.lookups), proof_ref.n_sets(cs)
     want, ev_sh, ev_h = expected_queries(cs)
     qs = [(rot % n, p) for rot, p, _ in want]
     for scheme in ("gwc", "shplonk"):
         g = got[scheme]
         code = SHPLONK if scheme == "shplonk" else GWC
         rotations = [int(r) % n for r in g["rotations"]]
-        assert len(set(rotations)) == len(rotations) == shuffle_ref.n_point_sets(cs)
+        assert len(set(rotations)) == len(rotations) == proof_ref.n_point_sets(cs)
         queries = []
         for tok in g["queries"]:
             p, rest = tok.split("@")
@@ -104,10 +101,10 @@ def check_case(cs, got):
         assert [q[2] for q in by_ev] == list(range(ev_h + 1))
         assert [(plh.poly_of(t.split("@")[0]), rotations[int(t.split("@")[1])]) for t in g["transcript"]] == [(q[1], q[0]) for q in by_ev]
         # lengths: both transcripts, and the bounds
-        points, scalars = shuffle_ref.counts(cs, 1, code)
+        points, scalars = proof_ref.counts(cs, N=1, scheme=code)
         sizes = dict(zip(g["sizes"][::2], (int(v) for v in g["sizes"][1::2])))
         assert (sizes["points"], sizes["scalars"]) == (points, scalars) and scalars == ev_h
-        assert sizes["evm"] == shuffle_ref.proof_len(cs, code, EVM) and sizes["blake2b"] == shuffle_ref.proof_len(cs, code, BLAKE2B)
+        assert sizes["evm"] == proof_ref.proof_len(cs, scheme=code, transcript=EVM) and sizes["blake2b"] == proof_ref.proof_len(cs, scheme=code, transcript=BLAKE2B)
         tail = 2 if scheme == "shplonk" else len(rotations)
         max_open = 2 if scheme == "shplonk" else 2 + len(cs.advice_queries) + len(cs.fixed_queries)
         assert sizes["bound_evm"] == sizes["evm"] + 64 * (max_open - tail) and sizes["bound_blake2b"] == sizes["blake2b"] + 32 * (max_open - tail)
@@ -132,7 +129,7 @@ def check_case(cs, got):
         assert [int(v) for v in g["items"]] == list(range(before)) + [before + scalars + i for i in range(tail)]
     sets = [plh.ints(t) for t in got["gwc"]["sets"]]
     assert sets == [[i for i, q in enumerate(qs) if q[0] == rot] for rot in rotations]
-    ref_sets, T = shplonk_ref.intermediate_sets(qs)
+    ref_sets, T = proof_ref.intermediate_sets(qs)
     g = got["shplonk"]
     coms = []
     for tok in g["coms"]:
@@ -221,16 +218,13 @@ def test_reference_without_shuffles_is_phases_ref_and_the_oracle(orc, make):
     adv, inst = asg.advice_values(), asg.instance_values(ilen)
     st, proof, _ = orc.create_proof(pk, adv, inst, 7)
     assert st == 0
-    vk = shuffle_ref.Vk(cs, params, fixed, sigma, vk_repr)
+    vk = proof_ref.Vk(cs, params, fixed, sigma, vk_repr)
     late = bytearray(proof)
     late[-70] ^= 1
     for i, prf in enumerate((proof, bytes(late), proof[:-1], proof + b"\0")):
         want = orc.verify_proof_pairing(pk, inst, prf)
-        got = shuffle_ref.verify(vk, [inst], prf)
-        assert got.verdict == (1 if want == 1 else 0 if want == 0 else -1) == phases_ref.verify(vk, [inst], prf).verdict, i
-    for scheme in (GWC, SHPLONK):
-        for tr in (EVM, BLAKE2B):
-            assert shuffle_ref.proof_len(cs, scheme, tr) == phases_ref.proof_len(cs, scheme, tr)
+        got = proof_ref.verify(vk, [inst], prf)
+        assert got.verdict == (1 if want == 1 else 0 if want == 0 else -1), i
 
 
 # ---------------------------------------------------------------------------------------------- the circuits themselves
@@ -247,7 +241,7 @@ def test_circuits_state_shuffles_and_the_bad_witness_is_none(name):
         for ph in range(pc.n_phases):
             cols.update(pc.witness(ph, ch, variant))
         at = shuffle_circuits.cell_at(pc, cols, ch)
-        ends = [shuffle_ref.shuffle_product(cs, j, at, 0x1234, 0x5678)[pc.usable] for j in range(len(cs.shuffles))]
+        ends = [proof_ref.shuffle_product(cs, j, at, 0x1234, 0x5678)[pc.usable] for j in range(len(cs.shuffles))]
         assert all(e == 1 for e in ends) == holds, (variant, ends)
 
 

@@ -1,16 +1,16 @@
 """The host side of halo2's Blake2b transcript with compressed points, on a machine without a GPU:
 csrc/blake2b.h, the Blake2bTranscript of csrc/transcript.h and the host path of csrc/g1_compress.h through the stand-alone
-program tests/abi/transcript_probe.hip, against hashlib and Python integers (tests/blake2b_ref.py); and the golden Blake2b
+program tests/abi/transcript_probe.hip, against hashlib and Python integers (tests/transcript_ref.py); and the golden Blake2b
 proof of two circuits, made on the GPU, against the reference verifier."""
 import hashlib
 import json
 import os
 import subprocess
 
-import blake2b_ref as b2
 import field9_ref as ref
-import multi_ref
+import proof_ref
 import transcript_cases as tc
+import transcript_ref as b2
 from circuit import R
 from test_gpu_multi import toy_family
 
@@ -67,7 +67,7 @@ def transcript_cases():
     the second squeeze finalises one byte later; then points and scalars into the proof, and the identity refused"""
     rng_vals = [(0x1234567 * (i + 1) ** 3) % R for i in range(31)]
     P, S = ref.ec_mul(7, ref.G), ref.ec_mul(11, ref.G)
-    t = b2.Transcript()
+    t = b2.Blake2bWriter()
     toks, outs = [], []
     for v in rng_vals:
         t.common_scalar(v)
@@ -88,7 +88,7 @@ def transcript_cases():
     outs.append(le(t.squeeze()))
     toks.append("q")
     first = ("tr " + " ".join(toks), " ".join(outs) + " stream=%s failed=0" % bytes(t.out).hex())
-    ident = ("tr p%s,%s q" % (le(0), le(0)), "%s stream=- failed=1" % le(b2.Transcript().squeeze()))
+    ident = ("tr p%s,%s q" % (le(0), le(0)), "%s stream=- failed=1" % le(b2.Blake2bWriter().squeeze()))
     return [first, ident]
 
 
@@ -148,22 +148,25 @@ def test_host_build_under_the_sanitizers(tmp_path):
     check(exe, tmp_path)
 
 
-def test_golden_proof_of_two_circuits(orc, monkeypatch):
+def test_golden_proof_of_two_circuits(orc):
     """the device prover's Blake2b proof of two toy circuits (k = 5, GWC; tests/test_gpu_transcript.py holds the prover to
     these bytes): the reference verifier accepts it, and rejects it with the instances swapped"""
-    b2.use(monkeypatch)
     rec = json.load(open(tc.GOLDEN_B2_N2))
     family = toy_family(2)
     cs, asg, ilen = family[0]
     params = orc.params_new(cs.k, rec["params_seed"])
-    vk = multi_ref.Vk(cs, params, asg.fixed_values(), asg.sigma_values(), orc.fr_from_int(rec["vk_repr"]))
+    vk = proof_ref.Vk(cs, params, asg.fixed_values(), asg.sigma_values(), orc.fr_from_int(rec["vk_repr"]))
     inst = [a.instance_values(ilen) for _, a, _ in family]
     proof = bytes.fromhex(rec["proof"])
-    assert len(proof) == b2.proof_len(cs, 2, b2.GWC) < multi_ref.proof_len(cs, 2)
-    assert b2.verify(vk, inst, proof) == 1
-    assert b2.verify(vk, [inst[1], inst[0]], proof) == 0
-    assert b2.verify(vk, inst, proof + b"\x00") == 0
-    assert b2.verify(vk, inst, proof[:-1]) == -1
+
+    def verdict(instances, p) -> int:
+        return proof_ref.verify(vk, instances, p, transcript=b2.BLAKE2B).verdict
+
+    assert len(proof) == proof_ref.proof_len(cs, N=2, transcript=b2.BLAKE2B) < proof_ref.proof_len(cs, N=2)
+    assert verdict(inst, proof) == 1
+    assert verdict([inst[1], inst[0]], proof) == 0
+    assert verdict(inst, proof + b"\x00") == 0
+    assert verdict(inst, proof[:-1]) == -1
     flipped = bytearray(proof)
     flipped[31] ^= 0x80  # the first commitment's sign: its negative
-    assert b2.verify(vk, inst, bytes(flipped)) == 0
+    assert verdict(inst, bytes(flipped)) == 0

@@ -2,8 +2,8 @@
 (halo2curves' 32-byte GroupEncoding) and the record of the golden Blake2b proof."""
 import os
 
-import blake2b_ref as b2
 import field9_ref as ref
+import transcript_ref as b2
 
 Q = b2.Q
 GOLDEN_B2_N2 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "blake2b_n2.json")
@@ -27,7 +27,7 @@ def signed(x: int, sign: int) -> bytes:
 
 
 def edge_encodings() -> dict:
-    """name -> 32 bytes; what each decodes to is for blake2b_ref.decompress to say"""
+    """name -> 32 bytes; what each decodes to is for transcript_ref.decompress to say"""
     P = ref.ec_mul(5, ref.G)
     bit6 = bytearray(b2.compress(*P))
     bit6[31] |= 0x40
