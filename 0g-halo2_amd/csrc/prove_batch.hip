@@ -582,8 +582,9 @@ struct ProveBatch {
         if (st_fn != 0) {
             (void)prover_drain(p);
             p->in_flight = false;
-            for (uint32_t b = 0; b < nb; b++) proof_lens[b] = 0;
-            ZG_REQUIRE(false, ZG_ERR_INVALID_ARG, "zg_prover_prove_phased: the callback returned %d in phase %u", st_fn, ph);
+            for (uint32_t b = 0; b < ntr; b++) proof_lens[b] = 0;
+            ZG_REQUIRE(false, ZG_ERR_INVALID_ARG, "%s: the callback returned %d in phase %u",
+                       multi ? "zg_prover_prove_circuits_phased" : "zg_prover_prove_phased", st_fn, ph);
         }
         return ZG_OK;
     }
@@ -633,8 +634,9 @@ struct ProveBatch {
         std::vector<Fe>& vals = chal_vals;  // [nb][NC][2]: the value as the rows hold it, and as the coset slabs do
         vals.resize((size_t)nb * (NC ? NC : 1) * 2, fe_zero());
         for (uint32_t j : squeezed) {
+            Fe c{};
             for (uint32_t b = 0; b < nb; b++) {
-                const Fe c = tr[b].squeeze();
+                if (b < ntr) c = tr[b].squeeze();  // (multi: ONE squeeze, the same value in every circuit's row and column)
                 memcpy(&chal[(size_t)b * nch + j], &c, 32);
                 if (j < NC) {
                     vals[((size_t)b * NC + j) * 2] = c;
@@ -854,18 +856,29 @@ struct ProveBatch {
     int products_absorb_shuffles() {
         const uint32_t mb = S + NL;
         ZG_TRY(wait_points(p, (size_t)nb * (prod_per + NS), pts, W_PRODUCTS));
-        for (uint32_t b = 0; b < nb; b++) {
-            const Jac* q = &pts[(size_t)b * prod_per];
-            for (uint32_t i = 0; i < mb; i++) tr[b].write_point(q[i]);
-            if (!have_random) random_commit[b] = q[mb];
-            const Jac* qs = &pts[(size_t)nb * prod_per + (size_t)b * NS];
-            for (uint32_t j = 0; j < NS; j++) tr[b].write_point(qs[j]);
+        // (a proof per slot takes its three families in turn; the proof of several circuits takes each family as a pass over
+        //  the circuits, as upstream commits them)
+        auto family = [&](uint32_t b, uint32_t fam) {  // slot b's permutation z (0), lookup z (1) or shuffle z (2)
+            const Jac* q = fam < 2 ? &pts[(size_t)b * prod_per + (fam ? S : 0)] : &pts[(size_t)nb * prod_per + (size_t)b * NS];
+            const uint32_t cnt = fam == 0 ? S : fam == 1 ? NL : NS;
+            for (uint32_t i = 0; i < cnt; i++) T(b).write_point(q[i]);
+        };
+        if (multi) {
+            for (uint32_t fam = 0; fam < 3; fam++)
+                for (uint32_t b = 0; b < nb; b++) family(b, fam);
+        } else {
+            for (uint32_t b = 0; b < nb; b++)
+                for (uint32_t fam = 0; fam < 3; fam++) family(b, fam);
         }
+        for (uint32_t b = 0; b < nb && !have_random; b++) random_commit[b] = pts[(size_t)b * prod_per + mb];
         have_random = true;
+        for (uint32_t b = 0; b < ntr; b++) tr[b].write_point(random_commit[b]);  // (multi: ONE random polynomial, slot 0's, from key 0)
+        Fe y{};
         for (uint32_t b = 0; b < nb; b++) {
-            tr[b].write_point(random_commit[b]);
-            evalh_consts(p->hpc[b], tr[b].squeeze(), pk);
+            if (b < ntr) y = tr[b].squeeze();
+            evalh_consts(p->hpc[b], y, pk);
         }
+        if (multi) fold_weights(y);
         ZG_TICK("y");
         ZG_TRY(publish());
         lap(2);
@@ -873,10 +886,10 @@ struct ProveBatch {
     }
 
     // multi: the weights of the slots' quotients in the proof's.  upstream's evaluate_h carries its Horner value in y from
-    // one circuit into the next, so with m terms per circuit (gates, permutation, 5 per lookup) and h_c the quotient of
-    // circuit c alone, h = sum_c y^(m (N - 1 - c)) h_c: Horner in Y = y^m over the circuits, circuit 0 first.
+    // one circuit into the next, so with m terms per circuit (gates, permutation, 5 per lookup, 3 per shuffle) and h_c the
+    // quotient of circuit c alone, h = sum_c y^(m (N - 1 - c)) h_c: Horner in Y = y^m over the circuits, circuit 0 first.
     void fold_weights(const Fe& y) {
-        const uint32_t m = pk.dc.n_gates + (S ? 2 + (S - 1) + S : 0) + 5 * NL;
+        const uint32_t m = pk.dc.n_gates + (S ? 2 + (S - 1) + S : 0) + 5 * NL + 3 * NS;
         const Fe Y = Fr::pow_u64(y, m);
         Fe w = Fr::one();
         for (uint32_t c = nb; c-- > 0;) {
@@ -1426,23 +1439,32 @@ static int prove_batch_impl(zg_prover* p, size_t count, const zg_fr* const* advi
 }
 
 // create_proof for a `circuits` slice: ONE proof of `circuits` instances of the circuit (ProveBatch::multi).  One circuit is
-// the single-proof path, byte for byte.
-static int prove_multi_impl(zg_prover* p, size_t circuits, const zg_fr* const* advice_host, void* const* advice_dev,
-                            const zg_fr* const* instance, size_t instance_len, const uint8_t* keys /* [circuits][32] */, uint8_t* proof,
-                            size_t proof_cap, size_t* proof_len) {
-    ZG_REQUIRE(p && proof && proof_len && keys, ZG_ERR_INVALID_ARG, "zg_prover_prove_multi: null argument");
+// the single-proof path, byte for byte.  `who`: zg_prover_prove_multi, which keeps to circuits without challenges, later
+// phases and -- for more than one circuit -- shuffles (`general` = false), or zg_prover_prove_circuits*, which takes them
+// all; on a circuit that has none of the three the two are one path.
+static int prove_multi_impl(const char* who, bool general, zg_prover* p, size_t circuits, const zg_fr* const* advice_host,
+                            void* const* advice_dev, const zg_fr* const* instance, size_t instance_len,
+                            const uint8_t* keys /* [circuits][32] */, uint8_t* proof, size_t proof_cap, size_t* proof_len,
+                            zg_phase_fn phase_fn = nullptr, void* phase_user = nullptr) {
+    ZG_REQUIRE(p && proof && proof_len && keys, ZG_ERR_INVALID_ARG, "%s: null argument", who);
     *proof_len = 0;
-    ZG_TRY(batch_args_ok("zg_prover_prove_multi", "circuits", p, circuits, instance, instance_len));
-    ZG_REQUIRE(!p->phased(), ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not for a circuit with challenges or advice phases");
-    ZG_REQUIRE(circuits == 1 || p->pk->NS == 0, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: several circuits in one proof, not for a circuit with shuffles");
+    ZG_TRY(batch_args_ok(who, "circuits", p, circuits, instance, instance_len));
+    ZG_REQUIRE(general || !p->phased(), ZG_ERR_UNSUPPORTED, "%s: not for a circuit with challenges or advice phases (zg_prover_prove_circuits*)", who);
+    ZG_REQUIRE(general || circuits == 1 || p->pk->NS == 0, ZG_ERR_UNSUPPORTED,
+               "%s: several circuits in one proof, not for a circuit with shuffles (zg_prover_prove_circuits*)", who);
+    ZG_REQUIRE(phase_fn || p->n_phases == 1, ZG_ERR_INVALID_ARG,
+               "%s: the circuit has advice columns in %u phases, whose witness depends on challenges: use zg_prover_prove_circuits_phased", who,
+               p->n_phases);
     uint8_t* out[1] = {proof};
-    if (circuits == 1) return prove_batch_impl(p, 1, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr);
-    ZG_REQUIRE(p->world <= 1 && !p->rccl_comm, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: not on a point-range shard of the SRS");
-    ZG_REQUIRE(circuits <= FOLD_MAX_SLOTS, ZG_ERR_UNSUPPORTED, "zg_prover_prove_multi: %zu circuits in one proof (max %u)", circuits,
-               FOLD_MAX_SLOTS);
-    ZG_REQUIRE(p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG, "zg_prover_prove_multi: the base sets hold %u of %u points", p->shard_n, p->pk->n);
+    if (circuits == 1)
+        return prove_batch_impl(p, 1, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr, phase_fn, phase_user);
+    ZG_REQUIRE(p->world <= 1 && !p->rccl_comm, ZG_ERR_UNSUPPORTED, "%s: not on a point-range shard of the SRS", who);
+    ZG_REQUIRE(circuits <= FOLD_MAX_SLOTS, ZG_ERR_UNSUPPORTED, "%s: %zu circuits in one proof (max %u)", who, circuits, FOLD_MAX_SLOTS);
+    ZG_REQUIRE(p->shard_n == p->pk->n, ZG_ERR_INVALID_ARG, "%s: the base sets hold %u of %u points", who, p->shard_n, p->pk->n);
     ZG_ENTER(p->ctx);
     ProveBatch job(p, circuits, advice_host, advice_dev, instance, instance_len, keys, out, proof_cap, proof_len, nullptr, true);
+    job.phase_fn = phase_fn;
+    job.phase_user = phase_user;
     return job.run();  // (never gated: the gate is a lone proof's)
 }
 
@@ -1453,12 +1475,35 @@ size_t zg_prover_proof_size_multi(const zg_prover* p, size_t circuits) {
 
 int zg_prover_prove_multi(zg_prover* p, size_t circuits, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,
                           const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
-    return prove_multi_impl(p, circuits, advice, nullptr, instance, instance_len, rng_keys, proof, proof_cap, proof_len);
+    return prove_multi_impl("zg_prover_prove_multi", false, p, circuits, advice, nullptr, instance, instance_len, rng_keys, proof, proof_cap,
+                            proof_len);
 }
 
 int zg_prover_prove_multi_dev(zg_prover* p, size_t circuits, void* const* d_advice, const zg_fr* const* instance, size_t instance_len,
                               const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
-    return prove_multi_impl(p, circuits, nullptr, d_advice, instance, instance_len, rng_keys, proof, proof_cap, proof_len);
+    return prove_multi_impl("zg_prover_prove_multi", false, p, circuits, nullptr, d_advice, instance, instance_len, rng_keys, proof, proof_cap,
+                            proof_len);
+}
+
+// ... for every circuit the library proves: shuffles, challenges and advice phases included
+int zg_prover_prove_circuits(zg_prover* p, size_t circuits, const zg_fr* const* advice, const zg_fr* const* instance, size_t instance_len,
+                             const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    return prove_multi_impl("zg_prover_prove_circuits", true, p, circuits, advice, nullptr, instance, instance_len, rng_keys, proof, proof_cap,
+                            proof_len);
+}
+
+int zg_prover_prove_circuits_dev(zg_prover* p, size_t circuits, void* const* d_advice, const zg_fr* const* instance, size_t instance_len,
+                                 const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    return prove_multi_impl("zg_prover_prove_circuits", true, p, circuits, nullptr, d_advice, instance, instance_len, rng_keys, proof, proof_cap,
+                            proof_len);
+}
+
+int zg_prover_prove_circuits_phased(zg_prover* p, size_t circuits, zg_phase_fn fn, void* user, const zg_fr* const* instance,
+                                    size_t instance_len, const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+    ZG_REQUIRE(p && fn, ZG_ERR_INVALID_ARG, "zg_prover_prove_circuits_phased: null argument");
+    // (the slots hold the columns: the callback writes them, phase by phase)
+    return prove_multi_impl("zg_prover_prove_circuits_phased", true, p, circuits, nullptr, nullptr, instance, instance_len, rng_keys, proof,
+                            proof_cap, proof_len, fn, user);
 }
 
 int zg_prover_prove_batch(zg_prover* p, size_t count, const zg_fr* const* advice, const zg_fr* const* instance,

@@ -994,15 +994,19 @@ int zg_verifier_verify_batch(zg_verifier* v, size_t count, const uint8_t* const*
     return zg_verifier_verify_multi(v, count, 1, proofs, proof_lens, instance, instance_len, key, verdicts);
 }
 
-int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, const uint8_t* const* proofs, const size_t* proof_lens,
-                             const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
+// zg_verifier_verify_multi keeps to circuits without challenges, later phases and shuffles when a proof holds several
+// circuits (`general` = false); zg_verifier_verify_circuits is the same body without the two refusals
+static int verify_multi_impl(bool general, zg_verifier* v, size_t count, size_t circuits, const uint8_t* const* proofs,
+                             const size_t* proof_lens, const zg_fr* const* instance, size_t instance_len, const uint8_t key[32],
+                             int* verdicts) {
     ZG_REQUIRE(v && key && (count == 0 || (proofs && proof_lens && verdicts && (instance || v->a.I == 0))),
                ZG_ERR_INVALID_ARG, "zg_verifier_verify_batch: null argument");
     ZG_REQUIRE(circuits >= 1 && circuits <= 1024, ZG_ERR_INVALID_ARG, "zg_verifier_verify_multi: proofs of %zu circuits", circuits);
-    ZG_REQUIRE(circuits == 1 || !v->phased(), ZG_ERR_UNSUPPORTED,
-               "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with challenges or advice phases");
-    ZG_REQUIRE(circuits == 1 || v->a.NS == 0, ZG_ERR_UNSUPPORTED,
-               "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with shuffles");
+    ZG_REQUIRE(general || circuits == 1 || !v->phased(), ZG_ERR_UNSUPPORTED,
+               "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with challenges or advice phases "
+               "(zg_verifier_verify_circuits)");
+    ZG_REQUIRE(general || circuits == 1 || v->a.NS == 0, ZG_ERR_UNSUPPORTED,
+               "zg_verifier_verify_multi: proofs of several circuits are not verified for a circuit with shuffles (zg_verifier_verify_circuits)");
     ZG_REQUIRE(count < (1u << 24) && instance_len < (1u << 24), ZG_ERR_UNSUPPORTED,
                "zg_verifier_verify_batch: %zu proofs of %zu instance rows", count, instance_len);
     if (count == 0) return ZG_OK;
@@ -1114,6 +1118,16 @@ int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, cons
         }
     }
     return ZG_OK;
+}
+
+int zg_verifier_verify_multi(zg_verifier* v, size_t count, size_t circuits, const uint8_t* const* proofs, const size_t* proof_lens,
+                             const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
+    return verify_multi_impl(false, v, count, circuits, proofs, proof_lens, instance, instance_len, key, verdicts);
+}
+
+int zg_verifier_verify_circuits(zg_verifier* v, size_t count, size_t circuits, const uint8_t* const* proofs, const size_t* proof_lens,
+                                const zg_fr* const* instance, size_t instance_len, const uint8_t key[32], int* verdicts) {
+    return verify_multi_impl(true, v, count, circuits, proofs, proof_lens, instance, instance_len, key, verdicts);
 }
 
 }  // extern "C"

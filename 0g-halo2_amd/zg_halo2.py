@@ -92,6 +92,7 @@ ABI_SYMBOLS = [
     "zg_permutation_sigma", "zg_prover_export_key", "zg_params_lagrange", "zg_params_lagrange_dev", "zg_params_check",
     "zg_prover_proof_size_multi", "zg_prover_prove_multi", "zg_prover_prove_multi_dev", "zg_prover_prove_images_multi",
     "zg_verifier_verify_multi",
+    "zg_prover_prove_circuits", "zg_prover_prove_circuits_dev", "zg_prover_prove_circuits_phased", "zg_verifier_verify_circuits",
     "zg_wnn_create", "zg_wnn_destroy", "zg_wnn_predict", "zg_wnn_predict_dev", "zg_wnn_accuracy",
     "zg_prover_evaluate_h_dev", "zg_prover_lookup_compress_dev", "zg_permute_expression_pair_dev",
     "zg_permute_expression_pair", "zg_lookup_product_terms_dev", "zg_prover_permutation_sets",
@@ -964,7 +965,10 @@ class Prover:
         per proof, a dict {advice column: uint64[rows, 4]} of the columns of that phase, rows >= the usable rows; their
         usable rows are copied into the proof's slot before the call returns to the library (the blinding rows are the
         library's).  An exception, or a column outside 0 .. n_advice, aborts the batch (status -1).  Returns (proofs, status)."""
-        count = len(seeds)
+        return self.prove_phased_c(self._phase_callback(synthesize), instances, seeds, raise_on_error=raise_on_error)
+
+    def _phase_callback(self, synthesize):
+        """the zg_phase_fn of prove_phased / prove_circuits_phased around a Python `synthesize`"""
         n, hip = self.n, _hip_runtime()
         usable = n - (self.image.c.blinding_factors + 1)
         nch = len(self.phases[2])
@@ -991,7 +995,7 @@ class Prover:
                 traceback.print_exc()
                 return 1
 
-        return self.prove_phased_c(PHASE_FN(_cb), instances, seeds, raise_on_error=raise_on_error)
+        return PHASE_FN(_cb)
 
     @property
     def batch(self) -> int:
@@ -1113,8 +1117,12 @@ class Prover:
         """ONE proof of len(seeds) circuit instances (<= the prover's batch): one transcript, one h, one GWC opening.
         advice / instances / seeds per circuit, as prove_batch takes them (device=True: zg_prover_prove_multi_dev).
         A lookup failure in any circuit raises ZgError(ZG_ERR_CONSTRAINT)."""
-        count = len(seeds)
         lib = self.ctx.lib
+        return self._prove_one(lib.zg_prover_prove_multi_dev if device else lib.zg_prover_prove_multi, advice, instances, seeds, device)
+
+    def _prove_one(self, fn, advice, instances, seeds, device) -> bytes:
+        """the call of zg_prover_prove_multi* / zg_prover_prove_circuits*: one proof of len(seeds) circuits"""
+        count = len(seeds)
         keep = []
         if advice is None:
             adv_ptrs = None
@@ -1132,9 +1140,41 @@ class Prover:
         cap = max(self.proof_size_multi(count), 1)
         buf = (ctypes.c_uint8 * cap)()
         plen = c_size_t(0)
-        fn = lib.zg_prover_prove_multi_dev if device else lib.zg_prover_prove_multi
         _check(fn(self.h, c_size_t(count), adv_ptrs, inst_ptrs, c_size_t(inst_len), keys, buf, c_size_t(cap), ctypes.byref(plen)))
         return bytes(buf[: plen.value])
+
+    def prove_circuits(self, advice, instances, seeds, device=False) -> bytes:
+        """zg_prover_prove_circuits / _dev: prove_multi for every circuit the library proves -- shuffles, challenges (every
+        advice column in phase 0) and, through prove_circuits_phased, advice phases.  The same arguments."""
+        lib = self.ctx.lib
+        return self._prove_one(lib.zg_prover_prove_circuits_dev if device else lib.zg_prover_prove_circuits, advice, instances, seeds, device)
+
+    def prove_circuits_phased_c(self, fn_ptr, instances, seeds, user: int = 0, raise_on_error=True):
+        """zg_prover_prove_circuits_phased with a zg_phase_fn given as a PHASE_FN object or the address of a C function."""
+        count = len(seeds)
+        insts, inst_len = [], 0
+        for b in range(count):
+            i, inst_len = self._inst(instances[b])
+            insts.append(i)
+        inst_ptrs = (c_void_p * max(count, 1))(*[c_void_p(i.ctypes.data) for i in insts])
+        keys = b"".join(rng_key(s) for s in seeds)
+        cap = max(self.proof_size_multi(count), 1)
+        buf = (ctypes.c_uint8 * cap)()
+        plen = c_size_t(0)
+        fn = fn_ptr if isinstance(fn_ptr, PHASE_FN) else ctypes.cast(fn_ptr, PHASE_FN)
+        call = self.ctx.lib.zg_prover_prove_circuits_phased
+        call.argtypes = [c_void_p, c_size_t, PHASE_FN, c_void_p, c_void_p, c_size_t, ctypes.c_char_p, c_void_p, c_size_t, c_void_p]
+        st = call(self.h, c_size_t(count), fn, c_void_p(user), inst_ptrs, c_size_t(inst_len), keys, buf, c_size_t(cap), ctypes.byref(plen))
+        if st != 0 and raise_on_error:
+            _check(st)
+        return bytes(buf[: plen.value]), st
+
+    def prove_circuits_phased(self, synthesize, instances, seeds, raise_on_error=True):
+        """zg_prover_prove_circuits_phased with the witness made by a Python function, prove_phased's convention:
+        synthesize(phase, challenges) is called once per phase with challenges uint64[circuits, n_challenges, 4] -- every row
+        the same values, the proof has one transcript -- and returns, per circuit, a dict {advice column: uint64[rows, 4]}.
+        Returns (proof, status); an exception in the callback gives (b"", -1)."""
+        return self.prove_circuits_phased_c(self._phase_callback(synthesize), instances, seeds, raise_on_error=raise_on_error)
 
     def prove_multi_dev(self, d_advice, instances, seeds) -> bytes:
         """prove_multi with the advice columns in HBM (device addresses, or None = the slots as they stand)."""
@@ -1467,6 +1507,14 @@ class Verifier:
     def verify_multi(self, proofs, instances, key, circuits: int) -> list:
         """verify for proofs of `circuits` instances each (Prover.prove_multi): instances[b] = the list of proof b's
         per-circuit instance arrays.  Verdicts as verify."""
+        return self._verify_several(self.ctx.lib.zg_verifier_verify_multi, proofs, instances, key, circuits)
+
+    def verify_circuits(self, proofs, instances, key, circuits: int) -> list:
+        """zg_verifier_verify_circuits: verify_multi for the proofs of Prover.prove_circuits* -- circuits with shuffles,
+        challenges and advice phases included."""
+        return self._verify_several(self.ctx.lib.zg_verifier_verify_circuits, proofs, instances, key, circuits)
+
+    def _verify_several(self, fn, proofs, instances, key, circuits: int) -> list:
         count = len(proofs)
         bufs = [bytes(p) for p in proofs]
         pptrs = (ctypes.c_char_p * count)(*bufs)
@@ -1479,8 +1527,7 @@ class Verifier:
                 insts.append(i)
         iptrs = (c_void_p * max(len(insts), 1))(*[c_void_p(i.ctypes.data) for i in insts])
         verdicts = (c_int * count)()
-        _check(self.ctx.lib.zg_verifier_verify_multi(self.h, c_size_t(count), c_size_t(circuits), pptrs, lens, iptrs,
-                                                     c_size_t(inst_len), rng_key(key), verdicts))
+        _check(fn(self.h, c_size_t(count), c_size_t(circuits), pptrs, lens, iptrs, c_size_t(inst_len), rng_key(key), verdicts))
         return list(verdicts)
 
     def close(self):

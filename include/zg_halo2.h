@@ -531,7 +531,8 @@ int zg_prover_create_shared(zg_ctx *ctx, const zg_circuit *circuit, const zg_fr 
  * A prover with shuffles makes single proofs and lock-step batches (zg_prover_prove, _dev, _batch, _batch_dev, _phased);
  * zg_prover_prove_multi* of several circuits, zg_prover_prove_images*, zg_prover_check_batch, _batch_dev and _images (a
  * witness of such a circuit is checked by zg_prover_check_circuit*), a point-range shard and the arithmetic-level entries
- * that take the whole circuit (zg_prover_evaluate_h*) answer ZG_ERR_UNSUPPORTED. */
+ * that take the whole circuit (zg_prover_evaluate_h*) answer ZG_ERR_UNSUPPORTED.  One proof of several such circuits is
+ * made by zg_prover_prove_circuits* and verified by zg_verifier_verify_circuits. */
 int zg_prover_create_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
                               const zg_fr *fixed_values, const zg_fr *sigma_values, const zg_g1_affine *g,
                               const zg_g1_affine *g_lagrange, const zg_fr *vk_repr, zg_prover **out);
@@ -604,6 +605,38 @@ int zg_prover_prove_multi(zg_prover *p, size_t circuits, const zg_fr *const *adv
 int zg_prover_prove_multi_dev(zg_prover *p, size_t circuits, void *const *d_advice, const zg_fr *const *instance,
                               size_t instance_len, const uint8_t *rng_keys, uint8_t *proof, size_t proof_cap,
                               size_t *proof_len);
+/* The general form of zg_prover_prove_multi / _dev: ONE proof of `circuits` instances of ANY circuit the library proves,
+ * those with shuffle arguments, challenges and advice phases included.  Arguments, keys, limits
+ * and statuses are zg_prover_prove_multi's: 1 <= circuits <= zg_prover_batch(p) else ZG_ERR_INVALID_ARG; more than 64
+ * circuits or a point-range shard ZG_ERR_UNSUPPORTED; a lookup failure in any circuit ZG_ERR_CONSTRAINT with
+ * *proof_len = 0.  zg_prover_proof_size_multi is the bound for these entries too: it is computed from the circuit's shape,
+ * which counts the shuffle arguments, and the phases change no length.  On a circuit without shuffles, challenges and
+ * later phases the entries ARE zg_prover_prove_multi / _dev (the same bytes, the same kernel launches); circuits = 1 is
+ * zg_prover_prove / zg_prover_prove_phased, byte for byte.
+ *
+ * The proof, with N = circuits: the vk scalar and every circuit's instance scalars; per phase in ascending order every
+ * circuit's advice commitments of that phase (circuit after circuit, ascending column) and then ONE squeeze per challenge
+ * of that phase, theta behind the last phase; every circuit's permuted columns, beta, gamma; every circuit's permutation
+ * products, then every circuit's lookup products, then every circuit's shuffle products, the random polynomial once, y;
+ * the pieces of h once, x; the evaluations in zg_prover_prove_multi's order with every circuit's z_j(x), z_j(omega x) behind
+ * every circuit's lookup evaluations; the opening queries circuit after circuit (advice, permutation, lookups, shuffles),
+ * then fixed, sigmas, h, random; either multi-open tail.  h = sum_c y^(m (N - 1 - c)) h_c with m = gates + permutation
+ * terms + 5 per lookup + 3 per shuffle.  Circuit c draws every blinding row -- advice, permuted columns, every product,
+ * the shuffle products under their own tag -- from key c with the tags and indices of the single proof; the random
+ * polynomial comes from key 0.  A witness that is no shuffle still gives ZG_OK and a proof of full length that no
+ * verifier accepts.
+ *
+ * The plain forms take a circuit with challenges while every advice column is in phase 0 and return ZG_ERR_INVALID_ARG
+ * otherwise (use zg_prover_prove_circuits_phased), as the single-proof entries do.  _phased: fn is called once per phase
+ * with count = circuits, d_advice[c] the slot of circuit c and challenges [circuits][n_challenges], every row the same
+ * values (one transcript); the rest is zg_prover_prove_phased's contract -- a non-zero return gives ZG_ERR_INVALID_ARG,
+ * *proof_len = 0, the queue drained and the prover usable. */
+int zg_prover_prove_circuits(zg_prover *p, size_t circuits, const zg_fr *const *advice, const zg_fr *const *instance,
+                             size_t instance_len, const uint8_t *rng_keys, uint8_t *proof, size_t proof_cap,
+                             size_t *proof_len);
+int zg_prover_prove_circuits_dev(zg_prover *p, size_t circuits, void *const *d_advice, const zg_fr *const *instance,
+                                 size_t instance_len, const uint8_t *rng_keys, uint8_t *proof, size_t proof_cap,
+                                 size_t *proof_len);
 /* One proof (the batch of one).  advice: [n_advice][2^k] column values (host).  instance: [n_instance][instance_len]
  * public inputs.  proof: receives the transcript bytes (EvmTranscript layout). */
 int zg_prover_prove(zg_prover *p, const zg_fr *advice, const zg_fr *instance, size_t instance_len,
@@ -641,7 +674,8 @@ int zg_prover_prove_dev(zg_prover *p, void *d_advice, const zg_fr *instance, siz
  * zg_prover_prove_phased); zg_prover_prove_multi*, zg_prover_prove_images*, zg_prover_check_batch, _batch_dev and _images
  * (a witness of such a circuit is checked by zg_prover_check_circuit*, with the caller's challenge values),
  * zg_verifier_verify_multi with more than one circuit and a point-range shard are ZG_ERR_UNSUPPORTED; the ZG_LAT_GATE
- * gate stays off. */
+ * gate stays off.  One proof of several such circuits is made by zg_prover_prove_circuits* and verified by
+ * zg_verifier_verify_circuits. */
 int zg_prover_set_phases(zg_prover *p, const uint8_t *advice_phase, uint32_t n_challenges, const uint8_t *challenge_phase);
 int zg_prover_phases(const zg_prover *p, uint8_t *advice_phase, uint32_t *n_challenges, uint8_t *challenge_phase);
 /* create_proof's phase loop for a batch of `count` proofs whose witness is synthesised phase by phase.  The library
@@ -658,6 +692,11 @@ int zg_prover_phases(const zg_prover *p, uint8_t *advice_phase, uint32_t *n_chal
 typedef int (*zg_phase_fn)(void *user, uint32_t phase, size_t count, const zg_fr *challenges, void *const *d_advice);
 int zg_prover_prove_phased(zg_prover *p, size_t count, zg_phase_fn fn, void *user, const zg_fr *const *instance,
                            size_t instance_len, const uint8_t *rng_keys, uint8_t *const *proofs, size_t *proof_lens);
+/* ... for ONE proof of `circuits` instances: zg_prover_prove_circuits with the witness synthesised phase by phase (the
+ * contract stands at zg_prover_prove_circuits).  proof must hold zg_prover_proof_size_multi(p, circuits) bytes. */
+int zg_prover_prove_circuits_phased(zg_prover *p, size_t circuits, zg_phase_fn fn, void *user, const zg_fr *const *instance,
+                                    size_t instance_len, const uint8_t *rng_keys, uint8_t *proof, size_t proof_cap,
+                                    size_t *proof_len);
 
 /* Point-range shard of the commitments across `world` GPUs (one process and one prover per GPU):
  * this prover's base sets hold points [first_point, first_point + zg_bases_len) of ParamsKZG::g / ::g_lagrange, it
@@ -1027,7 +1066,7 @@ int zg_verifier_create(zg_ctx *ctx, const zg_circuit *circuit, const zg_g1_affin
  * shuffle products behind the lookup products and their evaluations behind the lookups', the expected h(x) takes the
  * three terms per shuffle behind the lookup terms and the opening check the two queries per shuffle.  The shuffles are
  * validated as zg_prover_create_shuffles validates them, circuit->cs_degree included.  zg_verifier_verify_multi
- * of several circuits answers ZG_ERR_UNSUPPORTED for such a verifier. */
+ * of several circuits answers ZG_ERR_UNSUPPORTED for such a verifier; zg_verifier_verify_circuits verifies such proofs. */
 int zg_verifier_create_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
                                 const zg_g1_affine *fixed_commitments, const zg_g1_affine *sigma_commitments,
                                 const zg_g1_affine *g0, const zg_g2_affine *g2, const zg_g2_affine *s_g2, const zg_fr *vk_repr,
@@ -1048,6 +1087,13 @@ int zg_verifier_verify_batch(zg_verifier *v, size_t count, const uint8_t *const 
 int zg_verifier_verify_multi(zg_verifier *v, size_t count, size_t circuits, const uint8_t *const *proofs,
                              const size_t *proof_lens, const zg_fr *const *instance, size_t instance_len,
                              const uint8_t key[32], int *verdicts);
+/* zg_verifier_verify_multi for the proofs of zg_prover_prove_circuits*: the same arguments, verdict classes, weights and
+ * bisection, for every circuit the verifier was created for -- shuffle arguments, challenges and advice phases included
+ * (zg_verifier_create_shuffles, zg_verifier_set_phases; the proof's order: zg_prover_prove_circuits).  On a circuit without
+ * them it IS zg_verifier_verify_multi; circuits = 1 is zg_verifier_verify_batch. */
+int zg_verifier_verify_circuits(zg_verifier *v, size_t count, size_t circuits, const uint8_t *const *proofs,
+                                const size_t *proof_lens, const zg_fr *const *instance, size_t instance_len,
+                                const uint8_t key[32], int *verdicts);
 /* Which multi-open argument the proofs handed to zg_verifier_verify_batch / _multi end with (ZG_MULTIOPEN_*, default GWC;
  * VerifierSHPLONK: DESIGN.md section 16).  Verdict classes are the same: a point of the tail that is off the curve, at
  * infinity or not canonical gives a negative verdict, trailing bytes or a failing equation 0.  Query tables are built per
@@ -1069,7 +1115,7 @@ int zg_verifier_transcript(const zg_verifier *v);
  * getter.  The transcript walk reads each phase's advice commitments, then squeezes that phase's challenges, and the
  * expected h(x) takes a ZG_CHALLENGE query from them.  A verifier without the call reads every advice commitment before
  * the challenges, so it rejects a proof made in several phases.  zg_verifier_verify_multi with more than one circuit is
- * ZG_ERR_UNSUPPORTED for a circuit with a challenge or a phase > 0. */
+ * ZG_ERR_UNSUPPORTED for a circuit with a challenge or a phase > 0; zg_verifier_verify_circuits verifies such proofs. */
 int zg_verifier_set_phases(zg_verifier *v, const uint8_t *advice_phase, uint32_t n_challenges, const uint8_t *challenge_phase);
 int zg_verifier_phases(const zg_verifier *v, uint8_t *advice_phase, uint32_t *n_challenges, uint8_t *challenge_phase);
 /* Host helper (no device): *result = 1 iff prod_i e(p[i], q[i]) = 1 in GT (BN254 optimal ate pairing); identity

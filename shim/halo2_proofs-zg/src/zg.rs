@@ -414,7 +414,7 @@ where
         return None;
     }
     if circuits.len() > 1 {
-        // several circuits behind one transcript: zg_prover_prove_multi (UNVERIFIED source like the rest of this file)
+        // several circuits behind one transcript: zg_prover_prove_circuits (UNVERIFIED source like the rest of this file)
         return try_create_proof_multi::<Scheme, E, R, T, ConcreteCircuit>(params, pk, circuits, instances, rng, transcript);
     }
     if TypeId::of::<Scheme>() != TypeId::of::<KZGCommitmentScheme<Bn256>>() {
@@ -477,8 +477,9 @@ where
     })())
 }
 
-/// `create_proof` for `circuits.len() > 1`: one proof of all the instances (`zg_prover_prove_multi`).  A handle of its own
-/// (slot count, throughput form), one 32-byte blinding key per circuit from the caller's RNG.
+/// `create_proof` for `circuits.len() > 1`: one proof of all the instances (`zg_prover_prove_circuits`, the general form of
+/// `zg_prover_prove_multi`: on the circuits `flatten` lets through -- no challenge, one phase -- the two are one path).  A
+/// handle of its own (slot count, throughput form), one 32-byte blinding key per circuit from the caller's RNG.
 fn try_create_proof_multi<'params, Scheme, E, R, T, ConcreteCircuit>(
     params: &'params Scheme::ParamsProver,
     pk: &ProvingKey<Scheme::Curve>,
@@ -541,8 +542,8 @@ where
         let mut buf = vec![0u8; cap];
         let mut len = 0usize;
         check(unsafe {
-            zg_prover_prove_multi(h.prover, count, adv_ptrs.as_ptr(), inst_ptrs.as_ptr(), inst_len, keys.as_ptr(), buf.as_mut_ptr(),
-                                  buf.len(), &mut len)
+            zg_prover_prove_circuits(h.prover, count, adv_ptrs.as_ptr(), inst_ptrs.as_ptr(), inst_len, keys.as_ptr(), buf.as_mut_ptr(),
+                                     buf.len(), &mut len)
         })?;
         replay::<Scheme::Curve, E, T>(cs, count, &buf[..len], transcript).map_err(Error::from)
     })())
