@@ -105,6 +105,8 @@ ABI_SYMBOLS = [
     "zg_g1_compress", "zg_g1_decompress", "zg_g1_decompress_dev",
     "zg_prover_set_phases", "zg_prover_phases", "zg_prover_prove_phased", "zg_verifier_set_phases", "zg_verifier_phases",
     "zg_prover_create_shuffles", "zg_prover_create_shared_shuffles", "zg_prover_shuffles", "zg_verifier_create_shuffles",
+    "zg_witness_plan_create_field", "zg_witness_run_field_dev", "zg_prover_prove_inputs", "zg_prover_prove_inputs_circuits",
+    "zg_prover_check_inputs",
 ]
 
 # zg_shuffle (include/zg_halo2.h): halo2's shuffle argument, the layout of zg_lookup
@@ -803,11 +805,22 @@ class WitnessPlan:
         self.n_instance = int(inst.shape[0])
         self.image_bytes = int(arrays["image_bytes"])
         h = c_void_p()
-        _check(lib.zg_witness_plan_create(ctx.h, _ptr(ops), c_size_t(ops.shape[0]), _ptr(level_start),
-                                          c_size_t(level_start.shape[0] - 1), _ptr(consts), c_size_t(consts.shape[0]),
-                                          _ptr(table), c_size_t(table.shape[0]), _ptr(cell_slot), c_uint32(self.n_advice),
-                                          c_uint32(self.k), _ptr(inst), c_size_t(self.n_instance),
-                                          c_size_t(self.image_bytes), ctypes.byref(h)))
+        args = [ctx.h, _ptr(ops), c_size_t(ops.shape[0]), _ptr(level_start), c_size_t(level_start.shape[0] - 1), _ptr(consts),
+                c_size_t(consts.shape[0]), _ptr(table), c_size_t(table.shape[0]), _ptr(cell_slot), c_uint32(self.n_advice),
+                c_uint32(self.k), _ptr(inst), c_size_t(self.n_instance), c_size_t(self.image_bytes)]
+        self.n_challenges = 0
+        if "phase_level_start" in arrays:
+            # zg_witness_plan_create_field: field operations, challenges, advice phases
+            pls = np.ascontiguousarray(arrays["phase_level_start"], dtype=np.uint32)
+            adv = np.ascontiguousarray(arrays["advice_phase"], dtype=np.uint8)
+            chal = np.ascontiguousarray(arrays.get("challenge_phase", []), dtype=np.uint8)
+            if adv.size != self.n_advice:
+                raise ValueError(f"{adv.size} advice phases for {self.n_advice} advice columns")
+            self.n_challenges = int(chal.size)
+            _check(lib.zg_witness_plan_create_field(*args, _ptr(pls), c_uint32(pls.size - 1), _ptr(adv), c_uint32(chal.size),
+                                                    _ptr(chal) if chal.size else None, ctypes.byref(h)))
+        else:
+            _check(lib.zg_witness_plan_create(*args, ctypes.byref(h)))
         self.h = h
         ctx._adopt(self)
 
@@ -828,6 +841,23 @@ class WitnessPlan:
         ptrs = (c_void_p * count)(*[c_void_p(a) for a in d_advice])
         out = np.zeros((count, self.n_instance, 4), np.uint64)
         _check(self.ctx.lib.zg_witness_run_dev(self.h, _ptr(images), c_size_t(count), ptrs, _ptr(out)))
+        return out
+
+    def run_field(self, inputs: np.ndarray, d_advice, challenges=None) -> np.ndarray:
+        """zg_witness_run_field_dev: run() for a plan with challenges -- every phase for the caller's challenge values,
+        uint64[count, n_challenges, 4] (Montgomery limbs; None for a plan without challenges).  Returns the instance values."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint8).reshape(len(d_advice), -1)
+        assert inputs.shape[1] == self.image_bytes, "input size does not match the recorded program"
+        count = inputs.shape[0]
+        chal = None
+        if challenges is not None:
+            chal = np.ascontiguousarray(challenges, dtype=np.uint64)
+            if chal.shape != (count, self.n_challenges, 4):
+                raise ValueError(f"challenges of shape {chal.shape} for {count} inputs of {self.n_challenges} challenges")
+        ptrs = (c_void_p * count)(*[c_void_p(a) for a in d_advice])
+        out = np.zeros((count, self.n_instance, 4), np.uint64)
+        _check(self.ctx.lib.zg_witness_run_field_dev(self.h, _ptr(inputs), c_size_t(count), _ptr(chal) if chal is not None and chal.size else None,
+                                                     ptrs, _ptr(out)))
         return out
 
     def close(self):
@@ -1104,6 +1134,57 @@ class Prover:
         if st != 0 and raise_on_error:
             _check(st)
         return [bytes(bufs[b][: lens[b]]) for b in range(count)], outputs, list(sts)
+
+    def prove_inputs(self, plan: "WitnessPlan", inputs: np.ndarray, seeds, raise_on_error=True):
+        """zg_prover_prove_inputs: prove_images for every circuit the library proves -- input bytes -> (proofs, outputs
+        uint64[count, n_instance, 4], statuses); a circuit with advice phases has its later phases replayed by the plan
+        with the challenges the proof squeezes.  The plan's phases must be the prover's."""
+        count = len(seeds)
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint8).reshape(count, -1)
+        keys = b"".join(rng_key(s) for s in seeds)
+        bufs = [(ctypes.c_uint8 * self.proof_cap)() for _ in range(count)]
+        out_ptrs = (c_void_p * count)(*[ctypes.addressof(b) for b in bufs])
+        lens = (c_size_t * count)()
+        sts = (c_int * count)()
+        outputs = np.zeros((count, plan.n_instance, 4), np.uint64)
+        st = self.ctx.lib.zg_prover_prove_inputs(self.h, plan.h, _ptr(inputs), c_size_t(count), keys, out_ptrs,
+                                                 c_size_t(self.proof_cap), lens, _ptr(outputs), sts)
+        if st != 0 and raise_on_error:
+            _check(st)
+        return [bytes(bufs[b][: lens[b]]) for b in range(count)], outputs, list(sts)
+
+    def prove_inputs_circuits(self, plan: "WitnessPlan", inputs: np.ndarray, seeds):
+        """zg_prover_prove_inputs_circuits: len(seeds) inputs in ONE proof (prove_circuits / prove_circuits_phased with the
+        plan as the witness): input bytes -> (proof, outputs uint64[circuits, n_instance, 4])."""
+        count = len(seeds)
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint8).reshape(max(count, 1), -1)
+        keys = b"".join(rng_key(s) for s in seeds)
+        cap = max(self.proof_size_multi(count), 1)
+        buf = (ctypes.c_uint8 * cap)()
+        plen = c_size_t(0)
+        outputs = np.zeros((max(count, 1), plan.n_instance, 4), np.uint64)
+        _check(self.ctx.lib.zg_prover_prove_inputs_circuits(self.h, plan.h, _ptr(inputs), c_size_t(count), keys, buf, c_size_t(cap),
+                                                            ctypes.byref(plen), _ptr(outputs)))
+        return bytes(buf[: plen.value]), outputs
+
+    def check_inputs(self, plan: "WitnessPlan", inputs: np.ndarray, challenges=None, cap: int = 64):
+        """zg_prover_check_inputs: input bytes -> (reports as check_circuit, outputs uint64[count, n_instance, 4]); the
+        witness is the plan's for the caller's challenges, uint64[count, n_challenges, 4] (None without challenges)."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint8)
+        count = inputs.shape[0]
+        inputs = inputs.reshape(count, -1)
+        chal = None
+        if challenges is not None:
+            chal = np.ascontiguousarray(challenges, dtype=np.uint64)
+            if chal.shape != (count, plan.n_challenges, 4):
+                raise ValueError(f"challenges of shape {chal.shape} for {count} inputs of {plan.n_challenges} challenges")
+        outputs = np.zeros((count, plan.n_instance, 4), np.uint64)
+        recs = (Failure * max(1, count * cap))()
+        totals = (c_uint32 * (4 * count))()
+        _check(self.ctx.lib.zg_prover_check_inputs(self.h, plan.h, _ptr(inputs), c_size_t(count),
+                                                   _ptr(chal) if chal is not None and chal.size else None, _ptr(outputs),
+                                                   recs if cap else None, c_size_t(cap), totals))
+        return self._reports(count, cap, recs, totals, 4), outputs
 
     # ---- one proof of several circuit instances (create_proof's `circuits` slice)
     def proof_size_multi(self, circuits: int) -> int:

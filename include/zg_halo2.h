@@ -532,7 +532,8 @@ int zg_prover_create_shared(zg_ctx *ctx, const zg_circuit *circuit, const zg_fr 
  * zg_prover_prove_multi* of several circuits, zg_prover_prove_images*, zg_prover_check_batch, _batch_dev and _images (a
  * witness of such a circuit is checked by zg_prover_check_circuit*), a point-range shard and the arithmetic-level entries
  * that take the whole circuit (zg_prover_evaluate_h*) answer ZG_ERR_UNSUPPORTED.  One proof of several such circuits is
- * made by zg_prover_prove_circuits* and verified by zg_verifier_verify_circuits. */
+ * made by zg_prover_prove_circuits* and verified by zg_verifier_verify_circuits; input -> proof and input -> check go
+ * through zg_prover_prove_inputs* and zg_prover_check_inputs. */
 int zg_prover_create_shuffles(zg_ctx *ctx, const zg_circuit *circuit, const zg_shuffle *shuffles, uint32_t n_shuffles,
                               const zg_fr *fixed_values, const zg_fr *sigma_values, const zg_g1_affine *g,
                               const zg_g1_affine *g_lagrange, const zg_fr *vk_repr, zg_prover **out);
@@ -675,7 +676,8 @@ int zg_prover_prove_dev(zg_prover *p, void *d_advice, const zg_fr *instance, siz
  * (a witness of such a circuit is checked by zg_prover_check_circuit*, with the caller's challenge values),
  * zg_verifier_verify_multi with more than one circuit and a point-range shard are ZG_ERR_UNSUPPORTED; the ZG_LAT_GATE
  * gate stays off.  One proof of several such circuits is made by zg_prover_prove_circuits* and verified by
- * zg_verifier_verify_circuits. */
+ * zg_verifier_verify_circuits; a witness program with field operations and phases (zg_witness_plan_create_field) goes from
+ * input bytes to such proofs through zg_prover_prove_inputs*, and to the check through zg_prover_check_inputs. */
 int zg_prover_set_phases(zg_prover *p, const uint8_t *advice_phase, uint32_t n_challenges, const uint8_t *challenge_phase);
 int zg_prover_phases(const zg_prover *p, uint8_t *advice_phase, uint32_t *n_challenges, uint8_t *challenge_phase);
 /* create_proof's phase loop for a batch of `count` proofs whose witness is synthesised phase by phase.  The library
@@ -961,6 +963,62 @@ int zg_prover_prove_images(zg_prover* p, zg_witness_plan* plan, const uint8_t* i
 int zg_prover_prove_images_multi(zg_prover* p, zg_witness_plan* plan, const uint8_t* images, size_t circuits,
                                  const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len, zg_fr* outputs);
 
+/* ---- the witness program with field arithmetic, challenges and advice phases ---------------
+ * What a circuit with challenges or advice phases otherwise synthesises through a zg_phase_fn on the host: a product
+ * modulo r, an inverse, a running random linear combination, a shuffle's grand product.  Five more operations; with r
+ * the BN254 scalar modulus, operands are slots holding ANY 256-bit integer and the result is the canonical
+ * representative in [0, r) -- exactly (a mod r) * (b mod r) mod r and so on, as integers:
+ *
+ *   op  17 CHAL  challenge imm of this input, as its canonical integer      18 ADDM (a+b) mod r     19 SUBM (a-b) mod r
+ *       20 MULM (a*b) mod r     21 INVM a^-1 mod r, and 0 when a = 0 (mod r): what Assigned::invert / evaluate yields
+ *
+ * Slots stay integers, so integer and field operations mix freely.  phase_level_start [n_phases + 1]: the levels of
+ * phase ph are [phase_level_start[ph], phase_level_start[ph + 1]), contiguous from level 0, 1 <= n_phases <=
+ * ZG_MAX_PHASES; a slot's phase is its level's.  advice_phase [n_advice], n_challenges <= ZG_MAX_CHALLENGES and
+ * challenge_phase [n_challenges]: as zg_prover_set_phases takes them.  Checked here, before anything is uploaded, and
+ * ZG_ERR_INVALID_ARG with a message beside zg_witness_plan_create's own refusals: an unknown opcode; CHAL with imm >=
+ * n_challenges or in a phase <= challenge_phase[imm] (the value does not exist yet); a cell of column c showing a slot of
+ * a phase > advice_phase[c]; an instance slot outside phase 0 (the instances are hashed before any challenge exists);
+ * phase bounds that do not ascend or do not cover the levels; a phase >= n_phases in either phase array.
+ *
+ * A plan without a field operation, in one phase, is zg_witness_plan_create's: the same layout, the same kernels.  Any
+ * other plan takes the field form: one launch per phase over that phase's levels, the slots of a batch in a buffer the
+ * plan owns so that a later phase reads what an earlier one made.  The LDS allocation, its spill path and ZG_WITNESS_LDS
+ * apply as they do to any plan, phase by phase: a field result counts as "may exceed 64 bits" (range [0, r - 1]), a value
+ * holds its cell up to its last consumer of its own phase, and a slot of an earlier phase is an operand in HBM
+ * (zg_witness_plan_info counts the levels that read one among those whose barrier waits for HBM).  One call at a time
+ * per plan.
+ * zg_witness_plan_create itself is unchanged and keeps refusing opcodes above 16. */
+int zg_witness_plan_create_field(zg_ctx* ctx, const zg_witness_op* ops, size_t n_ops, const uint32_t* level_start, size_t n_levels,
+                                 const uint64_t* consts, size_t n_consts, const uint64_t* table, size_t n_table,
+                                 const uint32_t* cell_slot, uint32_t n_advice, uint32_t k, const uint32_t* instance_slots,
+                                 size_t n_instance, size_t image_bytes, const uint32_t* phase_level_start, uint32_t n_phases,
+                                 const uint8_t* advice_phase, uint32_t n_challenges, const uint8_t* challenge_phase,
+                                 zg_witness_plan** out);
+/* The whole witness, every phase, for GIVEN challenge values: zg_witness_run_dev's arguments and limits plus challenges,
+ * host, [count][n_challenges], Montgomery form, the caller's values -- NULL if and only if the plan has none.  Whole
+ * columns are written (unassigned cells zero).  zg_witness_run_dev takes a field-form plan too while it has no challenge. */
+int zg_witness_run_field_dev(zg_witness_plan* plan, const uint8_t* inputs, size_t count, const zg_fr* challenges,
+                             void* const* d_advice, zg_fr* instance_out);
+/* input -> proof for EVERY circuit the library proves: the general form of zg_prover_prove_images.  Phase 0 of the
+ * program goes into slots 0..count-1 and its instance values come out (outputs, [count][n_instance]); the proofs ride
+ * on zg_prover_prove_batch_dev for a one-phase circuit and on zg_prover_prove_phased otherwise, with a phase callback of
+ * the library's own that replays the plan's slice of each phase with the challenges it is handed and writes the usable
+ * rows of that phase's columns.  Shuffles, both multi-open schemes, both transcripts, both scheduling forms and forks
+ * work because the rides do.  Limits are zg_prover_prove_images': 64 inputs per call, count <= zg_prover_batch(p), plan and
+ * prover on one device, the same k and column count, at most one instance column.  Besides, the plan's phases,
+ * advice_phase, n_challenges and challenge_phase must EQUAL what zg_prover_phases(p) reports: ZG_ERR_INVALID_ARG
+ * otherwise, nothing written, the prover usable.  With advice phases proof_cap must be at least zg_prover_proof_size(p)
+ * (ZG_ERR_INVALID_ARG) and statuses[b] is ZG_OK for a proof that has bytes, the call's status (ZG_ERR_CONSTRAINT for a
+ * failed lookup) for one that has none.  A point-range shard of a circuit with shuffles, challenges or phases:
+ * ZG_ERR_UNSUPPORTED.  On a plan and circuit zg_prover_prove_images accepts: its bytes from its launches. */
+int zg_prover_prove_inputs(zg_prover* p, zg_witness_plan* plan, const uint8_t* inputs, size_t count, const uint8_t* rng_keys,
+                           uint8_t* const* proofs, size_t proof_cap, size_t* proof_lens, zg_fr* outputs, int* statuses);
+/* ... into ONE proof of `circuits` inputs, on zg_prover_prove_circuits_dev / _phased: one squeeze per challenge, the same
+ * value into every input's program.  proof must hold zg_prover_proof_size_multi(p, circuits) bytes. */
+int zg_prover_prove_inputs_circuits(zg_prover* p, zg_witness_plan* plan, const uint8_t* inputs, size_t circuits,
+                                    const uint8_t* rng_keys, uint8_t* proof, size_t proof_cap, size_t* proof_len, zg_fr* outputs);
+
 /* ------------------------------------------------------------------ witness check
  * Replaces halo2_proofs::dev::MockProver::run followed by MockProver::verify / assert_satisfied (halo2_proofs
  * v2023_04_20 src/dev.rs), as Wnn::mock_proof calls them (/root/reference/src/wnn.rs:203-210), for a batch of
@@ -1031,6 +1089,12 @@ int zg_prover_check_circuit(zg_prover *p, size_t count, const zg_fr *const *advi
                             size_t instance_len, const zg_fr *challenges, zg_failure *failures, size_t cap, uint32_t *totals);
 int zg_prover_check_circuit_dev(zg_prover *p, size_t count, void *const *d_advice, const zg_fr *const *instance,
                                 size_t instance_len, const zg_fr *challenges, zg_failure *failures, size_t cap, uint32_t *totals);
+/* input -> check for every circuit the library proves: zg_witness_run_field_dev for the caller's challenge values into
+ * slots 0..count-1, then zg_prover_check_circuit_dev on the slots with the program's instance values.  totals:
+ * [count][4]; challenges: [count][n_challenges], Montgomery form, NULL if and only if the circuit has none; outputs and
+ * the plan's conditions as zg_prover_prove_inputs. */
+int zg_prover_check_inputs(zg_prover *p, zg_witness_plan *plan, const uint8_t *inputs, size_t count, const zg_fr *challenges,
+                           zg_fr *outputs, zg_failure *failures, size_t cap, uint32_t *totals);
 /* Host helper (no device): next_col / next_row [n_perm][2^k] such that sigma_values[c][r] = delta^next_col *
  * omega^next_row -- Assembly::mapping back from what halo2's ProvingKey holds (pk.permutation.permutations).
  * ZG_ERR_INVALID_ARG when a value is no such product. */
